@@ -2,6 +2,7 @@
 """Benchmark of the MI355X resampling hot path (BASELINE.json metric).
 
     python bench.py --gpus N --steps K --warmup W [--config 2|3rx|3tx|5|5h|rx16|rx48|rx96|tx4|tx16|tx32|tx48|tx96]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one streaming pass of the configuration's polyphase FIR (sxfir_decimate / sxfir_interpolate
 through the C ABI: one kernel launch, history carry-over fused) over the rank's resident synthetic IQ block
@@ -20,8 +21,16 @@ under "gather", never part of `value`: it is xGMI-link bound).  W
 torch.distributed environment this script starts the N ranks itself (fresh child processes, before the parent
 touches a GPU); under torchrun it is one of the ranks.  Rank 0 prints ONE JSON line.
 
-After the timed region the outputs of the last step are compared with the CPU oracle (start of the block, a
-window in its middle, its end: the line carries "verified": true, and the script exits non-zero otherwise).
+A plain run sets up, warms up, times the K steps and prints the line: the headline (`value`, `ms_per_step`) and
+the roofline fraction of the same K steps.  --dump-outputs DIR writes what the last timed step computed as
+DIR/<name>.npy (float32, a fixed seeded sample where the whole output is larger than DUMP_BYTES; the inputs are
+seeded, so two builds can be compared output for output).
+
+--full adds everything beside the headline, each in runs of its own after the timed region: the outputs of the
+last step compared with the CPU oracle (start of the block, a window in its middle, its end: the line carries
+"verified": true, and the script exits non-zero otherwise), the other regimes of the kernel, board telemetry and
+the shader clock, the rate table and size curve (config 2), the figures through the Device, the CPU baseline,
+and at N > 1 the per-rank efficiency and the certified gather.
 """
 import argparse
 import json
@@ -39,6 +48,7 @@ HBM_PEAK_GBS = 8000.0                            # MI355X_MICROARCH.md: 8.0 TB/s
 HBM_COPY_GBS = 6290.0                            # measured float4 copy ceiling (same guide)
 VALU_PEAK_TFLOPS = 157.3                         # fp32 vector peak at 2.4 GHz (same guide)
 XGMI_LINK_GBS = 153.0                            # one xGMI link, per direction (7 links per GPU, point to point)
+DUMP_BYTES = 32 << 20                            # --dump-outputs: float32 bytes per run, all files and ranks together
 
 # algorithmic bytes and flops per WIDEBAND-side sample (input of a decimator, output
 # of the interpolator); halo and tap re-reads excluded.
@@ -253,6 +263,35 @@ def load_oracle(fast=False):
     import oracle_lib
     oracle_lib.build()
     return oracle_lib.Oracle(fast=fast)
+
+
+# ----------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path computed, for output-for-output comparison of two builds
+# ----------------------------------------------------------------------------------------------------------
+def dump_index(n, k):
+    """The samples of an n-sample output that --dump-outputs writes: all of them when n <= k, else one from each of
+    k equal strata at a position drawn from a generator seeded with SEED (sorted, the same in every run)."""
+    import numpy as np
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    edges = np.arange(k + 1, dtype=np.int64) * n // k
+    rng = np.random.default_rng(SEED)
+    return edges[:-1] + (rng.random(k) * (edges[1:] - edges[:-1])).astype(np.int64)
+
+
+def dump_outputs(out_dir, arrays, fmt, budget):
+    """Writes every (name, y) of `arrays` -- y: channels x samples on the GPU, CF32 (complex64) or CF16 words (int32) --
+    as out_dir/<name>.npy: float32 of shape (channels, samples, 2), (I, Q) per sample, over the samples dump_index
+    picks so that all files together hold at most `budget` bytes."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for name, y in arrays:
+        nchan, n = y.shape
+        k = max(1, budget // len(arrays) // (8 * nchan))
+        iq = torch.view_as_real(y) if fmt == "CF32" else y.view(torch.float16).view(nchan, n, 2)
+        idx = torch.from_numpy(dump_index(n, k)).to(y.device)
+        np.save(os.path.join(out_dir, name + ".npy"), iq.index_select(1, idx).float().cpu().numpy())
 
 
 def cpu_baseline(cfg, seconds_target=10.0):
@@ -982,26 +1021,30 @@ def main_duplex(args):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     rx_ms, tx_ms = t_rx.elapsed_ms() / args.steps, t_tx.elapsed_ms() / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [("rx_output", yr), ("tx_output", yt)], "CF32", DUMP_BYTES)
 
-    orc = load_oracle()
-    ok_rx, n_rx = verify(rxc, rx_plan, xr, yr, n, 0, True, orc)
-    ok_tx, n_tx = verify(txc, tx_plan, xt, yt, n // 8, 0, True, orc)
-    # each direction alone, same buffers, for the price of sharing the chip
-    alone = {}
-    for name, plan, a, b, ni, no in (("rx", rx_plan, xr, yr, n, n // 8), ("tx", tx_plan, xt, yt, n // 8, n)):
-        plan.reset()
-        torch.cuda.synchronize()
-        alone[name] = plan.time_passes_ptr(a.data_ptr(), ni, ni, b.data_ptr(), no, min(max(args.steps, 40), 200),
-                                           torch.cuda.current_stream(dev).cuda_stream)
-    sampler = BoardSampler(0, 0.02)
-    sampler.start()
-    t_tel = time.perf_counter()
-    while time.perf_counter() - t_tel < 1.0:
-        for _ in range(50):
-            step()
-        torch.cuda.synchronize()
-    board = sampler.stop()
-    verified = ok_rx and ok_tx
+    verified = None
+    if args.full:
+        orc = load_oracle()
+        ok_rx, n_rx = verify(rxc, rx_plan, xr, yr, n, 0, True, orc)
+        ok_tx, n_tx = verify(txc, tx_plan, xt, yt, n // 8, 0, True, orc)
+        # each direction alone, same buffers, for the price of sharing the chip
+        alone = {}
+        for name, plan, a, b, ni, no in (("rx", rx_plan, xr, yr, n, n // 8), ("tx", tx_plan, xt, yt, n // 8, n)):
+            plan.reset()
+            torch.cuda.synchronize()
+            alone[name] = plan.time_passes_ptr(a.data_ptr(), ni, ni, b.data_ptr(), no, min(max(args.steps, 40), 200),
+                                               torch.cuda.current_stream(dev).cuda_stream)
+        sampler = BoardSampler(0, 0.02)
+        sampler.start()
+        t_tel = time.perf_counter()
+        while time.perf_counter() - t_tel < 1.0:
+            for _ in range(50):
+                step()
+            torch.cuda.synchronize()
+        board = sampler.stop()
+        verified = ok_rx and ok_tx
     ms_per_step = elapsed / args.steps * 1e3
     value = 2 * n * args.steps / elapsed / 1e6
     bytes_step = 9.0 * n * 2
@@ -1016,10 +1059,9 @@ def main_duplex(args):
         "metric": "complex MS/s, full-duplex 256-tap decim-by-8 RX + interp-by-8 TX CF32 (wideband rate, both directions)",
         "value": round(value, 1), "unit": "MS/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic", "verified": verified,
+        "dtype": "f32", "data": "synthetic",
         "config": {"workload": "1xMI355X: " + CONFIGS["3"]["name"], "bench_config": "3", "ntaps": 256, "decim": 8, "interp": 8,
                    "format": "CF32", "wideband_samples_per_direction": n, "untimed_settle_launches": args.settle,
-                   "verified_outputs": n_rx + n_tx,
                    "step": "one /8 pass over 2^%d wideband samples on the RX stream and one x8 pass producing 2^%d on the "
                            "TX stream, side by side" % (args.log2_samples, args.log2_samples)},
         "roofline": {
@@ -1030,6 +1072,13 @@ def main_duplex(args):
             "how": "both directions' algorithmic bytes (9 B per wideband sample each) / wall time per step; per direction: "
                    "HIP events on its own stream around the K timed steps / K (the two spans overlap in time)",
             "rx": direction(rx_ms, rxc["kernel"]), "tx": direction(tx_ms, txc["kernel"]),
+            "fp32_TFLOPs": round(128.0 * 2 * n / (ms_per_step * 1e-3) / 1e12, 2),
+        },
+    }
+    if args.full:
+        line["verified"] = verified
+        line["config"]["verified_outputs"] = n_rx + n_tx
+        line["roofline"].update({
             "alone_kernel_ms": {k: round(v, 4) for k, v in alone.items()},
             "sum_alone_ms": round(alone["rx"] + alone["tx"], 4),
             # what running the two directions side by side buys over running them one after the other: the step's wall
@@ -1037,25 +1086,23 @@ def main_duplex(args):
             # package power cap alone, so two streams share one power budget -- "full duplex" here is concurrency of the
             # API (read and write in flight together, SoapySX.cpp:878 / :979), not extra throughput
             "duplex_vs_serial": round(ms_per_step / (alone["rx"] + alone["tx"]), 4),
-            "fp32_TFLOPs": round(128.0 * 2 * n / (ms_per_step * 1e-3) / 1e12, 2),
             "board": board,
-        },
-    }
-    for k in ("power_w", "power_cap_w", "gfx_mhz_smi"):
-        line["roofline"][k] = board.get(k)
-    if not args.no_through_device:
-        try:
-            line["timed_loop"] = duplex_timed_loop()
-            verified = verified and bool(line["timed_loop"].get("latency_check_passed"))
-            line["verified"] = verified
-        except Exception as e:
-            line["timed_loop"] = {"error": "%s: %s" % (type(e).__name__, e)}
-            line["verified"] = verified = False
-    if not args.no_cpu_baseline:
-        line["cpu_baseline"] = cpu_baseline(rxc)
-        line["cpu_baseline"]["note_config3"] = "the RX direction's filter (256-tap decimate-by-8) on the host cores"
+        })
+        for k in ("power_w", "power_cap_w", "gfx_mhz_smi"):
+            line["roofline"][k] = board.get(k)
+        if not args.no_through_device:
+            try:
+                line["timed_loop"] = duplex_timed_loop()
+                verified = verified and bool(line["timed_loop"].get("latency_check_passed"))
+                line["verified"] = verified
+            except Exception as e:
+                line["timed_loop"] = {"error": "%s: %s" % (type(e).__name__, e)}
+                line["verified"] = verified = False
+        if not args.no_cpu_baseline:
+            line["cpu_baseline"] = cpu_baseline(rxc)
+            line["cpu_baseline"]["note_config3"] = "the RX direction's filter (256-tap decimate-by-8) on the host cores"
     print(json.dumps(line), flush=True)
-    if not verified:
+    if verified is False:
         sys.exit(4)
 
 
@@ -1081,6 +1128,12 @@ def main():
                          "128-tap /4 plan runs (a row of its own, not the headline)")
     ap.add_argument("--settle", type=int, default=150,
                     help="untimed launches before the warm-up steps (clock settling)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; a fixed seeded sample where "
+                         "the whole output exceeds %d MiB)" % (DUMP_BYTES >> 20))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: oracle check, kernel regimes, telemetry, "
+                         "rate table, size curve, Device figures, CPU baseline; N > 1: per-rank efficiency and the gather")
     args = ap.parse_args()
     cfg = CONFIGS[args.config]
     if cfg["mode"] == "duplex":
@@ -1206,12 +1259,13 @@ def main():
     # Setup, untimed and independent of --warmup: let the chip's power management settle on this kernel (its
     # time swings 0.49 -> 0.84 -> 0.60 ms over the first ~20 launches, LABBOOK.md section 7); same launches
     # as a step, then the stream restarts at position 0.
-    # The first 20 launches on a chip that has been idle (what a bursty readStream caller sees, the pattern of
+    # --full: the first 20 launches on a chip that has been idle (what a bursty readStream caller sees, the pattern of
     # example/linear_repeater.py:57-69): reported as roofline.kernel_ms_first_20, never part of `value`.
-    time.sleep(0.5)
-    kernel_ms_first_20 = plan.time_passes_ptr(x.data_ptr(), n_in, xs, y.data_ptr(), ys, 20, stream)
-    plan.reset()
-    torch.cuda.synchronize()
+    if args.full:
+        time.sleep(0.5)
+        kernel_ms_first_20 = plan.time_passes_ptr(x.data_ptr(), n_in, xs, y.data_ptr(), ys, 20, stream)
+        plan.reset()
+        torch.cuda.synchronize()
     if args.settle > 0:
         plan.time_passes_ptr(x.data_ptr(), n_in, xs, y.data_ptr(), ys, args.settle, stream)
         plan.reset()
@@ -1220,9 +1274,9 @@ def main():
     # N > 1: per-GPU efficiency measured INSIDE this job (a line from another box differs by the 4-6 % box spread):
     # every rank times its kernel alone while the others idle (turns behind host-side barriers), then all ranks time it
     # together.  Node-level power / thermal coupling is the only thing that can cost per-GPU efficiency on a path with
-    # no data-path collective, and this is what shows it.  Before any data-path collective; never part of `value`.
+    # no data-path collective, and this is what shows it.  Before any data-path collective; never part of `value`.  --full.
     per_rank = None
-    if world > 1:
+    if world > 1 and args.full:
         sampler = BoardSampler(gpu_index, 0.02, bdf=ident.get("pci_bus_id"))
         sampler.start()
 
@@ -1278,46 +1332,52 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if per_rank is not None:
         # every rank's own kernel time over the same K timed steps (HIP events on its stream): the roofline fraction per GPU
         timed = [None] * world
         dist.all_gather_object(timed, float(kernel_ms), group=ctl)
         for r, ms in zip(per_rank, timed):
             r["timed_kernel_ms"] = round(ms, 6)
             r["timed_frac"] = round(cfg["bytes"] * wide_per_gpu / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [("output" if world == 1 else "output_rank%d" % rank, y)], cfg["fmt"],
+                     DUMP_BYTES // world)
 
-    # the last step's output against the oracle (steady-state streaming: the block entered with its own tail
-    # as history, unless it was the very first block of the stream)
-    orc = load_oracle()
-    first_block = (args.warmup + args.steps) <= 1
-    ok1, cmp1 = verify(cfg, plan, x, y, n_in, lo, not first_block, orc)
+    verified = None
+    if args.full:
+        # the last step's output against the oracle (steady-state streaming: the block entered with its own tail
+        # as history, unless it was the very first block of the stream)
+        orc = load_oracle()
+        first_block = (args.warmup + args.steps) <= 1
+        ok1, cmp1 = verify(cfg, plan, x, y, n_in, lo, not first_block, orc)
 
-    # the same launches once more, back to back from one C loop ...
-    plan.reset()
-    torch.cuda.synchronize()
-    iters = min(max(args.steps, 40), 200)
-    kernel_ms_loop = plan.time_passes_ptr(x.data_ptr(), n_in, xs, y.data_ptr(), ys, iters, stream)
-    # ... for about a second more with the board's telemetry sampled beside it (socket power, its cap, the GFX
-    # clock the SMU reports: >= 10 samples) ...
-    board, kernel_ms_telemetry = {"error": "not sampled (rank > 0)"}, None
-    if rank == 0:
-        sampler = BoardSampler(gpu_index, 0.02)
-        sampler.start()
-        t_tel, tel_ms = time.perf_counter(), []
-        while time.perf_counter() - t_tel < 1.0:
-            tel_ms.append(plan.time_passes_ptr(x.data_ptr(), n_in, xs, y.data_ptr(), ys, 100, stream))
-        board = sampler.stop()
-        kernel_ms_telemetry = sum(tel_ms) / len(tel_ms)
-    # ... and once more with the in-kernel shader clock read beside it (a few probe waves on a second stream;
-    # their presence costs the kernel a few per cent, so this pass only supplies the clock)
-    probe = ClockProbe(gpu_index, 8000)
-    kernel_ms_probed = plan.time_passes_ptr(x.data_ptr(), n_in, xs, y.data_ptr(), ys, iters, stream)
-    shader_mhz = probe.read()
-    ok2, cmp2 = verify(cfg, plan, x, y, n_in, lo, False, orc)          # these passes started from zero history
-    verified = ok1 and ok2
-    if world > 1:
-        t = torch.tensor([1.0 if verified else 0.0], dtype=torch.float64, device=cdev)
-        dist.all_reduce(t, op=dist.ReduceOp.MIN)
-        verified = bool(t.item() > 0.5)
+        # the same launches once more, back to back from one C loop ...
+        plan.reset()
+        torch.cuda.synchronize()
+        iters = min(max(args.steps, 40), 200)
+        kernel_ms_loop = plan.time_passes_ptr(x.data_ptr(), n_in, xs, y.data_ptr(), ys, iters, stream)
+        # ... for about a second more with the board's telemetry sampled beside it (socket power, its cap, the GFX
+        # clock the SMU reports: >= 10 samples) ...
+        board, kernel_ms_telemetry = {"error": "not sampled (rank > 0)"}, None
+        if rank == 0:
+            sampler = BoardSampler(gpu_index, 0.02)
+            sampler.start()
+            t_tel, tel_ms = time.perf_counter(), []
+            while time.perf_counter() - t_tel < 1.0:
+                tel_ms.append(plan.time_passes_ptr(x.data_ptr(), n_in, xs, y.data_ptr(), ys, 100, stream))
+            board = sampler.stop()
+            kernel_ms_telemetry = sum(tel_ms) / len(tel_ms)
+        # ... and once more with the in-kernel shader clock read beside it (a few probe waves on a second stream;
+        # their presence costs the kernel a few per cent, so this pass only supplies the clock)
+        probe = ClockProbe(gpu_index, 8000)
+        kernel_ms_probed = plan.time_passes_ptr(x.data_ptr(), n_in, xs, y.data_ptr(), ys, iters, stream)
+        shader_mhz = probe.read()
+        ok2, cmp2 = verify(cfg, plan, x, y, n_in, lo, False, orc)          # these passes started from zero history
+        verified = ok1 and ok2
+        if world > 1:
+            t = torch.tensor([1.0 if verified else 0.0], dtype=torch.float64, device=cdev)
+            dist.all_reduce(t, op=dist.ReduceOp.MIN)
+            verified = bool(t.item() > 0.5)
     achieved = cfg["bytes"] * wide_per_gpu / (kernel_ms * 1e-3) / 1e9
 
     def frac_of(ms):
@@ -1358,7 +1418,6 @@ def main():
             "vs_baseline": None,
             "dtype": "f32",
             "data": "synthetic",
-            "verified": verified,
             "config": {
                 "workload": workload,
                 "bench_config": args.config + ("-asymmetric-taps" if args.asymmetric_taps else ""),
@@ -1367,7 +1426,6 @@ def main():
                 "untimed_settle_launches": args.settle,
                 "narrowband_MS/s": round(value / ratio, 1),
                 "per_gpu_MS/s": round(value / world, 1),
-                "verified_outputs": cmp1 + cmp2,
                 "rccl_ranks": dist.get_world_size() if world > 1 else None,     # the communicator's own count
                 "backend": backend_name,
                 "control_group": ctl_name if world > 1 else None,
@@ -1392,8 +1450,14 @@ def main():
                 "algorithmic_bytes_per_launch": int(cfg["bytes"] * wide_per_gpu),
                 "frac_of_measured_copy_ceiling": round(achieved / HBM_COPY_GBS, 4),
                 "fp32_TFLOPs": round(tflops, 2),
-                "shader_mhz": round(shader_mhz, 0),
                 "kernel_ms_how": "HIP events on the launch stream around the K timed steps (one launch per step) / K",
+            },
+        }
+        if args.full:
+            line["verified"] = verified
+            line["config"]["verified_outputs"] = cmp1 + cmp2
+            line["roofline"].update({
+                "shader_mhz": round(shader_mhz, 0),
                 "kernel_ms_back_to_back_loop": round(kernel_ms_loop, 4),
                 "kernel_ms_first_20": round(kernel_ms_first_20, 4),
                 # the four regimes of the same kernel on this box, as fractions of the 8 TB/s peak, read off one record:
@@ -1411,15 +1475,14 @@ def main():
                 "valu": {"achieved_TFLOPs": round(tflops, 2), "peak_TFLOPs_at_2400MHz": VALU_PEAK_TFLOPS,
                          "frac": round(tflops / VALU_PEAK_TFLOPS, 4),
                          "frac_at_measured_clock": round(tflops / (VALU_PEAK_TFLOPS * shader_mhz / 2400.0), 4)},
-            },
-        }
-        for k in ("power_w", "power_cap_w", "gfx_mhz_smi"):      # the board's own figures beside shader_mhz
-            line["roofline"][k] = board.get(k)
-        if args.config == "5h":
-            line["roofline"]["note"] = ("CF16 storage halves the bytes but not the 128 flop per sample: this leg is "
-                                        "bound by fp32 VALU throughput at the clock the power management allows; "
-                                        "see roofline.valu.  Since round 5 the half -> float conversion is made by the texture "
-                                        "path on the way into LDS (buffer_load_format_x ... lds), not by the VALU")
+            })
+            for k in ("power_w", "power_cap_w", "gfx_mhz_smi"):      # the board's own figures beside shader_mhz
+                line["roofline"][k] = board.get(k)
+            if args.config == "5h":
+                line["roofline"]["note"] = ("CF16 storage halves the bytes but not the 128 flop per sample: this leg is "
+                                            "bound by fp32 VALU throughput at the clock the power management allows; "
+                                            "see roofline.valu.  Since round 5 the half -> float conversion is made by the texture "
+                                            "path on the way into LDS (buffer_load_format_x ... lds), not by the VALU")
         if per_rank is not None:
             # in-job efficiency: every rank's kernel alone (the others idle) against all ranks at once
             ratios = sorted(r["alone_ms"] / r["together_ms"] for r in per_rank)
@@ -1447,12 +1510,12 @@ def main():
                 # a peer block that is not what its sender held: the line must not say verified, and the job fails
                 line["verified"] = False
                 gather_failed["v"] = True
-        if world == 1 and not args.no_through_device:
+        if args.full and world == 1 and not args.no_through_device:
             try:
                 line["through_device"] = through_device()
             except Exception as e:                               # reported beside the value, never able to take it down
                 line["through_device"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and args.config == "2" and not args.no_rate_table and not args.asymmetric_taps:
+        if args.full and world == 1 and args.config == "2" and not args.no_rate_table and not args.asymmetric_taps:
             try:
                 line["size_curve"] = size_curve(dev)
             except Exception as e:
@@ -1461,7 +1524,7 @@ def main():
                 line["rate_table"] = rate_table(orc, dev, log2n=args.log2_samples)
             except Exception as e:
                 line["rate_table"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # rank 0's host cores, at every N: a SCALE line at N > 1 is self-contained
             line["cpu_baseline"] = cpu_baseline(cfg)
         print(json.dumps(line), flush=True)
@@ -1471,7 +1534,7 @@ def main():
     # the gather figures -- and ends the rank with a failure status -- if the collective does not come back.
     gather = None
     gather_failed = {"v": False}
-    if world > 1:
+    if world > 1 and args.full:
         import threading
         finished, stage = threading.Event(), {"name": "serial", "gather": None}
         cert = GatherCertifier(cfg, plan, orc, world, rank, ctl, total_channels, nchan_local, n_in)
@@ -1524,7 +1587,7 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
-    if not verified or gather_failed["v"]:
+    if verified is False or gather_failed["v"]:
         sys.exit(4)
 
 

@@ -10,7 +10,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--steps", "3", "--warmup", "2", "--settle", "4", "--log2-samples", "22", "--no-cpu-baseline",
+SMALL = ["--full", "--steps", "3", "--warmup", "2", "--settle", "4", "--log2-samples", "22", "--no-cpu-baseline",
          "--no-through-device", "--no-rate-table", "--alone-seconds", "0.05"]
 
 
@@ -85,6 +85,60 @@ def test_bench_line_every_config(config):
     assert line["config"]["gpus"] and line["config"]["distinct_gpus"] == 1 and line["config"]["gpu_arch"].startswith("gfx950")
 
 
+def steady_state_output(config, n_in):
+    """What a step of bench.py's timed loop computes once the stream is past its first block: a pass over the block with
+    the block's own tail as filter history (channel 0 of the seeded synthetic stream), as a [1, n_out] tensor."""
+    import torch
+    import bench
+    import sxxcvr_amd
+    from sxxcvr_amd.resampler import DECIMATE, INTERPOLATE
+    cfg = bench.CONFIGS[config]
+    taps = sxxcvr_amd.design_lowpass(cfg["ntaps"], cfg["ratio"], 8.0, cfg["gain"])
+    plan = sxxcvr_amd.Resampler(DECIMATE if cfg["mode"] == "decim" else INTERPOLATE, taps, cfg["ratio"], fmt=cfg["fmt"],
+                                device=0)
+    x = torch.empty((1, n_in), dtype=torch.complex64 if cfg["fmt"] == "CF32" else torch.int32, device="cuda:0")
+    sxxcvr_amd.synth_fill(x, bench.SEED, first_channel=0, start=0, fmt=cfg["fmt"])
+    plan.process(x)
+    return plan.process(x)
+
+
+def dumped_part(y, fmt, n_dumped):
+    """The samples of y that bench.py --dump-outputs writes when it writes n_dumped of them, as it writes them."""
+    import numpy as np
+    import torch
+    import bench
+    iq = torch.view_as_real(y) if fmt == "CF32" else y.view(torch.float16).view(y.shape[0], y.shape[1], 2)
+    iq = iq.float().cpu().numpy()
+    idx = bench.dump_index(y.shape[1], n_dumped)
+    assert idx.size == n_dumped and np.all(np.diff(idx) > 0) and idx[-1] < y.shape[1]
+    return iq[:, idx]
+
+
+@pytest.mark.parametrize("config", ["2", "5h", "3"])
+def test_bench_plain_run_and_its_output_dump(config, tmp_path):
+    """Without --full a run times the K steps and reports the headline, nothing else; --dump-outputs writes what the last
+    timed step computed (float32 (I, Q) pairs; at config 3's TX side, 2^22 outputs, a seeded sample of them)."""
+    import numpy as np
+    line = run_bench(["--config", config, "--steps", "3", "--warmup", "2", "--settle", "4", "--log2-samples", "22",
+                      "--dump-outputs", str(tmp_path)])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert key in line, key
+    assert line["steps"] == 3 and line["warmup"] == 2 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert not {"verified", "cpu_baseline", "through_device", "rate_table", "size_curve", "timed_loop"} & set(line), sorted(line)
+    n = 1 << 22
+    if config == "3":
+        want = {"rx_output": ("3rx", n, 1 << 21), "tx_output": ("3tx", n // 8, 1 << 21)}
+    else:
+        want = {"output": (config, n, 1 << 22)}
+    assert sorted(os.listdir(tmp_path)) == sorted(k + ".npy" for k in want)
+    assert sum(os.path.getsize(os.path.join(tmp_path, k + ".npy")) for k in want) <= 64 << 20
+    for name, (cfg, n_in, budget) in want.items():
+        got = np.load(os.path.join(tmp_path, name + ".npy"))
+        y = steady_state_output(cfg, n_in)
+        assert got.dtype == np.float32 and got.shape == (1, min(y.shape[1], budget), 2), (name, got.shape)
+        assert np.array_equal(got.view(np.uint32), dumped_part(y, line["config"]["format"], got.shape[1]).view(np.uint32)), name
+
+
 def test_bench_line_carries_the_table_of_the_references_rates():
     """The default line (config 2) reports every rate of the reference's table beside the value: twelve rows, each checked
     against the oracle before it is timed."""
@@ -129,7 +183,7 @@ def test_bench_config3_full_duplex_line():
     """BASELINE config 3 as ONE workload: /8 RX and x8 TX side by side on two streams, both verified against the
     oracle, a roofline entry per direction, and the timed readStream -> writeStream loop through the Device with the
     latency check on every block (example/linear_repeater.py:40-69; SoapySX.cpp:950, :1012)."""
-    line = run_bench(["--config", "3", "--steps", "3", "--warmup", "2", "--settle", "4", "--log2-samples", "22",
+    line = run_bench(["--config", "3", "--full", "--steps", "3", "--warmup", "2", "--settle", "4", "--log2-samples", "22",
                       "--no-cpu-baseline"])
     assert line["verified"] is True and line["config"]["bench_config"] == "3" and line["n_gpus"] == 1
     assert "full-duplex" in line["config"]["workload"] and line["config"]["verified_outputs"] >= 8192
@@ -149,7 +203,7 @@ def test_bench_config3_full_duplex_line():
 
 
 def test_bench_reports_device_and_cpu_figures():
-    line = run_bench(["--steps", "3", "--warmup", "2", "--settle", "4", "--log2-samples", "22"], timeout=900)
+    line = run_bench(["--full", "--steps", "3", "--warmup", "2", "--settle", "4", "--log2-samples", "22"], timeout=900)
     assert line["verified"] is True
     c = line["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] >= 1 and c["value"] > 0

@@ -6,7 +6,7 @@
 #   tests[:expr]        pytest -m gpu (optionally -k expr)
 #   testsall            the whole GPU suite without -x;  repeat:expr  the selected tests five times (flakiness)
 #   bench[:config]      bench.py --config C (default 2) without the CPU legs
-#   benchfull           bench.py with everything (the driver's call)
+#   benchfull           bench.py --full: everything
 #   kb32 | kb32h | kb8 | kb16   kbench A/B of the /32 (CF32, CF16), /8, /16 kernels incl. ablations and stamps
 #   kb4                 the /4 production kernel + its memory side;  kb4o  FMA issue-order variants of it
 #   ib8                 interpolator x8 (tiled)
@@ -64,8 +64,8 @@ for S in "$@"; do
     repfile)  for i in 1 2 3 4 5 6 7 8; do timeout 900 python3 -m pytest $ARG -m gpu -q 2>&1 | grep -E "passed|failed|differ" | cut -c1-400 >> $LOG; done; RC=$?; cat $LOG ;;
     devpath)  for n in ${ARG//,/ }; do timeout 300 python3 tools/devpath_probe.py $n 60 >> $LOG 2>&1; done; RC=$?; grep -v amdgpu.ids $LOG | tail -16 ;;
     stress)   timeout 900 python3 tools/stress_direct_rx.py ${ARG//,/ } >> $LOG 2>&1; RC=$?; grep -v amdgpu.ids $LOG | tail -25 ;;
-    bench)    timeout 600 python3 bench.py --config ${ARG:-2} --no-cpu-baseline --no-through-device >> $LOG 2>&1; RC=$?; tail -1 $LOG | cut -c1-1500 ;;
-    benchfull) T0=$(date +%s); timeout 900 python3 bench.py >> $LOG 2>&1; RC=$?; echo "bench.py wall seconds: $(( $(date +%s) - T0 ))" | tee -a $LOG; tail -2 $LOG | cut -c1-3000 ;;
+    bench)    timeout 600 python3 bench.py --full --config ${ARG:-2} --no-cpu-baseline --no-through-device >> $LOG 2>&1; RC=$?; tail -1 $LOG | cut -c1-1500 ;;
+    benchfull) T0=$(date +%s); timeout 900 python3 bench.py --full >> $LOG 2>&1; RC=$?; echo "bench.py wall seconds: $(( $(date +%s) - T0 ))" | tee -a $LOG; tail -2 $LOG | cut -c1-3000 ;;
     kb32)     KB_D=32 timeout 600 python3 tools/kbench.py dense:8:0:0:0 w4:8:0:0:0 dense:8:0:3:0 w4:8:0:3:0 dense:8:0:1:0 dense:8:0:2:0 w4:8:0:1:0 w4:8:0:2:0 dense:4:0:0:0 dense:16:0:0:0 dense:2:0:0:0 >> $LOG 2>&1; RC=$?; grep -v "amdgpu.ids" $LOG | tail -40 ;;
     kb32h)    KB_D=32 KB_FMT=CF16 timeout 600 python3 tools/kbench.py w4:8:0:0:0 w4:8:0:3:0 >> $LOG 2>&1; RC=$?; grep -v "amdgpu.ids" $LOG | tail -12 ;;
     kb8)      KB_D=8 timeout 600 python3 tools/kbench.py dense:8:0:0:0 w4:8:0:0:0 dense:8:0:3:0 w4:8:0:3:0 dense:8:0:1:0 dense:8:0:2:0 w4:8:0:1:0 w4:8:0:2:0 dense:4:0:0:0 dense:16:0:0:0 >> $LOG 2>&1; RC=$?; grep -v "amdgpu.ids" $LOG | tail -24 ;;
