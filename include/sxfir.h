@@ -271,7 +271,10 @@ int sxfir_comm_gather_all(sxfir_comm *const *comms, int ndev, const void *const 
 /* What a call with n_in new input samples would launch NOW (16-byte aligned output assumed): kernel family, tiles, workgroups
  * and how many of those the chip holds at once.  For callers that size their batches (the Device's chains), for
  * tools/sizebench.py, and for the Device's log line when a plan falls to the generic one-output-per-thread kernels
- * (tiled == 0: any ratio outside {4, 8, 16, 32, 48, 96} or taps_per_phase != 32 -- two orders of magnitude slower). */
+ * (tiled == 0: any ratio outside {4, 8, 16, 32, 48, 96} or taps_per_phase != 32 -- two orders of magnitude slower).
+ * A plan whose calls may report split > 1 (the decimators by 48 and 96) is SINGLE-STREAM: its join scratch and arrival counters
+ * belong to one launch at a time, so its calls go to one stream (or are ordered by events); sxfir_reset puts the counters back
+ * to zero with the history. */
 typedef struct sxfir_geometry {
     char kernel[64];          /* kernel family, e.g. "decim_blocks_kernel"; "*_generic_kernel" when tiled == 0 */
     int tiled;                /* 1: an LDS-tiled kernel runs this call; 0: the generic kernel */

@@ -29,6 +29,20 @@ int sxfir_debug_clock(sxfir_plan *plan, double *mhz);
  * FIR arithmetic, output transposition + stores, whole-wave cycles, whole-wave 100 MHz ticks, 0}. */
 int sxfir_debug_stamps(sxfir_plan *plan, unsigned long long *host, size_t capacity_records, size_t *n_records);
 
+/* Test hooks of the (tile, block) join of the decimators by 48 and 96 (decim_blocks_kernel<..., SPLIT>: block values handed from
+ * workgroup to workgroup through the plan's scratch, one arrival counter per tile).  SXFIR_EUNSUPPORTED for a plan without that
+ * scratch.  With them goes the knob SXFIR_BLOCKS_JOIN_DROP=<b>, read when a plan is created: the items of block b count
+ * themselves in without storing their block value where the joiner looks for it (it goes to a side buffer and is copied into
+ * the scratch behind the launch): a hand-off that does not arrive -- the joiner adds what the slot held, the PREVIOUS launch's
+ * value or the poison -- so wrong results on purpose (tests/test_gpu_join.py: the proof that its checker sees one).
+ *   poison:      fills the whole block-value scratch with `word`, asynchronously on `stream` (0x7fc00000: a quiet NaN everywhere);
+ *   counters:    waits for `stream` and returns how many of the plan's arrival counters are not zero (between launches: none);
+ *   set_counter: writes one arrival counter, asynchronously on `stream` (index: channel * tiles of the call + tile).  Only
+ *                sxfir_reset puts a plan right again after this. */
+int sxfir_debug_join_poison(sxfir_plan *plan, uint32_t word, void *stream);
+int sxfir_debug_join_counters(sxfir_plan *plan, long long *nonzero, void *stream);
+int sxfir_debug_join_set_counter(sxfir_plan *plan, long long tile_index, unsigned value, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -123,6 +123,9 @@ def load_sxfir(profiling=False):
     if profiling:
         sig["sxfir_debug_clock"] = (ci, [vp, P(dbl)])
         sig["sxfir_debug_stamps"] = (ci, [vp, P(C.c_ulonglong), sz, P(sz)])
+        sig["sxfir_debug_join_poison"] = (ci, [vp, C.c_uint32, vp])
+        sig["sxfir_debug_join_counters"] = (ci, [vp, P(ll), vp])
+        sig["sxfir_debug_join_set_counter"] = (ci, [vp, ll, C.c_uint, vp])
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError if the symbol is missing
         fn.restype = res

@@ -78,10 +78,24 @@ struct DecimBlocks16 {
 // floats = 16 slots): four per 128-byte-line instruction of the CF32 form.  A block's piece of a row is 64 bytes here -- half a
 // line, the other half the neighbouring block's -- so each line crosses the L2's memory side twice: the bytes of the CF32 form,
 // not half of them (the kernel is arithmetic-bound at either).
+#ifndef SXFIR_PROFILING
 struct DecimBlocksJoin {
     f32x4 *partials;        // [channel][tile][block][256 lanes]: a block value, two outputs per lane
     unsigned *arrived;      // [channel][tile]: items of the tile that have written theirs; the last one resets it to 0
 };
+#else
+// The profiling build's argument carries two more fields -- under ANOTHER TYPE NAME, so that its kernels are other symbols than the
+// product's: both libraries live in one process (tests, tools), a kernel's host stub is a weak template symbol, and with one name
+// the dynamic linker binds the profiling library's launches to libsxfir.so's stub and kernel (112 bytes of arguments, no hook).
+struct DecimBlocksJoinHooked {
+    f32x4 *partials;
+    unsigned *arrived;
+    f32x4 *shadow;          // test hook (SXFIR_BLOCKS_JOIN_DROP): [channel][tile][256 lanes], where the items of block drop_blk put
+    int drop_blk;           // their block value INSTEAD of the scratch -- a hand-off that does not arrive in this launch,
+                            // deterministically (wrong results on purpose; sxfir_launch.hip.h copies it over afterwards); -1 = none
+};
+using DecimBlocksJoin = DecimBlocksJoinHooked;
+#endif
 
 // RP (round 6; what ships -- RP = false is round 5's form, the A/B partner in the profiling build, SXFIR_BLOCKS_RP=0): the eight subsets
 // of a block dealt to the waves by COLUMN GROUP -- wave c runs (p = 1, c) then (p = 0, c) -- instead of by row half.  The two windows
@@ -412,6 +426,9 @@ __global__ __launch_bounds__(256) void decim_blocks_kernel(const DecimMultiArgs 
             const long long slot = ((long long)ch * a.n_tiles + tile) * NB;
             {
                 const f32x4 *q = jn.partials + (slot + blk) * 256 + tid;
+#ifdef SXFIR_PROFILING
+                if (jn.drop_blk == blk) q = jn.shadow + ((long long)ch * a.n_tiles + tile) * 256 + tid;     // (wave-uniform)
+#endif
                 asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(q), "v"(y) : "memory");
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -179,7 +179,11 @@ static int launch_decim(sxfir_plan *p, const void *in_dev, size_t n_in, size_t i
             // /48, /96: sixteen-column blocks, scalar taps from the block-major table of the rotated taps
             if (int rc = need_tap_table(p, TAPS_BLOCKS16, "decim_blocks_kernel")) return rc;
             a.taps = p->taps_scaled_dev;
+#ifdef SXFIR_PROFILING
+            const sxfir::DecimBlocksJoin jn{(sxfir::f32x4 *)p->join_partials, p->join_arrived, (sxfir::f32x4 *)p->join_shadow, p->join_drop};
+#else
             const sxfir::DecimBlocksJoin jn{(sxfir::f32x4 *)p->join_partials, p->join_arrived};
+#endif
             // the lines no other tile reads as non-temporal loads: 2-3 % less time (profiles/round5_rates.txt)
 #define SXFIR_BLOCKS_LAUNCH(NB_, S32_, NT_, HALF_) \
             do { \
@@ -222,6 +226,13 @@ static int launch_decim(sxfir_plan *p, const void *in_dev, size_t n_in, size_t i
             }
 #undef SXFIR_BLOCKS_LAUNCH
             HIPCHECK(hipGetLastError());
+#ifdef SXFIR_PROFILING
+            // test hook: the dropped block's values reach the scratch only now, behind the launch that should have read them -- the
+            // NEXT launch's joiners find them there unless theirs arrive (what a stale hand-off looks like, deterministically)
+            if (p->join_drop >= 0 && geom.split > 1)
+                HIPCHECK(hipMemcpy2DAsync((char *)p->join_partials + 4096 * (size_t)p->join_drop, 4096 * (size_t)p->blocks, p->join_shadow, 4096,
+                                          4096, (size_t)(n_tiles * p->nchan), hipMemcpyDeviceToDevice, st));
+#endif
             *history_done = true;
             return SXFIR_OK;
         }
@@ -451,6 +462,9 @@ int sxfir_decimate(sxfir_plan *p, const void *in_dev, size_t n_in, size_t in_str
     bool history_done = false;
     if (n_out > 0) {
         rc = launch_decim(p, in_dev, n_in, in_stride, out_dev, out_stride, n_out, S(stream), &history_done);
+        // a (tile, block) launch that failed may have left arrival counters half way: the next launch starts from zero again
+        if (rc == SXFIR_EHIP && p->join_arrived)
+            (void)hipMemsetAsync(p->join_arrived, 0, sizeof(unsigned) * (size_t)p->join_tiles, S(stream));
         if (rc) return rc;
     }
     if (!history_done) {

@@ -13,9 +13,14 @@ struct sxfir_plan {
     int jsplit, cw;        // numeric contract
     int rot;               // ... and its rotation (0; 1 for /48, /96: sxfir_contract_rotation)
     void *join_partials;   // /48, /96: scratch of decim_blocks_kernel<..., SPLIT>: join_tiles x blocks block values of 4 KiB
-    unsigned *join_arrived;   // ... and one arrival counter per (channel, tile); zero between launches
+    unsigned *join_arrived;   // ... and one arrival counter per (channel, tile); zero between launches: each tile's last item
+                              // zeroes its own, sxfir_reset and a failed launch zero them all
     long long join_tiles;  // tiles (over all channels) the scratch holds = the largest call the SPLIT form takes
     bool blocks_split;     // (profiling: SXFIR_BLOCKS_SPLIT=0 switches the (tile, block) dealing off)
+#ifdef SXFIR_PROFILING
+    int join_drop;         // SXFIR_BLOCKS_JOIN_DROP=<b> (test hook): the items of block b store their block value to join_shadow instead
+    void *join_shadow;     // of the scratch, where it is copied behind the launch (join_tiles x 4 KiB, allocated with the knob); -1 = off
+#endif
     bool ipass_split;      // x32, x48, x96: (tile, phase block) items for small calls (profiling: SXFIR_IPASS_SPLIT=0 switches it off)
     bool tile_capable;     // decim4_tile_kernel (ratio 4, 128 or 64 taps, CF32)
     bool multi_capable;    // decim_multi_kernel (ratio 8/16/32, 32 taps per phase, CF32)
@@ -167,6 +172,10 @@ int sxfir_create(sxfir_plan **out, int mode, const float *taps, int ntaps, int r
     p->join_arrived = nullptr;
     p->join_tiles = 0;
     p->blocks_split = true;
+#ifdef SXFIR_PROFILING
+    p->join_drop = -1;
+    p->join_shadow = nullptr;
+#endif
     p->ipass_split = true;
 
     if (mode == SXFIR_DECIMATE) {
@@ -394,6 +403,8 @@ int sxfir_create(sxfir_plan **out, int mode, const float *taps, int ntaps, int r
             p->blocks_split = atoi(v) != 0;
             if (atoi(v) > 1) p->join_tiles = (long long)atoi(v) * p->compute_units * p->occ_multi;
         }
+        // test hook: a hand-off that never arrives (tests/test_gpu_join.py proves with it that its checker sees one)
+        if (const char *v = getenv("SXFIR_BLOCKS_JOIN_DROP")) p->join_drop = (atoi(v) >= 0 && atoi(v) < p->blocks) ? atoi(v) : -1;
 #endif
     }
     if (p->tile_capable) {
@@ -556,6 +567,9 @@ int sxfir_create(sxfir_plan **out, int mode, const float *taps, int ntaps, int r
         e = hipMalloc(&p->join_partials, (size_t)p->join_tiles * (size_t)p->blocks * 4096);
         if (e == hipSuccess) e = hipMalloc((void **)&p->join_arrived, sizeof(unsigned) * (size_t)p->join_tiles);
         if (e == hipSuccess) e = hipMemset(p->join_arrived, 0, sizeof(unsigned) * (size_t)p->join_tiles);
+#ifdef SXFIR_PROFILING
+        if (e == hipSuccess && p->join_drop >= 0) e = hipMalloc(&p->join_shadow, (size_t)p->join_tiles * 4096);
+#endif
     }
     if (e == hipSuccess) e = hipMalloc(&p->hist_dev, sample_bytes(fmt) * (size_t)p->hist_len * (size_t)nchan);
     if (e == hipSuccess) e = hipMalloc(&p->hist_alt, sample_bytes(fmt) * (size_t)p->hist_len * (size_t)nchan);
@@ -568,6 +582,9 @@ int sxfir_create(sxfir_plan **out, int mode, const float *taps, int ntaps, int r
         if (p->hist_alt) (void)hipFree(p->hist_alt);
         if (p->join_partials) (void)hipFree(p->join_partials);
         if (p->join_arrived) (void)hipFree(p->join_arrived);
+#ifdef SXFIR_PROFILING
+        if (p->join_shadow) (void)hipFree(p->join_shadow);
+#endif
         delete p;
         return fail(SXFIR_EHIP, "plan allocation failed: %s", hipGetErrorString(e));
     }
@@ -584,6 +601,9 @@ int sxfir_destroy(sxfir_plan *p)
     (void)hipFree(p->hist_alt);
     if (p->join_partials) (void)hipFree(p->join_partials);
     if (p->join_arrived) (void)hipFree(p->join_arrived);
+#ifdef SXFIR_PROFILING
+    if (p->join_shadow) (void)hipFree(p->join_shadow);
+#endif
     delete p;
     return SXFIR_OK;
 }
@@ -593,6 +613,9 @@ int sxfir_reset(sxfir_plan *p, void *stream)
     if (!p) return fail(SXFIR_EINVAL, "plan is NULL");
     HIPCHECK(hipMemsetAsync(p->hist_dev, 0, sample_bytes(p->fmt) * (size_t)p->hist_len * (size_t)p->nchan,
                             S(stream)));
+    // /48, /96: the arrival counters of the (tile, block) join too (16 KiB at 256 CUs) -- a launch that was abandoned, or a plan
+    // that was misused on two streams, must not make the next stream's tiles join early or never
+    if (p->join_arrived) HIPCHECK(hipMemsetAsync(p->join_arrived, 0, sizeof(unsigned) * (size_t)p->join_tiles, S(stream)));
     p->consumed = p->produced = 0;
     return SXFIR_OK;
 }
@@ -661,6 +684,37 @@ int sxfir_debug_stamps(sxfir_plan *p, unsigned long long *host, size_t capacity_
     // records: 5 x uint64 (multi-column kernel, ablate 3) or 8 x uint64 (tile2 kernel, ablate 5)
     HIPCHECK(hipMemcpy(host, p->stamps_dev, (p->ablate == 5 ? 64 : 40) * n, hipMemcpyDeviceToHost));
     *n_records = n;
+    return SXFIR_OK;
+}
+
+// Test hooks of the (tile, block) join of decim_blocks_kernel<..., SPLIT> (tests/gpu_util.py, tools/soak_split.py).
+int sxfir_debug_join_poison(sxfir_plan *p, uint32_t word, void *stream)
+{
+    if (!p) return fail(SXFIR_EINVAL, "plan is NULL");
+    if (!p->join_partials) return fail(SXFIR_EUNSUPPORTED, "this plan has no join scratch");
+    HIPCHECK(hipMemsetD32Async((hipDeviceptr_t)p->join_partials, (int)word, (size_t)p->join_tiles * (size_t)p->blocks * 1024, S(stream)));
+    return SXFIR_OK;
+}
+
+int sxfir_debug_join_counters(sxfir_plan *p, long long *nonzero, void *stream)
+{
+    if (!p || !nonzero) return fail(SXFIR_EINVAL, "NULL argument");
+    if (!p->join_arrived) return fail(SXFIR_EUNSUPPORTED, "this plan has no join scratch");
+    std::vector<unsigned> h((size_t)p->join_tiles);
+    HIPCHECK(hipMemcpyAsync(h.data(), p->join_arrived, sizeof(unsigned) * h.size(), hipMemcpyDeviceToHost, S(stream)));
+    HIPCHECK(hipStreamSynchronize(S(stream)));
+    long long n = 0;
+    for (unsigned v : h) n += v != 0;
+    *nonzero = n;
+    return SXFIR_OK;
+}
+
+int sxfir_debug_join_set_counter(sxfir_plan *p, long long tile_index, unsigned value, void *stream)
+{
+    if (!p) return fail(SXFIR_EINVAL, "plan is NULL");
+    if (!p->join_arrived) return fail(SXFIR_EUNSUPPORTED, "this plan has no join scratch");
+    if (tile_index < 0 || tile_index >= p->join_tiles) return fail(SXFIR_EINVAL, "tile %lld of %lld", tile_index, p->join_tiles);
+    HIPCHECK(hipMemsetD32Async((hipDeviceptr_t)(p->join_arrived + tile_index), (int)value, 1, S(stream)));
     return SXFIR_OK;
 }
 

@@ -135,6 +135,7 @@ class Resampler:
 
     def __init__(self, mode, taps, ratio, nchan=1, fmt="CF32", device=-1, profiling=False):
         self._lib = load_sxfir(profiling)
+        self.profiling = bool(profiling)
         self._plan = C.c_void_p()
         taps = np.ascontiguousarray(taps, dtype=np.float32)
         self.mode, self.ratio, self.nchan, self.fmt, self.ntaps = mode, int(ratio), int(nchan), _FMT[fmt], taps.size
@@ -192,6 +193,26 @@ class Resampler:
 
     def reset(self, stream=None):
         self._ck(self._lib.sxfir_reset(self._plan, C.c_void_p(stream or 0)))
+
+    # -- test hooks of the (tile, block) join of the decimators by 48 and 96 (include/sxfir_prof.h) ----------
+    def _hook(self, name):
+        if not self.profiling:
+            raise RuntimeError("%s exists in the profiling build only: Resampler(..., profiling=True)" % name)
+        return getattr(self._lib, name)
+
+    def join_poison(self, word=0x7FC00000, stream=0):
+        """Fill the plan's block-value scratch with `word` (a quiet NaN in every lane), asynchronously on `stream`."""
+        self._ck(self._hook("sxfir_debug_join_poison")(self._plan, int(word), C.c_void_p(stream or 0)))
+
+    def join_counters(self, stream=0):
+        """Wait for `stream`; how many of the plan's arrival counters are not zero (between launches: none)."""
+        n = C.c_longlong()
+        self._ck(self._hook("sxfir_debug_join_counters")(self._plan, C.byref(n), C.c_void_p(stream or 0)))
+        return n.value
+
+    def join_set_counter(self, tile_index, value, stream=0):
+        """Write one arrival counter (index: channel * tiles of the call + tile); only reset() puts the plan right again."""
+        self._ck(self._hook("sxfir_debug_join_set_counter")(self._plan, int(tile_index), int(value), C.c_void_p(stream or 0)))
 
     def set_history_ptr(self, src_ptr, n, stride, stream=0):
         """The filter state becomes the last samples of the device block [src_ptr, src_ptr + n) of every channel

@@ -32,3 +32,238 @@ def to_gpu(x):
 
 def to_cpu(t):
     return t.cpu().numpy()
+
+
+# ---- the (tile, block) join of the decimators by 48 and 96 (decim_blocks_kernel<..., SPLIT>) --------------------------------
+# One checker for tests/test_gpu_join.py and tools/soak_split.py.  The dealt form hands 4 KiB block values from workgroup to
+# workgroup through the plan's scratch; what could go wrong there is a joiner that reads a block value of an EARLIER launch (stale),
+# half of one (torn) or none, or an arrival counter that is not zero when a launch starts.  So: several DIFFERENT inputs of one
+# geometry in turn (a stale value is then another input's and differs), the scratch poisoned with NaNs before every launch where
+# the library has the hook (a value that was never stored, or is read before it lands, is then a NaN), the destination prefilled
+# with NaNs (an output that was never stored shows), call sizes that change the slots' meaning, a second stream that loads the
+# chip unevenly, back-to-back launches with no host synchronisation, and EVERY output word of every launch compared -- on the GPU,
+# against the bits of another kernel instance (the walking form: one workgroup adds a tile's blocks in registers) which, for CF32,
+# is itself checked against the CPU oracle.
+JOIN_POISON = 0x7FC00000          # a quiet NaN in every fp32 lane of the scratch
+OUT_FILL = 0x7FC07FC0             # a NaN as one fp32 word and as two halves: no kernel output of random data is this word
+TILE_OUT = 512
+
+
+def plan_knobs(**knobs):
+    """Context manager: the environment holds exactly these SXFIR_* knobs (the profiling build reads them when a plan is created)
+    and is put back afterwards."""
+    import contextlib
+    import os
+
+    @contextlib.contextmanager
+    def cm():
+        keep = ("SXFIR_NO_TORCH", "SXFIR_PROF_LIB")
+        saved = {k: v for k, v in os.environ.items() if k.startswith("SXFIR_") and k not in keep}
+        for k in saved:
+            del os.environ[k]
+        os.environ.update({k: str(v) for k, v in knobs.items()})
+        try:
+            yield
+        finally:
+            for k in knobs:
+                os.environ.pop(k, None)
+            os.environ.update(saved)
+    return cm()
+
+
+def join_taps(D):
+    """Asymmetric random taps, 32 per phase."""
+    return (np.random.default_rng(D + 1).standard_normal(32 * D) / 64.0).astype(np.float32)
+
+
+_load_rig = None
+
+
+def _join_load_rig():
+    """The neighbour of the soak: a /4, 128-tap plan of the product library with 2^26 samples of input (made once per process)."""
+    global _load_rig
+    if _load_rig is None:
+        import torch
+        import sxxcvr_amd
+        from sxxcvr_amd.resampler import DECIMATE, KERNEL_TILED
+        plan = sxxcvr_amd.Resampler(DECIMATE, sxxcvr_amd.design_lowpass(128, 4, 8.0, 1.0), 4)
+        plan.set_kernel(KERNEL_TILED)
+        x = torch.empty(1 << 26, dtype=torch.complex64, device="cuda")
+        sxxcvr_amd.synth_fill(x, 0x10AD, 0, 0)
+        y = torch.empty(1 << 24, dtype=torch.complex64, device="cuda")
+        torch.cuda.synchronize()
+        _load_rig = (plan, x, y, torch.cuda.Stream())
+    return _load_rig
+
+
+class JoinSoak:
+    """Inputs and references of one case (ratio D, format, channels, outputs per channel of the full call); run() soaks a plan.
+
+    Inputs: n_inputs windows of one buffer, each `shift` = 4 D x 37 samples after the one before (a multiple of 4 D, no multiple of
+    a tile: what a slot of the scratch held in the last launch is never what it gets in this one).  Call sizes: "full", "one"
+    (one tile) and "few" (five tiles, the last ragged) over the same windows.  References: the walking form of the PROFILING
+    library (SXFIR_BLOCKS_SPLIT=0), one launch per (input, size), kept as whole destination images (the NaN prefill beyond the
+    call's outputs included: a store past the end shows too); for CF32 with `oracle` those are checked against
+    decim_f32 under the contract the plan reports -- everywhere when the call is small, else over five windows of 3000 outputs
+    with the first and the last."""
+
+    def __init__(self, D, fmt, nchan, n_out, oracle=None, n_inputs=3, seed=0x51255):
+        import torch
+        import sxxcvr_amd
+        from sxxcvr_amd.resampler import DECIMATE, KERNEL_TILED
+        assert n_out % 4 == 0 and n_out > 5 * TILE_OUT and n_inputs >= 2
+        self.D, self.fmt, self.nchan, self.n_inputs = D, fmt, nchan, n_inputs
+        self.h = join_taps(D)
+        self.sizes = {"full": n_out, "one": TILE_OUT, "few": 4 * TILE_OUT + 76}
+        self.n_tiles = (n_out + TILE_OUT - 1) // TILE_OUT
+        self.shift = 4 * D * 37
+        assert self.shift % (4 * D) == 0 and self.shift % (TILE_OUT * D) != 0
+        self.total = n_out * D + (n_inputs - 1) * self.shift
+        self.sb = 4 if fmt == "CF16" else 8               # bytes per input sample
+        self.wpo = 1 if fmt == "CF16" else 2              # 32-bit words per output sample
+        if fmt == "S32":
+            g = torch.Generator(device="cuda")
+            g.manual_seed(seed)
+            self.buf = torch.randint(-2 ** 31, 2 ** 31, (nchan, self.total, 2), generator=g, device="cuda").to(torch.int32)
+        elif fmt == "CF16":
+            self.buf = torch.empty((nchan, self.total), dtype=torch.int32, device="cuda")
+            sxxcvr_amd.synth_fill(self.buf, seed, 90, 0, fmt="CF16")
+        else:
+            self.buf = torch.empty((nchan, self.total), dtype=torch.complex64, device="cuda")
+            sxxcvr_amd.synth_fill(self.buf, seed, 90, 0)
+        self.y = torch.empty((nchan, n_out * self.wpo), dtype=torch.int32, device="cuda")
+        self.stream = torch.cuda.Stream()
+        self.stream.wait_stream(torch.cuda.current_stream())
+        with plan_knobs(SXFIR_BLOCKS_SPLIT=0):
+            walk = sxxcvr_amd.Resampler(DECIMATE, self.h, D, nchan=nchan, fmt=fmt, profiling=True)
+        walk.set_kernel(KERNEL_TILED)
+        contract = walk.contract
+        rot = contract.rot                              # (read first: the pair alone does not state a rotated contract)
+        self.contract = tuple(contract) + (rot,)
+        assert self.contract == (2, 4, 1), self.contract
+        self.refs = {}
+        for i in range(n_inputs):
+            for size, n in self.sizes.items():
+                g = walk.geometry(n * D)
+                assert g["kernel"] == "decim_blocks_kernel" and g["split"] == 1, g
+                self.launch(walk, i, size)
+                with torch.cuda.stream(self.stream):
+                    self.refs[i, size] = self.y.clone()
+        self.stream.synchronize()
+        walk.close()
+        for (i, size), r in self.refs.items():
+            n = self.sizes[size] * self.wpo
+            assert int((r[:, :n] == _i32(OUT_FILL)).sum()) == 0, "the walking form left outputs unstored (input %d, %s)" % (i, size)
+            assert int((r[:, n:] != _i32(OUT_FILL)).sum()) == 0, "the walking form stored past its outputs (input %d, %s)" % (i, size)
+        self.oracle_outputs = 0
+        if oracle is not None and fmt == "CF32":
+            self._check_refs(oracle)
+
+    def in_ptr(self, i):
+        return self.buf.data_ptr() + self.sb * self.shift * i
+
+    def launch(self, plan, i, size, poison=False):
+        """Prefill the destination, reset, (poison,) one call of `size` over input i: all on the soak's stream, nothing waits."""
+        import torch
+        s = self.stream.cuda_stream
+        with torch.cuda.stream(self.stream):
+            self.y.fill_(_i32(OUT_FILL))
+        plan.reset(s)
+        if poison:
+            plan.join_poison(JOIN_POISON, s)
+        n = self.sizes[size]
+        got = plan.process_ptr(self.in_ptr(i), n * self.D, self.total, self.y.data_ptr(), self.sizes["full"], s)
+        assert got == n
+
+    def _check_refs(self, oracle):
+        js, cw, rot = self.contract
+        D = self.D
+        th = oracle.max_threads()
+        for (i, size), r in sorted(self.refs.items()):
+            n = self.sizes[size]
+            if n <= 40000:
+                windows = [(0, n)]
+            else:
+                k = 3000
+                windows = [(0, k)] + [((n * j // 4) | 1, k) for j in (1, 2, 3)] + [(n - k, k)]
+            ref = r.cpu().numpy()
+            for c in range(self.nchan):
+                for m0, k in windows:
+                    lead = min(m0, 32)                     # rows of history in front of the window (zero history before the stream)
+                    s0 = self.shift * i + (m0 - lead) * D
+                    x = self.buf[c, s0:s0 + (lead + k) * D].cpu().numpy()
+                    want = oracle.decim_f32(self.h, D, x, js, cw, m0=lead, n_out=k, rot=rot, threads=th)
+                    got = ref[c, 2 * m0:2 * (m0 + k)].view(np.complex64)
+                    assert_bit_exact(got, want, "/%d walking form against the oracle, input %d (%s) channel %d outputs %d.." % (D, i, size, c, m0))
+                    self.oracle_outputs += k
+
+    def check_geometry(self, plan):
+        """Every call size the soak uses takes the dealt form on this plan."""
+        for size, n in self.sizes.items():
+            g = plan.geometry(n * self.D)
+            assert g["kernel"] == "decim_blocks_kernel" and g["split"] == self.D // 16, (size, g)
+
+    def run(self, plan, launches, poison, load, mixed=True, per_tile=False, seconds=None):
+        """`launches` launches (or, with `seconds`, batches of 100 until that long has passed), inputs in turn, every 7th with
+        another call size (mixed); returns {"launches", "bad_words", "counters" (profiling plans, else None)} and, with per_tile
+        (full-size calls only), per launch the number of tiles with a differing word and of tiles whose every word is a NaN."""
+        import time
+        import torch
+        self.check_geometry(plan)
+        if poison and not plan.profiling:
+            raise ValueError("the product library has no poison hook")
+        assert not (per_tile and (mixed or self.fmt == "CF16"))
+        bad = torch.zeros((), dtype=torch.int64, device="cuda")
+        self.stream.wait_stream(torch.cuda.current_stream())
+        tiles_bad, tiles_nan = [], []
+        if load:
+            lplan, lx, ly, lstream = _join_load_rig()
+            order = np.random.default_rng(7).integers(22, 27, size=997)       # 2^22 .. 2^26 samples, a fixed order
+        other = ("one", "few")
+        k, t0 = 0, time.time()
+        while k < launches or (seconds is not None and time.time() - t0 < seconds):
+            for _ in range(min(100, launches - k) if seconds is None else 100):
+                i = k % self.n_inputs
+                size = other[(k // 7) % 2] if (mixed and k % 7 == 6) else "full"
+                if load:
+                    lplan.process_ptr(lx.data_ptr(), 1 << int(order[k % order.size]), 1 << 26, ly.data_ptr(), 1 << 24, lstream.cuda_stream)
+                self.launch(plan, i, size, poison)
+                with torch.cuda.stream(self.stream):
+                    diff = self.y != self.refs[i, size]
+                    bad += diff.sum()
+                    if per_tile:
+                        nan = torch.isnan(self.y.view(torch.float32))
+                        tiles_bad.append(self._by_tile(diff, False).any(-1).sum())
+                        tiles_nan.append(self._by_tile(nan, True).all(-1).sum())
+                k += 1
+        torch.cuda.synchronize()
+        res = {"launches": k, "bad_words": int(bad.item()),
+               "counters": plan.join_counters(self.stream.cuda_stream) if plan.profiling else None}
+        if per_tile:
+            res["tiles_bad"] = [int(t) for t in tiles_bad]
+            res["tiles_nan"] = [int(t) for t in tiles_nan]
+        return res
+
+    def _by_tile(self, flags, fill):
+        """[nchan, words] flags as [nchan, tiles, words per tile], the ragged last tile filled up with `fill`."""
+        import torch
+        per = flags.shape[1] // self.sizes["full"] * TILE_OUT
+        out = torch.full((self.nchan, self.n_tiles * per), fill, dtype=torch.bool, device=flags.device)
+        out[:, :flags.shape[1]] = flags
+        return out.view(self.nchan, self.n_tiles, per)
+
+    def inputs_differ_tiles(self, i, j):
+        """How many (channel, tile) pairs of the full call see different input in windows i and j (their own 512 D samples)."""
+        import torch
+        n = self.sizes["full"] * self.D
+
+        def words(k):
+            w = self.buf[:, self.shift * k:self.shift * k + n]
+            if w.dtype == torch.complex64:
+                w = torch.view_as_real(w).view(torch.int32)
+            return w.reshape(self.nchan, -1)
+        return int(self._by_tile(words(i) != words(j), False).any(-1).sum())
+
+
+def _i32(word):
+    return word - (1 << 32) if word >= 1 << 31 else word

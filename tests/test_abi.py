@@ -28,6 +28,13 @@ def test_sxfir_exports_every_declared_symbol():
     # and the python binding declares a prototype for each of them
     assert set(names) <= set(lib._sx_signatures), set(names) - set(lib._sx_signatures)
     assert lib.sxfir_abi_version() == 6
+    # the profiling build's extra entry points (include/sxfir_prof.h) are in libsxfir_prof.so, bound, and NOT in the product
+    prof = sxxcvr_amd.load_sxfir(profiling=True)
+    extra = sorted(set(_declared("sxfir_prof.h")) - set(names))
+    assert {"sxfir_debug_join_poison", "sxfir_debug_join_counters", "sxfir_debug_join_set_counter"} <= set(extra), extra
+    for n in extra:
+        assert hasattr(prof, n) and n in prof._sx_signatures, "libsxfir_prof.so / its binding lacks " + n
+        assert not hasattr(lib, n), "libsxfir.so exports the profiling entry point " + n
 
 
 def test_time_arithmetic_matches_oracle(oracle):

@@ -403,6 +403,10 @@ def test_blocks_split_and_walking_forms_agree(oracle, monkeypatch, D, fmt, nchan
         plan.set_kernel(KERNEL_TILED)
         g = plan.geometry(D * 512 * 7)
         assert g["kernel"] == "decim_blocks_kernel" and g["split"] == (D // 16 if split == "1" else 1), g
+        contract = plan.contract                        # what sxfir_contract / sxfir_contract_rotation report is what is checked
+        rot = contract.rot
+        assert tuple(contract) == (2, 4) and rot == 1
+        jsplit, cw = contract
         outs, pos = [], 0
         for n in lens:
             blk = x_dev[:, D * pos:D * (pos + n)].contiguous()
@@ -418,7 +422,7 @@ def test_blocks_split_and_walking_forms_agree(oracle, monkeypatch, D, fmt, nchan
     if fmt == "CF32":
         n_chk = sum(lens[:3])
         for c in range(nchan):
-            ref = oracle.decim_f32(h, D, x32[c][:D * n_chk], 2, 4, rot=1)
+            ref = oracle.decim_f32(h, D, x32[c][:D * n_chk], jsplit, cw, rot=rot)
             assert_bit_exact(a[c][:n_chk], ref, "/%d dealt form, channel %d" % (D, c))
 
 
