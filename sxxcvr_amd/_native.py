@@ -119,6 +119,11 @@ def load_sxfir(profiling=False):
         "sxfir_memcpy_h2d": (ci, [vp, vp, sz, vp]),
         "sxfir_memcpy_d2h": (ci, [vp, vp, sz, vp]),
         "sxfir_stream_sync": (ci, [vp]),
+        # include/sxfir_complex.h: complex-tap (band-pass) decimators
+        "sxfir_complex_abi_version": (ci, []),
+        "sxfir_create_complex": (ci, [P(vp), ci, vp, ci, ci, ci, ci, ci]),
+        "sxfir_taps_are_complex": (ci, [vp, P(ci)]),
+        "sxfir_design_bandpass": (ci, [ci, ci, dbl, dbl, ci, ci, vp]),
     }
     if profiling:
         sig["sxfir_debug_clock"] = (ci, [vp, P(dbl)])

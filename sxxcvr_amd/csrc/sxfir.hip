@@ -1,6 +1,7 @@
 // C ABI of the MI355X resampling path (include/sxfir.h).  Host side of the
 // "thin extern C shim": plan bookkeeping, kernel selection and launches.
 #include "../../include/sxfir.h"
+#include "../../include/sxfir_complex.h"
 
 #include <hip/hip_runtime.h>
 
@@ -61,6 +62,7 @@
 #include "sxfir_interp_tile.hip.h"
 #include "sxfir_interp_pass.hip.h"
 #include "sxfir_decim_wide.hip.h"               // /4, 128 symmetric taps: the shipped form since round 4
+#include "sxfir_decim_cx.hip.h"                 // /4, 128 complex taps (include/sxfir_complex.h)
 #ifdef SXFIR_PROFILING
 #include "sxfir_decim_tile2.hip.h"              // round 3's /4 form and its variants: A/B partners of the wide kernel, no instance in the production library since round 4
 #include "experiments/sxfir_decim_pair.hip.h"   // measured variant, not shipped (LABBOOK.md 5.1)
@@ -103,3 +105,4 @@ inline size_t sample_bytes(int fmt) { return fmt == SXFIR_CF16 ? 4 : 8; }   // C
 #include "sxfir_timing.hip.h"    // sxfir_time_*, sxfir_clock_probe_*
 #include "sxfir_runtime.hip.h"   // synthetic source, converters, time arithmetic, tap design, memory / stream / event helpers
 #include "sxfir_comm.hip.h"      // sxfir_comm_*: the RCCL gather
+#include "sxfir_complex.hip.h"   // sxfir_create_complex, sxfir_design_bandpass (include/sxfir_complex.h)

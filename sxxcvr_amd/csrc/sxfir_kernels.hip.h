@@ -104,24 +104,16 @@ __device__ __forceinline__ float2 sample_at(const GenericArgs &a, const void *in
     return make_float2(0.0f, 0.0f);
 }
 
-// One output per thread, any ntaps / ratio / alignment.  Same contract as the
-// tiled kernels: partial[c][p] over rows j descending and phases r descending,
-// adjacent-pair trees over p then c.  (jsplit, cw <= 32 partials each.)
-template <typename F, typename FO = F>
-__global__ __launch_bounds__(256) void decim_generic_kernel(const GenericArgs a)
+// One output of the real-tap decimator under the contract: partial[c][p] over rows j descending and phases r descending,
+// adjacent-pair trees over p then c.  (jsplit, cw <= 32 partials each.)  `taps`: ntaps floats.
+template <typename F>
+__device__ __forceinline__ float2 decim_generic_output(const GenericArgs &a, const float *taps, const void *in, const void *hist,
+                                                       long long newest)
 {
-    const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= a.n_out) return;
-    const int ch = blockIdx.y;
-    const char *in = (const char *)a.in + sizeof(typename F::storage) * a.in_stride * ch;
-    const char *hist = (const char *)a.hist + sizeof(typename F::storage) * a.hist_stride * ch;
-    char *out = (char *)a.out + sizeof(typename FO::storage) * a.out_stride * ch;
-
     const int D = a.ratio;
     const int jt = (a.ntaps + D - 1) / D;
     const int jl = jt / a.jsplit;
     const int ncol = D / a.cw;
-    const long long newest = a.first + m * D;
 
     float ci[32], cq[32];
     for (int c = 0; c < ncol; ++c) {
@@ -135,7 +127,7 @@ __global__ __launch_bounds__(256) void decim_generic_kernel(const GenericArgs a)
                     k += a.rot;
                     if (k >= a.ntaps) k -= a.ntaps;
                     const float2 x = sample_at<F>(a, in, hist, newest - k);
-                    const float t = a.taps[k];
+                    const float t = taps[k];
                     si = __builtin_fmaf(t, x.x, si);
                     sq = __builtin_fmaf(t, x.y, sq);
                 }
@@ -162,7 +154,43 @@ __global__ __launch_bounds__(256) void decim_generic_kernel(const GenericArgs a)
             cq[n / 2] = cq[n - 1];
         }
     }
-    FO::store(out, m, make_float2(ci[0], cq[0]), a.thr2);
+    return make_float2(ci[0], cq[0]);
+}
+
+// One output per thread, any ntaps / ratio / alignment.  Same contract as the
+// tiled kernels.
+template <typename F, typename FO = F>
+__global__ __launch_bounds__(256) void decim_generic_kernel(const GenericArgs a)
+{
+    const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= a.n_out) return;
+    const int ch = blockIdx.y;
+    const char *in = (const char *)a.in + sizeof(typename F::storage) * a.in_stride * ch;
+    const char *hist = (const char *)a.hist + sizeof(typename F::storage) * a.hist_stride * ch;
+    char *out = (char *)a.out + sizeof(typename FO::storage) * a.out_stride * ch;
+    FO::store(out, m, decim_generic_output<F>(a, a.taps, in, hist, a.first + m * a.ratio), a.thr2);
+}
+
+// Complex taps h = a + j b (a.taps: a[0, ntaps) then b[0, ntaps)), one output per thread: A = a (*) x and B = b (*) x are two
+// real-tap outputs under the contract above, one after the other through the same code (one set of partial arrays); then
+// y.re = A.re - B.im, y.im = A.im + B.re, one rounding each, and FO::store rounds to half once for CF16.
+template <typename F, typename FO = F>
+__global__ __launch_bounds__(256) void decim_cx_generic_kernel(const GenericArgs a)
+{
+    const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= a.n_out) return;
+    const int ch = blockIdx.y;
+    const char *in = (const char *)a.in + sizeof(typename F::storage) * a.in_stride * ch;
+    const char *hist = (const char *)a.hist + sizeof(typename F::storage) * a.hist_stride * ch;
+    char *out = (char *)a.out + sizeof(typename FO::storage) * a.out_stride * ch;
+    float2 ab[2] = {make_float2(0.0f, 0.0f), make_float2(0.0f, 0.0f)};
+#pragma nounroll
+    for (int part = 0; part < 2; ++part) {
+        const float2 v = decim_generic_output<F>(a, a.taps + (size_t)part * a.ntaps, in, hist, a.first + m * a.ratio);
+        if (part == 0) ab[0] = v;
+        else ab[1] = v;
+    }
+    FO::store(out, m, make_float2(__fsub_rn(ab[0].x, ab[1].y), __fadd_rn(ab[0].y, ab[1].x)), a.thr2);
 }
 
 // Interpolator, one output per thread: y[n] = sum_j h[j*L + n%L] x[n/L - j],

@@ -46,7 +46,7 @@ struct LaunchGeom {
     long long resident;       // workgroups the chip holds at once, all channels
     int split;                // work items per tile ((tile, block) dealing of decim_blocks_kernel), else 1
 };
-enum { GEOM_GENERIC = 0, GEOM_MULTI = 1, GEOM_WIDE = 2, GEOM_TILE = 3, GEOM_IPASS = 4, GEOM_ITILE = 5 };
+enum { GEOM_GENERIC = 0, GEOM_MULTI = 1, GEOM_WIDE = 2, GEOM_TILE = 3, GEOM_IPASS = 4, GEOM_ITILE = 5, GEOM_CX = 6 };
 
 // Generations of workgroups per launch.  The plan's figure (8) was measured at 2^28 samples; the calls the API issues are 2^17 ..
 // 2^25, and there the kernels whose workgroups pay a heavy prologue per launch (64 taps into VGPRs: decim_dense_kernel<16 / 32>;
@@ -78,6 +78,21 @@ static LaunchGeom decim_geom(const sxfir_plan *p, long long n_out, bool aligned,
     const long long D = p->ratio;
     const long long first = ((p->consumed + D - 1) / D) * D - p->consumed;
     const bool want = p->kernel != SXFIR_KERNEL_GENERIC && first == 0;
+    if (p->cx) {
+        // complex taps (sxfir_create_complex): decim4_cx_kernel for /4 x 128 on CF32, the generic complex kernel for everything else
+        g.kernel = "decim_cx_generic_kernel";
+        if (p->cx_tiled && want && aligned) {
+            g.kind = GEOM_CX;
+            g.kernel = "decim4_cx_kernel";
+            g.tile_out = 512;
+            g.n_tiles = (n_out + 511) / 512;
+            g.resident = (long long)p->compute_units * p->occ_cx;
+            // the wide kernel's sixteen generations of waves at the sizes they were measured at, fewer while that would leave a wave
+            // under four tiles (generations(): a small call is one strided pass of resident waves)
+            g.groups = clamp_groups(g.resident * generations(p, g.n_tiles, g.resident, true) / p->nchan, g.n_tiles);
+        }
+        return g;
+    }
     if (p->multi_capable && want && aligned_multi) {
         g.kind = GEOM_MULTI;
         g.kernel = p->blocks ? "decim_blocks_kernel" : p->dense32 ? "decim_dense_kernel" : "decim_multi_kernel";
@@ -141,6 +156,72 @@ static LaunchGeom interp_geom(const sxfir_plan *p, long long n_in, bool aligned)
     return g;        // (tile size and phase blocks: launch_interp, which alone knows the profiling knobs)
 }
 
+// Complex-tap plans: decim4_cx_kernel (tiles of 512 outputs, one wave per tile and pass, the wide kernel's schedule) or the
+// generic complex kernel.
+static int launch_decim_cx(sxfir_plan *p, const LaunchGeom &geom, const void *in_dev, size_t n_in, size_t in_stride, void *out_dev,
+                           size_t out_stride, long long n_out, long long first, hipStream_t st, bool *history_done)
+{
+    if (p->kernel == SXFIR_KERNEL_TILED && geom.kind != GEOM_CX)
+        return fail(SXFIR_EUNSUPPORTED,
+                    "tiled kernel needs a 16-byte aligned output, an even output stride and a call that starts on "
+                    "an output boundary");
+    if (geom.kind == GEOM_CX) {
+        if (geom.n_tiles > 0x7fffffffLL) return fail(SXFIR_EINVAL, "call too large");
+        sxfir::DecimTileArgs a;
+        memset(&a, 0, sizeof(a));
+        a.in = (const float *)in_dev;
+        a.hist = (const float *)p->hist_dev;
+        a.hist_out = (float *)p->hist_alt;
+        a.out = (float *)out_dev;
+        a.taps = p->taps_dev;                       // a[0, 128) then b[0, 128)
+        a.taps_scaled = nullptr;
+        a.n_in = (long long)n_in;
+        a.n_out = n_out;
+        a.in_stride = (long long)in_stride;
+        a.out_stride = (long long)out_stride;
+        a.hist_stride = p->hist_len;
+        const long long G = geom.groups;
+        a.n_tiles = (int)geom.n_tiles;
+        a.n_waves = (int)G;
+        a.w8 = (G % 8 == 0) ? (int)(G / 8) : 0;
+        {
+            const int t = (int)((geom.n_tiles - 1) % G);
+            a.hist_wave = a.w8 ? (t % a.w8) * 8 + t / a.w8 : t;
+        }
+        hipLaunchKernelGGL(sxfir::decim4_cx_kernel, dim3((unsigned)G, (unsigned)p->nchan), dim3(64), 0, st, a);
+        HIPCHECK(hipGetLastError());
+        *history_done = true;      // caller swaps hist_dev / hist_alt when it commits the call
+        return SXFIR_OK;
+    }
+    sxfir::GenericArgs a;
+    a.in = in_dev;
+    a.hist = p->hist_dev;
+    a.out = out_dev;
+    a.taps = p->taps_dev;                           // a[0, ntaps) then b[0, ntaps)
+    a.n_in = (long long)n_in;
+    a.n_out = n_out;
+    a.in_stride = (long long)in_stride;
+    a.out_stride = (long long)out_stride;
+    a.hist_stride = p->hist_len;
+    a.first = first;
+    a.ntaps = p->ntaps;
+    a.ratio = p->ratio;
+    a.hist_len = p->hist_len;
+    a.jsplit = p->jsplit;
+    a.cw = p->cw;
+    a.rot = p->rot;
+    a.thr2 = p->thr2;
+    const dim3 grid((unsigned)((n_out + 255) / 256), (unsigned)p->nchan);
+    if (p->fmt == SXFIR_CF32)
+        hipLaunchKernelGGL(sxfir::decim_cx_generic_kernel<sxfir::CF32>, grid, dim3(256), 0, st, a);
+    else if (p->fmt == SXFIR_CF16)
+        hipLaunchKernelGGL(sxfir::decim_cx_generic_kernel<sxfir::CF16>, grid, dim3(256), 0, st, a);
+    else
+        hipLaunchKernelGGL((sxfir::decim_cx_generic_kernel<sxfir::S32, sxfir::CF32>), grid, dim3(256), 0, st, a);
+    HIPCHECK(hipGetLastError());
+    return SXFIR_OK;
+}
+
 // Launch only the resampling kernel (no history update, no position change).
 static int launch_decim(sxfir_plan *p, const void *in_dev, size_t n_in, size_t in_stride, void *out_dev,
                         size_t out_stride, long long n_out, hipStream_t st, bool *history_done)
@@ -153,6 +234,7 @@ static int launch_decim(sxfir_plan *p, const void *in_dev, size_t n_in, size_t i
     const LaunchGeom geom = decim_geom(p, n_out, ((uintptr_t)out_dev % 16 == 0) && (p->nchan == 1 || out_stride % 2 == 0),
                                        ((uintptr_t)out_dev % 16 == 0) &&
                                            (p->nchan == 1 || out_stride % (p->fmt == SXFIR_CF16 ? 4 : 2) == 0));
+    if (p->cx) return launch_decim_cx(p, geom, in_dev, n_in, in_stride, out_dev, out_stride, n_out, first, st, history_done);
     const bool tiled = geom.kind == GEOM_WIDE || geom.kind == GEOM_TILE;
     const bool multi = geom.kind == GEOM_MULTI;
     if (multi) {

@@ -119,10 +119,11 @@ static double i0(double x)
     return sum;
 }
 
-int sxfir_design_lowpass(int ntaps, int ratio, double beta, double gain, float *taps)
+// The Kaiser-windowed sinc prototype in fp64, scaled to its gain (sxfir_design_lowpass rounds it to fp32; sxfir_design_bandpass,
+// sxfir_complex.hip.h, turns it by a phasor first).
+static void lowpass_fp64(int ntaps, int ratio, double beta, double gain, std::vector<double> &h)
 {
-    if (ntaps < 1 || ratio < 1 || !taps) return fail(SXFIR_EINVAL, "bad argument");
-    std::vector<double> h((size_t)ntaps);
+    h.resize((size_t)ntaps);
     const double pi = 3.14159265358979323846;
     const double centre = (ntaps - 1) / 2.0;
     const double den = i0(beta);
@@ -137,7 +138,15 @@ int sxfir_design_lowpass(int ntaps, int ratio, double beta, double gain, float *
         h[(size_t)k] = sinc * win / ratio;
         total += h[(size_t)k];
     }
-    for (int k = 0; k < ntaps; ++k) taps[k] = (float)(h[(size_t)k] * (gain / total));
+    for (int k = 0; k < ntaps; ++k) h[(size_t)k] = h[(size_t)k] * (gain / total);
+}
+
+int sxfir_design_lowpass(int ntaps, int ratio, double beta, double gain, float *taps)
+{
+    if (ntaps < 1 || ratio < 1 || !taps) return fail(SXFIR_EINVAL, "bad argument");
+    std::vector<double> h;
+    lowpass_fp64(ntaps, ratio, beta, gain, h);
+    for (int k = 0; k < ntaps; ++k) taps[k] = (float)h[(size_t)k];
     return SXFIR_OK;
 }
 

@@ -1,4 +1,4 @@
-"""Python face of the C ABI in include/sxfir.h.
+"""Python face of the C ABI in include/sxfir.h and include/sxfir_complex.h.
 
 Device memory comes either from torch (complex64 / int32 CUDA tensors, the
 current torch stream is used) or from the library's own sxfir_malloc for
@@ -48,6 +48,16 @@ def design_lowpass(ntaps, ratio, beta=8.0, gain=1.0):
     lib = load_sxfir()
     taps = np.empty(ntaps, dtype=np.float32)
     check(lib.sxfir_design_lowpass(ntaps, ratio, beta, gain, taps.ctypes.data_as(C.c_void_p)))
+    return taps
+
+
+def design_bandpass(ntaps, ratio, num, den, beta=8.0, gain=1.0):
+    """Complex band-pass taps (complex64): the design_lowpass prototype turned to the band centre num/den cycles per INPUT
+    sample (sxfir_design_bandpass); k/ratio is sub-band k of the output raster.  Resampler(DECIMATE, these taps, ratio) takes
+    that band out in one pass and leaves its centre at 0 Hz of the output."""
+    lib = load_sxfir()
+    taps = np.empty(ntaps, dtype=np.complex64)
+    check(lib.sxfir_design_bandpass(ntaps, ratio, beta, gain, int(num), int(den), taps.ctypes.data_as(C.c_void_p)))
     return taps
 
 
@@ -137,10 +147,13 @@ class Resampler:
         self._lib = load_sxfir(profiling)
         self.profiling = bool(profiling)
         self._plan = C.c_void_p()
-        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        # complex-dtype taps: a complex-tap (band-pass) decimator, sxfir_create_complex; real arrays take sxfir_create as ever
+        cx = np.iscomplexobj(taps)
+        taps = np.ascontiguousarray(taps, dtype=np.complex64 if cx else np.float32)
         self.mode, self.ratio, self.nchan, self.fmt, self.ntaps = mode, int(ratio), int(nchan), _FMT[fmt], taps.size
-        self._ck(self._lib.sxfir_create(C.byref(self._plan), mode, taps.ctypes.data_as(C.c_void_p), taps.size,
-                                     int(ratio), int(nchan), self.fmt, int(device)))
+        create = self._lib.sxfir_create_complex if cx else self._lib.sxfir_create
+        self._ck(create(C.byref(self._plan), mode, taps.ctypes.data_as(C.c_void_p), taps.size,
+                        int(ratio), int(nchan), self.fmt, int(device)))
 
     def _ck(self, rc):
         _check(rc, self._lib)      # error text from the library this plan lives in
@@ -165,6 +178,13 @@ class Resampler:
         self._ck(self._lib.sxfir_contract(self._plan, C.byref(a), C.byref(b)))
         self._ck(self._lib.sxfir_contract_rotation(self._plan, C.byref(r)))
         return Contract((a.value, b.value), r.value)
+
+    @property
+    def complex_taps(self):
+        """True for a plan with complex taps (sxfir_taps_are_complex)."""
+        f = C.c_int()
+        self._ck(self._lib.sxfir_taps_are_complex(self._plan, C.byref(f)))
+        return bool(f.value)
 
     @property
     def position(self):
