@@ -22,8 +22,8 @@
 #endif
 
 // Instantiated (ratio, waves per workgroup, CF16, row split) variants of the multi-column decimator: one list
-// for the occupancy query in sxfir_create and the launch in launch_decim.  The production library carries
-// what it launches; the profiling build (-DSXFIR_PROFILING, libsxfir_prof.so: tools/ and
+// for the occupancy query in sxfir_create and the launch in prof_launch_multi.  The production library carries
+// what its kernel table names (sxfir_plan.hip.h); the profiling build (-DSXFIR_PROFILING, libsxfir_prof.so: tools/ and
 // tests/test_gpu_variants.py) adds the A/B variants, the ablation modes and the environment knobs.
 // (shipped: CF16 storage only -- since round 3 every CF32 / S32-word plan at ratio 8, 16, 32 runs decim_dense_kernel,
 // so the multi-column kernel's CF32 and S32 instances exist in the profiling build alone, as the A/B partner)
@@ -100,8 +100,8 @@ inline size_t sample_bytes(int fmt) { return fmt == SXFIR_CF16 ? 4 : 8; }   // C
 
 }  // namespace
 
-#include "sxfir_plan.hip.h"      // struct sxfir_plan, sxfir_create ... sxfir_outputs_for
-#include "sxfir_launch.hip.h"    // launch tables, sxfir_decimate / sxfir_interpolate / sxfir_interpolate_keyed
+#include "sxfir_plan.hip.h"      // struct sxfir_plan, the kernel table, sxfir_create ... sxfir_outputs_for
+#include "sxfir_launch.hip.h"    // launch geometry, argument builders, sxfir_decimate / sxfir_interpolate / sxfir_interpolate_keyed
 #include "sxfir_timing.hip.h"    // sxfir_time_*, sxfir_clock_probe_*
 #include "sxfir_runtime.hip.h"   // synthetic source, converters, time arithmetic, tap design, memory / stream / event helpers
 #include "sxfir_comm.hip.h"      // sxfir_comm_*: the RCCL gather

@@ -1,6 +1,6 @@
 // Complex-tap (band-pass) decimators of the C ABI (include/sxfir_complex.h): plan creation and the band-pass designer.  The plan
-// is an ordinary sxfir_plan with `cx` set -- decim_geom / launch_decim (sxfir_launch.hip.h) send it to decim4_cx_kernel or to
-// decim_cx_generic_kernel, every other entry point takes it as it is.  Included by sxfir.hip last; not a stand-alone translation unit.
+// is an ordinary sxfir_plan with `cx` set -- the kernel table (sxfir_plan.hip.h) gives it decim4_cx_kernel and
+// decim_cx_generic_kernel, decim_geom / launch_decim (sxfir_launch.hip.h) choose between the two per call, every other entry point takes it as it is.  Included by sxfir.hip last; not a stand-alone translation unit.
 #pragma once
 
 extern "C" {
@@ -66,11 +66,8 @@ int sxfir_create_complex(sxfir_plan **out, int mode, const float *taps_iq, int n
             p->cw = ratio;
         }
     }
-    if (p->cx_tiled) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)sxfir::decim4_cx_kernel, 64, 0) == hipSuccess && nb > 0)
-            p->occ_cx = nb;
-    }
+    resolve_kernels(p);
+    query_occupancy(&p->occ_cx, p->k.cx, 64);
 
     // planar on the device: a[0, ntaps) then b[0, ntaps)
     std::vector<float> planar(2 * (size_t)ntaps);

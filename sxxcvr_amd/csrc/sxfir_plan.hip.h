@@ -1,9 +1,25 @@
-// Plan bookkeeping of the C ABI (include/sxfir.h): what a plan holds, how sxfir_create chooses the kernel for a
-// shape (and lays out its tap tables), and the small state entry points (reset, history, position, contract).
+// Plan bookkeeping of the C ABI (include/sxfir.h): what a plan holds, the kernel table (which instance a shape
+// launches: the one statement of it, for the occupancy queries and the launches), how sxfir_create settles a plan's
+// flags and lays out its tap tables, and the small state entry points (reset, history, position, contract).
 // Included by sxfir.hip after the kernel headers; not a stand-alone translation unit.
 #pragma once
 
 enum TapTable { TAPS_SCALED = 0, TAPS_SUBSET8 = 1, TAPS_PASS8 = 2, TAPS_BLOCKS16 = 3 };
+
+// One typed kernel pointer per launch-argument family, and a plan's kernels: resolved once by sxfir_create /
+// sxfir_create_complex (resolve_kernels below), read by the occupancy queries there and by the launches (sxfir_launch.hip.h).
+typedef void (*GenericFn)(sxfir::GenericArgs);
+typedef void (*DecimMultiFn)(sxfir::DecimMultiArgs);
+typedef void (*DecimBlocksFn)(sxfir::DecimMultiArgs, sxfir::DecimBlocksJoin);
+typedef void (*DecimTileFn)(sxfir::DecimTileArgs);
+typedef void (*InterpTileFn)(sxfir::InterpTileArgs);
+struct KernelTable {
+    GenericFn generic;           // decim_generic_kernel / decim_cx_generic_kernel / interp_generic_kernel: every plan has one
+    DecimMultiFn dense;          // decim_dense_kernel (/8, /16, /32)
+    DecimBlocksFn blocks[2];     // decim_blocks_kernel (/48, /96): [0] the walking form, [1] SPLIT, (tile, block) items
+    DecimTileFn tile, wide, cx;  // /4: decim4_tile_kernel, decim4_wide_kernel, decim4_cx_kernel (complex taps)
+    InterpTileFn interp[2][2];   // [keyed][split]: interp8_pass_kernel; interp_tile_kernel on CF16 storage ([0][0] alone)
+};
 
 struct sxfir_plan {
     int mode, ntaps, ratio, nchan, fmt, device;
@@ -72,11 +88,152 @@ struct sxfir_plan {
     int occ_cx;               // its resident waves per CU
     void *hist_dev;        // current history: nchan * hist_len samples
     void *hist_alt;        // the tile kernel writes the next history here, then the two swap
+    KernelTable k;         // the instances this plan launches (null: none in this build for that family)
     long long consumed, produced;
 };
 
-extern "C" {
+// ---- The kernel table: for each family ONE function from a shape (mode, ratio, ntaps, fmt, symmetric, cx; for the
+// interpolators also the two run-time selectors, keyed and split) to the instance that ships.  This is the only place where
+// the product's template argument lists are written.  nullptr: no instance for that shape in the production library (its A/B
+// partners are launched by the profiling build's hooks, sxfir_prof_dispatch.inc); launch() refuses a null entry.
+//
+// Occupancy (sxfir_create) is queried on the entry of a plan's BASE form, which is not always the instance a call launches:
+// the walking, non-SPLIT form for /48 and /96; interp_kernel(16, CF32, unkeyed, walking) for every x16 .. x96 plan whatever its
+// ratio, format or keying, (8, CF32, ...) for x8 and (4, CF32, ...) for x4; decim4_tile_kernel's CF32 instance for S32 words too.
+// The launch geometry of every plan was measured with these figures.
+static GenericFn generic_kernel(int mode, int fmt, bool cx)
+{
+    using namespace sxfir;
+    if (cx) {
+        if (fmt == SXFIR_CF32) return decim_cx_generic_kernel<CF32>;
+        if (fmt == SXFIR_CF16) return decim_cx_generic_kernel<CF16>;
+        return decim_cx_generic_kernel<S32, CF32>;
+    }
+    if (mode == SXFIR_DECIMATE) {
+        if (fmt == SXFIR_CF32) return decim_generic_kernel<CF32>;
+        if (fmt == SXFIR_CF16) return decim_generic_kernel<CF16>;
+        return decim_generic_kernel<S32, CF32>;
+    }
+    if (fmt == SXFIR_CF32) return interp_generic_kernel<CF32>;
+    if (fmt == SXFIR_CF16) return interp_generic_kernel<CF16>;
+    return interp_generic_kernel<CF32, S32>;
+}
 
+// /8, /16, /32 with 32 taps per phase: decim_dense_kernel, non-temporal staging loads for the image rows no other tile reads
+// (NTLD = 2: both halos stay plain loads; round 4, profiles/round4h_kbench_both_halos_plain.txt: whole kernel -0.9 % at /32,
+// -2.8 % at /8 and /16 against plain loads).  /8 is the scalar-tap SUBSET form; CF16 storage: the typed LDS-DMA front end (HALFIN).
+template <int D, bool SUBSET>
+static DecimMultiFn dense_kernel_for(int fmt)
+{
+    if (fmt == SXFIR_CF16) return sxfir::decim_dense_kernel<D, 0, false, 2, SUBSET, false, true>;
+    if (fmt == SXFIR_S32) return sxfir::decim_dense_kernel<D, 0, true, 2, SUBSET>;
+    return sxfir::decim_dense_kernel<D, 0, false, 2, SUBSET>;
+}
+static DecimMultiFn dense_kernel(int ratio, int fmt)
+{
+    return ratio == 8 ? dense_kernel_for<8, true>(fmt) : ratio == 16 ? dense_kernel_for<16, false>(fmt) : ratio == 32 ? dense_kernel_for<32, false>(fmt) : nullptr;
+}
+
+// /48, /96: decim_blocks_kernel<NB, S32IN, NTLD, HALFIN, SPLIT, RP>, the lines no other tile reads as non-temporal loads (2-3 %
+// less time, profiles/round5_rates.txt), waves by column group (RP, round 6)
+template <int NB, bool SPLIT>
+static DecimBlocksFn blocks_kernel_for(int fmt)
+{
+    if (fmt == SXFIR_CF16) return sxfir::decim_blocks_kernel<NB, false, true, true, SPLIT, true>;
+    if (fmt == SXFIR_S32) return sxfir::decim_blocks_kernel<NB, true, true, false, SPLIT, true>;
+    return sxfir::decim_blocks_kernel<NB, false, true, false, SPLIT, true>;
+}
+static DecimBlocksFn blocks_kernel(int blocks, int fmt, bool split)
+{
+    if (blocks == 3) return split ? blocks_kernel_for<3, true>(fmt) : blocks_kernel_for<3, false>(fmt);
+    if (blocks == 6) return split ? blocks_kernel_for<6, true>(fmt) : blocks_kernel_for<6, false>(fmt);
+    return nullptr;
+}
+
+// /4, four outputs per lane: the VGPR-tap form for any 128 or 64 taps
+static DecimTileFn tile_kernel(int ntaps, int fmt)
+{
+    if (fmt == SXFIR_S32) return sxfir::decim4_tile_kernel<128, false, 0, true>;
+    if (ntaps == 128) return sxfir::decim4_tile_kernel<128, false>;
+    return sxfir::decim4_tile_kernel<64, false>;
+}
+
+// /4, 128 taps, eight outputs per lane (sxfir_decim_wide.hip.h): all 64 distinct taps of a bit-symmetric filter (every linear-phase
+// design) in SGPR pairs; 18.5 KB of LDS per wave -> 8 waves per CU.  Its ASYM form (round 5: taps 127..64 in SGPR pairs, taps 63..0 in
+// VGPR pairs) ships for CF16 storage only, where it beats the multi-column kernel by 3 %; on CF32 and S32 words it measured 1.4 %
+// slower / 0.7 % faster than decim4_tile_kernel<128> (profiles/round5_kbench_asym.txt), which therefore keeps the non-symmetric
+// 128-tap plans (the instances exist in the profiling build: SXFIR_WIDE_ASYM=1)
+static DecimTileFn wide_kernel(int fmt, bool symmetric)
+{
+    if (!symmetric) return fmt == SXFIR_CF16 ? sxfir::decim4_wide_kernel<0, false, 24, true, false, 0, true, true> : nullptr;
+    if (fmt == SXFIR_S32) return sxfir::decim4_wide_kernel<0, true>;
+    if (fmt == SXFIR_CF16) return sxfir::decim4_wide_kernel<0, false, 24, true, false, 0, true>;
+    return sxfir::decim4_wide_kernel<0, false>;
+}
+
+// Interpolators with 32 taps per phase.  CF32 / S32 words: interp8_pass_kernel<QI, KEYED, S32OUT, COUNTED, LL, LT, PBSPLIT> -- x4
+// with four inputs per lane and two passes, x8 with two inputs per lane and four passes, x16 .. x96 over ratio / 16 phase blocks of
+// sixteen per tile, walked or (x32, x48, x96: split) dealt.  CF16 storage: interp_tile_kernel with the typed LDS-DMA front end and
+// half stores, x48 / x96 as three phase blocks of its x16 / x32 form; the keying count is defined on CF32 input.
+template <bool KEYED, bool S32OUT>
+static InterpTileFn interp_pass_kernel_for(int ratio, bool split)
+{
+    using namespace sxfir;
+    switch (ratio + (split ? 1000 : 0)) {
+    case 4: return interp8_pass_kernel<4, KEYED, S32OUT, true, 4>;
+    case 8: return interp8_pass_kernel<2, KEYED, S32OUT>;
+    case 16: return interp8_pass_kernel<2, KEYED, S32OUT, true, 16, 16>;
+    case 32: return interp8_pass_kernel<2, KEYED, S32OUT, true, 16, 32>;
+    case 48: return interp8_pass_kernel<2, KEYED, S32OUT, true, 16, 48>;
+    case 96: return interp8_pass_kernel<2, KEYED, S32OUT, true, 16, 96>;
+    case 1032: return interp8_pass_kernel<2, KEYED, S32OUT, true, 16, 32, true>;
+    case 1048: return interp8_pass_kernel<2, KEYED, S32OUT, true, 16, 48, true>;
+    case 1096: return interp8_pass_kernel<2, KEYED, S32OUT, true, 16, 96, true>;
+    }
+    return nullptr;
+}
+static InterpTileFn interp_kernel(int ratio, int fmt, bool keyed, bool split)
+{
+    using namespace sxfir;
+    if (fmt == SXFIR_S32) return keyed ? interp_pass_kernel_for<true, true>(ratio, split) : interp_pass_kernel_for<false, true>(ratio, split);
+    if (fmt == SXFIR_CF32) return keyed ? interp_pass_kernel_for<true, false>(ratio, split) : interp_pass_kernel_for<false, false>(ratio, split);
+    if (keyed || split) return nullptr;
+    switch (ratio) {
+    case 4: return interp_tile_kernel<4, false, false, 4, true>;
+    case 8: return interp_tile_kernel<8, false, false, 8, true>;
+    case 16: return interp_tile_kernel<16, false, false, 16, true>;
+    case 32: return interp_tile_kernel<32, false, false, 32, true>;
+    case 48: return interp_tile_kernel<16, false, false, 48, true>;
+    case 96: return interp_tile_kernel<32, false, false, 96, true>;
+    }
+    return nullptr;
+}
+
+// The plan's kernels, from the capability flags sxfir_create has settled (the profiling knobs included)
+static void resolve_kernels(sxfir_plan *p)
+{
+    KernelTable &k = p->k;
+    k = KernelTable{};
+    k.generic = generic_kernel(p->mode, p->fmt, p->cx);
+    if (p->cx_tiled) k.cx = sxfir::decim4_cx_kernel;
+    if (p->dense32) k.dense = dense_kernel(p->ratio, p->fmt);
+    for (int split = 0; split < 2; ++split) k.blocks[split] = blocks_kernel(p->blocks, p->fmt, split != 0);
+    if (p->tile_capable) k.tile = tile_kernel(p->ntaps, p->fmt);
+    if (p->tile_capable && p->ntaps == 128) k.wide = wide_kernel(p->fmt, p->symmetric);
+    if (p->itile_capable)
+        for (int keyed = 0; keyed < 2; ++keyed)
+            for (int split = 0; split < 2; ++split) k.interp[keyed][split] = interp_kernel(p->ratio, p->fmt, keyed != 0, split != 0);
+}
+
+// resident workgroups per CU of a kernel; *occ keeps its default where the runtime has no answer
+template <typename Fn>
+static void query_occupancy(int *occ, Fn kernel, int threads, size_t dynamic_lds = 0)
+{
+    int nb = 0;
+    if (kernel && hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kernel, threads, dynamic_lds) == hipSuccess && nb > 0) *occ = nb;
+}
+
+extern "C" {
 
 int sxfir_abi_version(void) { return SXFIR_ABI_VERSION; }
 
@@ -146,7 +303,7 @@ int sxfir_create(sxfir_plan **out, int mode, const float *taps, int ntaps, int r
         return fail(SXFIR_ENODEVICE, "device %d is %s; kernels are built for gfx950 only", device,
                     prop.gcnArchName);
 
-    sxfir_plan *p = new (std::nothrow) sxfir_plan();
+    sxfir_plan *p = new (std::nothrow) sxfir_plan();       // value-initialised: every flag, pointer, counter and knob starts at zero
     if (!p) return fail(SXFIR_ENOMEM, "out of host memory");
     p->mode = mode;
     p->ntaps = ntaps;
@@ -156,28 +313,14 @@ int sxfir_create(sxfir_plan **out, int mode, const float *taps, int ntaps, int r
     p->device = device;
     p->kernel = SXFIR_KERNEL_AUTO;
     p->compute_units = prop.multiProcessorCount;
-    p->consumed = p->produced = 0;
-    p->taps_dev = nullptr;
-    p->taps_scaled_dev = nullptr;
-    p->ipass = false;
-    p->ipass_wait0 = false;
     p->occ_ipass = 16;
     p->ipass_qi = 2;
     p->symmetric = true;
     for (int k = 0; k < ntaps / 2; ++k)
         if (memcmp(&taps[k], &taps[ntaps - 1 - k], sizeof(float)) != 0) p->symmetric = false;
-    p->hist_dev = nullptr;
-    p->hist_alt = nullptr;
-    p->itile_capable = false;
-    p->blocks = 0;
-    p->rot = 0;
-    p->join_partials = nullptr;
-    p->join_arrived = nullptr;
-    p->join_tiles = 0;
     p->blocks_split = true;
 #ifdef SXFIR_PROFILING
     p->join_drop = -1;
-    p->join_shadow = nullptr;
 #endif
     p->ipass_split = true;
 
@@ -241,15 +384,9 @@ int sxfir_create(sxfir_plan **out, int mode, const float *taps, int ntaps, int r
     // measured on MI355X (tools/kbench.py): single-buffered LDS-DMA at 16 waves/CU, 16 generations
     // of short-lived waves (4 tiles each at 2^28 samples), strided XCD-blocked passes; the
     // double-buffered variant at 8 waves/CU and long contiguous runs are slower
-    p->tile_dbuf = false;
     p->occ_sb = p->occ_db = 8;
     p->oversub = 16;
-    p->ablate = 0;
-    p->sched = 0;
-    p->sgpr_r = 0;
     p->thr2 = 1.0e-3f * 1.0e-3f;
-    p->stamps_dev = nullptr;
-    p->stamps_n = 0;
     // waves per workgroup of the multi-column kernel, measured (tools/kbench.py, KB_D, specs "w1".."w8"):
     // the choice that brings the LDS image down to 10 KiB per wave (16 waves per CU) while the 31-row
     // halo stays a small part of the staging
@@ -261,21 +398,8 @@ int sxfir_create(sxfir_plan **out, int mode, const float *taps, int ntaps, int r
     // (HALFIN: the texture path converts half -> float on the way into the same CF32 image; no conversions in the FIR)
     p->dense32 = p->multi_capable && !p->blocks && (ratio == 8 || ratio == 16 || ratio == 32);
     // /8 CF32: the scalar-tap form of the dense kernel (tap subsets on the four waves, round 4: 4.4-5 % less time)
-    p->dense_hc = false;
     p->dense_subset = p->dense32 && ratio == 8;      // (CF16 storage too, round 5: the typed-DMA front end under the same scalar-tap FIR)
-    p->t2_wpg = p->t2_opt = 0;
-    p->dense_nt = 0;
-    p->dense_nt_set = 0;
-    p->lds_pad = 0;
-    p->pair = false;
-    p->pair_xsep = false;
     p->occ_pair = 8;
-    p->wide8 = false;
-    p->wide = false;
-    p->wide_nt = false;
-    p->wide_pin = false;
-    p->wide_pol = 0;
-    p->wide_nb = 0;
     p->occ_wide = 8;
     p->occ_multi = 2;
     // generations of workgroups per launch, measured (tools/kbench.py): the multi-column kernel's prologue
@@ -283,32 +407,15 @@ int sxfir_create(sxfir_plan **out, int mode, const float *taps, int ntaps, int r
     // interpolator is flat between 2 and 16 (tools/ibench.py)
     if (p->multi_capable) p->oversub = 8;
     if (p->itile_capable) p->oversub = ratio > 32 ? 2 : 4;     // (x48, x96: 2 measured 1-2 % ahead of 4 .. 32, profiles/round5_rates.txt)
-    if (p->itile_capable && ratio == 8 && (fmt == SXFIR_CF32 || fmt == SXFIR_S32)) {
+    // CF32 / S32 words: the scalar-tap pass kernel (interp8_pass_kernel) at every ratio -- x8 (two inputs per lane, four passes per
+    // tile; 4 / 8 / 16 generations measured within 0.3 %, tools/ibench2.py), x4 (round 5: four inputs per lane, two passes) and
+    // x16 .. x96 (round 5: ratio / 16 phase blocks of sixteen per tile, a lane's sixteen outputs per input and block are one line:
+    // 8-9 % less time than interp_tile_kernel, which keeps CF16 storage, profiles/round5_rates.txt)
+    if (p->itile_capable && fmt != SXFIR_CF16) {
         p->ipass = true;
-        p->oversub = 8;                                 // measured (tools/ibench2.py): 4 / 8 / 16 generations within 0.3 %
-        int nbi = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbi, (const void *)sxfir::interp8_pass_kernel<2>, 64, 0) == hipSuccess && nbi > 0)
-            p->occ_ipass = nbi;
-    }
-    // x16 .. x96 (round 5): the pass kernel over ratio / 16 phase blocks of sixteen per tile (a lane's sixteen outputs per input
-    // and block are one line): 8-9 % less time than interp_tile_kernel, which keeps CF16 storage (profiles/round5_rates.txt)
-    if (p->itile_capable && ratio >= 16 && (fmt == SXFIR_CF32 || fmt == SXFIR_S32)) {
-        p->ipass = true;
-        p->ipass_qi = 2;
+        p->ipass_qi = ratio == 4 ? 4 : 2;
         p->oversub = 8;
-        int nbi = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbi, (const void *)sxfir::interp8_pass_kernel<2, false, false, true, 16, 16>, 64, 0) == hipSuccess && nbi > 0)
-            p->occ_ipass = nbi;
-    }
-    // x4, 128 taps (round 5): the same scalar-tap pass form with four inputs per lane (two passes; a lane's sixteen outputs are
-    // one line)
-    if (p->itile_capable && ratio == 4 && (fmt == SXFIR_CF32 || fmt == SXFIR_S32)) {
-        p->ipass = true;
-        p->ipass_qi = 4;
-        p->oversub = 8;
-        int nbi = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbi, (const void *)sxfir::interp8_pass_kernel<4, false, false, true, 4>, 64, 0) == hipSuccess && nbi > 0)
-            p->occ_ipass = nbi;
+        query_occupancy(&p->occ_ipass, interp_kernel(ratio < 16 ? ratio : 16, SXFIR_CF32, false, false), 64);
     }
 #ifdef SXFIR_PROFILING
     // A/B knobs of the profiling build.  The production library never looks at the environment.
@@ -324,9 +431,7 @@ int sxfir_create(sxfir_plan **out, int mode, const float *taps, int ntaps, int r
         p->ipass = p->ipass && atoi(v) != 0;
         if (p->ipass && atoi(v) == 4 && ratio == 8) {
             p->ipass_qi = 4;
-            int nbi = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbi, (const void *)sxfir::interp8_pass_kernel<4>, 64, 0) == hipSuccess && nbi > 0)
-                p->occ_ipass = nbi;
+            query_occupancy(&p->occ_ipass, sxfir::interp8_pass_kernel<4>, 64);
         }
     }
     if (const char *v = getenv("SXFIR_IPASS_WAIT0")) p->ipass_wait0 = atoi(v) != 0;
@@ -349,38 +454,19 @@ int sxfir_create(sxfir_plan **out, int mode, const float *taps, int ntaps, int r
         if (const char *v = getenv("SXFIR_ABLATE")) p->ablate = atoi(v);
     }
 #endif
+    resolve_kernels(p);
     if (p->multi_capable) {
         // resident workgroups per CU: LDS is the limiter (checked against the occupancy API below)
         const int W = p->multi_waves;
-        int nb = 0;
-        const void *k = nullptr;
-        if (p->blocks) {
-            const bool w = fmt == SXFIR_S32;
+        const void *k = p->blocks ? (const void *)p->k.blocks[0] : (const void *)p->k.dense;
 #ifdef SXFIR_PROFILING
-            if (p->blocks < 3)       // (the unrotated instances have the same resources)
-                k = p->blocks == 1 ? (const void *)sxfir::decim_blocks_kernel<1, false, true, false, false, true> : (const void *)sxfir::decim_blocks_kernel<2, false, true, false, false, true>;
-            else
-#endif
-            k = p->blocks == 3 ? (w ? (const void *)sxfir::decim_blocks_kernel<3, true, true, false, false, true> : (const void *)sxfir::decim_blocks_kernel<3, false, true, false, false, true>)
-                               : (w ? (const void *)sxfir::decim_blocks_kernel<6, true, true, false, false, true> : (const void *)sxfir::decim_blocks_kernel<6, false, true, false, false, true>);
-            if (fmt == SXFIR_CF16 && p->blocks >= 3)
-                k = p->blocks == 3 ? (const void *)sxfir::decim_blocks_kernel<3, false, true, true, false, true> : (const void *)sxfir::decim_blocks_kernel<6, false, true, true, false, true>;
-        } else if (p->dense32 && fmt == SXFIR_CF16) {
-            k = ratio == 8    ? (const void *)sxfir::decim_dense_kernel<8, 0, false, 2, true, false, true>
-                : ratio == 16 ? (const void *)sxfir::decim_dense_kernel<16, 0, false, 2, false, false, true>
-                              : (const void *)sxfir::decim_dense_kernel<32, 0, false, 2, false, false, true>;
-        } else if (p->dense32) {
-            const bool w = fmt == SXFIR_S32;
-            k = ratio == 8    ? (w ? (const void *)sxfir::decim_dense_kernel<8, 0, true, 2, true> : (const void *)sxfir::decim_dense_kernel<8, 0, false, 2, true>)
-                : ratio == 16 ? (w ? (const void *)sxfir::decim_dense_kernel<16, 0, true, 2> : (const void *)sxfir::decim_dense_kernel<16, 0, false, 2>)
-                              : (w ? (const void *)sxfir::decim_dense_kernel<32, 0, true, 2> : (const void *)sxfir::decim_dense_kernel<32, 0, false, 2>);
-#ifdef SXFIR_PROFILING
-        } else if (fmt == SXFIR_S32) {   // wire-word input: one instantiation per ratio (4 waves, 2-way row split)
+        if (p->blocks && p->blocks < 3) {       // (the unrotated instances have the same resources)
+            k = p->blocks == 1 ? (const void *)sxfir::decim_blocks_kernel<1, false, true, false, false, true> : (const void *)sxfir::decim_blocks_kernel<2, false, true, false, false, true>;
+        } else if (!p->blocks && !p->dense32 && fmt == SXFIR_S32) {   // wire-word input: one instantiation per ratio (4 waves, 2-way row split)
             k = ratio == 8    ? (const void *)sxfir::decim_multi_kernel<8, 4, false, 0, 2, true>
                 : ratio == 16 ? (const void *)sxfir::decim_multi_kernel<16, 4, false, 0, 2, true>
                               : (const void *)sxfir::decim_multi_kernel<32, 4, false, 0, 2, true>;
-#endif
-        } else {
+        } else if (!p->blocks && !p->dense32) {
             switch (SXFIR_MULTI_KEY(ratio, W, fmt == SXFIR_CF16, p->multi_ps)) {
 #define SXFIR_X(DD, WW, HH, PP) \
             case SXFIR_MULTI_KEY(DD, WW, HH, PP): k = (const void *)sxfir::decim_multi_kernel<DD, WW, HH, 0, PP>; break;
@@ -388,11 +474,12 @@ int sxfir_create(sxfir_plan **out, int mode, const float *taps, int ntaps, int r
 #undef SXFIR_X
             }
         }
+#endif
         if (!k) {
             delete p;
             return fail(SXFIR_EUNSUPPORTED, "no multi-column kernel for ratio %d with %d waves per workgroup", ratio, W);
         }
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, 64 * W, 0) == hipSuccess && nb > 0) p->occ_multi = nb;
+        query_occupancy(&p->occ_multi, k, 64 * W);
     }
     if (p->blocks) {
         // calls of at most eight times as many tiles as the chip has workgroup slots are dealt as (tile, block) items (SPLIT).
@@ -411,47 +498,32 @@ int sxfir_create(sxfir_plan **out, int mode, const float *taps, int ntaps, int r
 #endif
     }
     if (p->tile_capable) {
-        int nb = 0;
-        // the 4-outputs-per-lane kernels: the VGPR-tap form for any 128 or 64 taps -- and, in the profiling build, round 3's
+        // the 4-outputs-per-lane kernels (the CF32 instance's figure: see the kernel table) -- and, in the profiling build, round 3's
         // scalar-tap form for 128 symmetric taps ("t2s"), the A/B partner of the wide kernel that replaced it
-        const void *ksb = ntaps == 128 ? (const void *)sxfir::decim4_tile_kernel<128, false> : (const void *)sxfir::decim4_tile_kernel<64, false>;
+        const void *ksb = (const void *)tile_kernel(ntaps, SXFIR_CF32);
 #ifdef SXFIR_PROFILING
         if (ntaps == 128 && p->symmetric)
             ksb = fmt == SXFIR_S32 ? (const void *)sxfir::decim4_tile2_kernel<128, 1, sxfir::T2_SHIPPED, 0, true>
                                    : (const void *)sxfir::decim4_tile2_kernel<128, 1, sxfir::T2_SHIPPED>;
 #endif
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ksb, 64, 0) == hipSuccess && nb > 0) p->occ_sb = nb;
-        if (ntaps == 128 && (p->symmetric || fmt == SXFIR_CF16)) {
-            // the shipped form for 128 bit-symmetric taps (every linear-phase design): eight outputs per lane, all 64 distinct taps in
-            // SGPR pairs (sxfir_decim_wide.hip.h); 18.5 KB of LDS per wave -> 8 waves per CU.  Its ASYM form (round 5: taps 127..64 in
-            // SGPR pairs, taps 63..0 in VGPR pairs) ships for CF16 storage only, where it beats the multi-column kernel by 3 %; on CF32
-            // and S32 words it measured 1.4 % slower / 0.7 % faster than decim4_tile_kernel<128> (profiles/round5_kbench_asym.txt),
-            // which therefore keeps the non-symmetric 128-tap plans (the instances exist in the profiling build: SXFIR_WIDE_ASYM=1)
-            p->wide8 = true;
-            const void *kw;
-            if (p->symmetric)
-                kw = fmt == SXFIR_S32    ? (const void *)sxfir::decim4_wide_kernel<0, true>
-                     : fmt == SXFIR_CF16 ? (const void *)sxfir::decim4_wide_kernel<0, false, 24, true, false, 0, true>
-                                         : (const void *)sxfir::decim4_wide_kernel<0, false>;
-            else
-                kw = (const void *)sxfir::decim4_wide_kernel<0, false, 24, true, false, 0, true, true>;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kw, 64, 0) == hipSuccess && nb > 0) p->occ_wide = nb;
-        }
+        query_occupancy(&p->occ_sb, ksb, 64);
+        // 128 taps: the wide kernel, for bit-symmetric taps and (its ASYM form) for CF16 storage
+        p->wide8 = p->k.wide != nullptr;
+        query_occupancy(&p->occ_wide, p->k.wide, 64);
 #ifdef SXFIR_PROFILING
-        if (ntaps == 128 && !p->symmetric && fmt != SXFIR_CF16 && getenv("SXFIR_WIDE_ASYM") && atoi(getenv("SXFIR_WIDE_ASYM"))) {
+        if (!p->k.wide && ntaps == 128 && getenv("SXFIR_WIDE_ASYM") && atoi(getenv("SXFIR_WIDE_ASYM"))) {
             p->wide8 = true;                                   // A/B: the wide kernel's ASYM form on CF32 / S32 words
-            int nbw = 0;
-            const void *kw = fmt == SXFIR_S32 ? (const void *)sxfir::decim4_wide_kernel<0, true, 24, true, false, 0, false, true>
-                                              : (const void *)sxfir::decim4_wide_kernel<0, false, 24, true, false, 0, false, true>;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbw, kw, 64, 0) == hipSuccess && nbw > 0) p->occ_wide = nbw;
+            p->k.wide = fmt == SXFIR_S32 ? sxfir::decim4_wide_kernel<0, true, 24, true, false, 0, false, true>
+                                         : sxfir::decim4_wide_kernel<0, false, 24, true, false, 0, false, true>;
+            query_occupancy(&p->occ_wide, p->k.wide, 64);
         }
         if (ntaps == 128) {
             const void *kp = fmt == SXFIR_S32 ? (const void *)sxfir::decim4_pair_kernel<0, true> : (const void *)sxfir::decim4_pair_kernel<0, false>;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kp, 128, 0) == hipSuccess && nb > 0) p->occ_pair = nb;
+            query_occupancy(&p->occ_pair, kp, 128);
         }
         const void *kdb = ntaps == 128 ? (const void *)sxfir::decim4_tile_kernel<128, true>
                                        : (const void *)sxfir::decim4_tile_kernel<64, true>;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kdb, 64, 0) == hipSuccess && nb > 0) p->occ_db = nb;
+        query_occupancy(&p->occ_db, kdb, 64);
         if (const char *v = getenv("SXFIR_TILE_VARIANT")) {
             p->tile_dbuf = (strcmp(v, "db") == 0);
             // "sb", "db", "sg": the first-generation tile kernel (taps in VGPR pairs) also for symmetric taps
@@ -462,8 +534,7 @@ int sxfir_create(sxfir_plan **out, int mode, const float *taps, int ntaps, int r
             if (p->sgpr_r && ntaps == 128) {
                 const void *k = p->sgpr_r == 8 ? (const void *)sxfir::decim4_sgpr_kernel<8>
                                                : (const void *)sxfir::decim4_sgpr_kernel<4>;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, 64, 0) == hipSuccess && nb > 0)
-                    p->occ_sb = nb;
+                query_occupancy(&p->occ_sb, k, 64);
             }
             // "wide": decim4_wide_kernel (sxfir_decim_wide.hip.h), symmetric taps only
             if (strncmp(v, "wide", 4) == 0 && ntaps == 128 && p->symmetric) {
@@ -481,10 +552,7 @@ int sxfir_create(sxfir_plan **out, int mode, const float *taps, int ntaps, int r
                 // form with a larger tile per wave -- 16 outputs per lane, 34 KB -- have left of the latency hiding?)
                 if (const char *lp = getenv("SXFIR_LDS_PAD")) {
                     p->lds_pad = atoi(lp) > 0 ? atoi(lp) : 0;
-                    int nbw = 0;
-                    if (p->lds_pad && hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbw, (const void *)sxfir::decim4_wide_kernel<0, false, 24, true>, 64,
-                                                                                     (size_t)p->lds_pad) == hipSuccess && nbw > 0)
-                        p->occ_wide = nbw;
+                    if (p->lds_pad) query_occupancy(&p->occ_wide, sxfir::decim4_wide_kernel<0, false, 24, true>, 64, (size_t)p->lds_pad);
                 }
             }
             // "pair": decim4_pair_kernel (sxfir_decim_pair.hip.h)
@@ -512,8 +580,9 @@ int sxfir_create(sxfir_plan **out, int mode, const float *taps, int ntaps, int r
                     // SXFIR_LDS_PAD: dynamic LDS bytes on top of the kernel's own image: fewer waves fit a CU
                     if (const char *lp = getenv("SXFIR_LDS_PAD")) p->lds_pad = atoi(lp) > 0 ? atoi(lp) : 0;
                     // occ_sb = resident WAVES per CU of this variant
-                    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, 64 * wpg, (size_t)p->lds_pad) == hipSuccess && nb > 0)
-                        p->occ_sb = nb * wpg;
+                    int nb = 0;
+                    query_occupancy(&nb, k, 64 * wpg, (size_t)p->lds_pad);
+                    if (nb > 0) p->occ_sb = nb * wpg;
                 }
             }
         }

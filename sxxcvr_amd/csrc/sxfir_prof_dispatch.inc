@@ -1,9 +1,22 @@
 // Launch tables of the profiling build (libsxfir_prof.so, -DSXFIR_PROFILING): kernel A/B variants, ablation modes and
-// phase stamps, selected by the SXFIR_* environment knobs read in sxfir_create.  Included by sxfir.hip in front of
-// launch_decim, so that the product dispatch there reads straight through; nothing in here exists in libsxfir.so.
+// phase stamps, selected by the SXFIR_* environment knobs (most of them read in sxfir_create).  Included by
+// sxfir_launch.hip.h in front of its geometry and launch functions, which call these hooks and otherwise read straight
+// through; in libsxfir.so every hook is the empty inline function at the end of this file.
 //
-// Every prof_launch_* returns 0 when the plan asks for nothing of its kind (the product dispatch goes on), 1 when it
+// Every prof_launch_* returns 0 when the plan asks for nothing of its kind (the product launch goes on), 1 when it
 // has launched the kernel, and a negative SXFIR_E* code on an error.
+#ifdef SXFIR_PROFILING
+
+static int prof_oversub_forced() { return getenv("SXFIR_OVERSUB") != nullptr; }              // the knob means what it says
+
+// decim4_sgpr_kernel<R>: tiles of 64 R outputs
+static long long prof_tile_out(const sxfir_plan *p, long long tile_out) { return (p->sgpr_r && p->ntaps == 128) ? 64 * p->sgpr_r : tile_out; }
+
+// SXFIR_IBLOCK16=1: x96 on CF32 as six phase blocks of the x16 tile kernel instead of three of the x32 one
+static int prof_iblock16(const sxfir_plan *p, bool keyed, int base_l)
+{
+    return (p->ratio == 96 && getenv("SXFIR_IBLOCK16") && atoi(getenv("SXFIR_IBLOCK16")) && !keyed && p->fmt == SXFIR_CF32) ? 16 : base_l;
+}
 
 // stamp records for `need` waves of `bytes_per_record` bytes each (kept with the plan, regrown on demand)
 static int prof_stamps(sxfir_plan *p, size_t need, size_t bytes_per_record, unsigned long long **out)
@@ -16,8 +29,8 @@ static int prof_stamps(sxfir_plan *p, size_t need, size_t bytes_per_record, unsi
 }
 
 // decim_dense_kernel: SXFIR_ABLATE = 1 (memory side alone), 2 (arithmetic alone), 3 (phase stamps); SXFIR_DENSE_NT = 2 / 1 / 0:
-// non-temporal loads for all but both halos / all but the next tile's halo / plain staging loads, at every ratio (the product ships 2 at all three ratios: launch_decim, SXFIR_DENSE_LAUNCH(.., 2))
-static int prof_launch_dense(sxfir_plan *p, sxfir::DecimMultiArgs &a, dim3 grid, hipStream_t st, long long groups, int W)
+// non-temporal loads for all but both halos / all but the next tile's halo / plain staging loads, at every ratio (the product ships 2 at all three ratios: dense_kernel, sxfir_plan.hip.h)
+static int prof_launch_dense_ablations(sxfir_plan *p, sxfir::DecimMultiArgs &a, dim3 grid, hipStream_t st)
 {
     if (p->fmt == SXFIR_CF16) return 0;                                                  // CF16 storage: the product dispatch (no ablations of it)
     if (p->dense_subset && p->ablate == 1 && p->fmt != SXFIR_S32) {                      // (ablate 0: the product dispatch launches it)
@@ -40,7 +53,7 @@ static int prof_launch_dense(sxfir_plan *p, sxfir::DecimMultiArgs &a, dim3 grid,
     if (p->dense_subset && p->ablate == 0 && p->dense_nt_set == 0) return 0;
     if (p->fmt == SXFIR_S32 || (p->ablate == 0 && p->dense_nt_set == 0) || p->ablate > 3) return 0;
     if (p->ablate == 3)
-        if (int rc = prof_stamps(p, (size_t)groups * p->nchan * W, 40, &a.stamps)) return rc;
+        if (int rc = prof_stamps(p, (size_t)grid.x * p->nchan * p->multi_waves, 40, &a.stamps)) return rc;
 #define SXFIR_PD(AA, NN) \
     do { \
         if (p->ratio == 8) hipLaunchKernelGGL((sxfir::decim_dense_kernel<8, AA, false, NN>), grid, dim3(256), 0, st, a); \
@@ -60,9 +73,23 @@ static int prof_launch_dense(sxfir_plan *p, sxfir::DecimMultiArgs &a, dim3 grid,
     return 1;
 }
 
-// decim_multi_kernel: S32 wire words (one instantiation per ratio) and the ablation / stamp builds of the CF32 forms
-static int prof_launch_multi(sxfir_plan *p, sxfir::DecimMultiArgs &a, dim3 grid, hipStream_t st, long long groups, int W)
+// ... and SXFIR_DENSE_SUBSET=0: the VGPR-tap forms at /8, A/B partners of the scalar-tap form that ships
+static int prof_launch_dense(sxfir_plan *p, sxfir::DecimMultiArgs &a, dim3 grid, hipStream_t st)
 {
+    if (const int pr = prof_launch_dense_ablations(p, a, grid, st)) return pr;
+    if (p->ratio != 8 || p->dense_subset) return 0;
+    if (p->fmt == SXFIR_CF16) hipLaunchKernelGGL((sxfir::decim_dense_kernel<8, 0, false, 0, false, false, true>), grid, dim3(256), 0, st, a);
+    else if (p->fmt == SXFIR_S32) hipLaunchKernelGGL((sxfir::decim_dense_kernel<8, 0, true, 2>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((sxfir::decim_dense_kernel<8, 0, false, 2>), grid, dim3(256), 0, st, a);
+    HIPCHECK(hipGetLastError());
+    return 1;
+}
+
+// decim_multi_kernel (SXFIR_DENSE=0, SXFIR_MULTI_PS / _W, SXFIR_TILE_VARIANT=mu; no instance in the production library): S32 wire
+// words (one instantiation per ratio), the (ratio, waves, CF16, row split) variants and their ablation / stamp builds
+static int prof_launch_multi(sxfir_plan *p, sxfir::DecimMultiArgs &a, dim3 grid, hipStream_t st)
+{
+    const int W = p->multi_waves;
     if (p->fmt == SXFIR_S32) {
         switch (p->ratio) {
         case 8: hipLaunchKernelGGL((sxfir::decim_multi_kernel<8, 4, false, 0, 2, true>), grid, dim3(256), 0, st, a); break;
@@ -72,11 +99,14 @@ static int prof_launch_multi(sxfir_plan *p, sxfir::DecimMultiArgs &a, dim3 grid,
         HIPCHECK(hipGetLastError());
         return 1;
     }
-    if (p->ablate == 0) return 0;
     if (p->ablate == 3)
-        if (int rc = prof_stamps(p, (size_t)groups * p->nchan * W, 40, &a.stamps)) return rc;
+        if (int rc = prof_stamps(p, (size_t)grid.x * p->nchan * W, 40, &a.stamps)) return rc;
     const int key = SXFIR_MULTI_KEY(p->ratio, W, p->fmt == SXFIR_CF16, p->multi_ps) + 100000 * p->ablate;
     switch (key) {
+#define SXFIR_X(DD, WW, HH, PP) \
+    case SXFIR_MULTI_KEY(DD, WW, HH, PP): hipLaunchKernelGGL((sxfir::decim_multi_kernel<DD, WW, HH, 0, PP>), grid, dim3(64 * WW), 0, st, a); break;
+        SXFIR_MULTI_VARIANTS(SXFIR_X)
+#undef SXFIR_X
     case 100801: hipLaunchKernelGGL((sxfir::decim_multi_kernel<8, 1, false, 1>), grid, dim3(64), 0, st, a); break;
     case 200801: hipLaunchKernelGGL((sxfir::decim_multi_kernel<8, 1, false, 2>), grid, dim3(64), 0, st, a); break;
     case 100804: hipLaunchKernelGGL((sxfir::decim_multi_kernel<8, 4, false, 1>), grid, dim3(256), 0, st, a); break;
@@ -98,6 +128,48 @@ static int prof_launch_multi(sxfir_plan *p, sxfir::DecimMultiArgs &a, dim3 grid,
     return 1;
 }
 
+// decim_blocks_kernel: the join-drop test hook's two extra argument fields, and the experiments -- /16 and /32 through the block
+// form (SXFIR_BLOCKS_SMALL=1, =2 unrotated), round 5's waves by row half (SXFIR_BLOCKS_RP=0), plain staging loads (SXFIR_BLOCKS_NT=0)
+static int prof_launch_blocks(sxfir_plan *p, const LaunchGeom &geom, const sxfir::DecimMultiArgs &a, sxfir::DecimBlocksJoin &jn, dim3 grid, hipStream_t st)
+{
+    jn.shadow = (sxfir::f32x4 *)p->join_shadow;
+    jn.drop_blk = p->join_drop;
+#define SXFIR_B(...) hipLaunchKernelGGL((sxfir::decim_blocks_kernel<__VA_ARGS__>), grid, dim3(256), 0, st, a, jn)
+    const bool cf32 = p->fmt == SXFIR_CF32, split = geom.split > 1;
+    if (p->blocks < 3 && !p->rot) {
+        if (p->blocks == 1) SXFIR_B(1, false, true, false, false, true, false);
+        else SXFIR_B(2, false, true, false, false, true, false);
+    } else if (p->blocks < 3) {
+        if (p->blocks == 1) SXFIR_B(1, false, true, false, false, true);
+        else SXFIR_B(2, false, true, false, false, true);
+    } else if (getenv("SXFIR_BLOCKS_RP") && !atoi(getenv("SXFIR_BLOCKS_RP")) && cf32) {
+        if (split && p->blocks == 3) SXFIR_B(3, false, true, false, true, false);
+        else if (split) SXFIR_B(6, false, true, false, true, false);
+        else if (p->blocks == 3) SXFIR_B(3, false, true, false, false, false);
+        else SXFIR_B(6, false, true, false, false, false);
+    } else if (getenv("SXFIR_BLOCKS_NT") && !atoi(getenv("SXFIR_BLOCKS_NT")) && cf32) {
+        if (split && p->blocks == 3) SXFIR_B(3, false, false, false, true, true);
+        else if (split) SXFIR_B(6, false, false, false, true, true);
+        else if (p->blocks == 3) SXFIR_B(3, false, false, false, false, true);
+        else SXFIR_B(6, false, false, false, false, true);
+    } else {
+        return 0;
+    }
+#undef SXFIR_B
+    HIPCHECK(hipGetLastError());
+    return 1;
+}
+
+// test hook: the dropped block's values reach the scratch only now, behind the launch that should have read them -- the
+// NEXT launch's joiners find them there unless theirs arrive (what a stale hand-off looks like, deterministically)
+static int prof_join_drop_copy(sxfir_plan *p, const LaunchGeom &geom, hipStream_t st)
+{
+    if (p->join_drop >= 0 && geom.split > 1)
+        HIPCHECK(hipMemcpy2DAsync((char *)p->join_partials + 4096 * (size_t)p->join_drop, 4096 * (size_t)p->blocks, p->join_shadow, 4096,
+                                  4096, (size_t)(geom.n_tiles * p->nchan), hipMemcpyDeviceToDevice, st));
+    return SXFIR_OK;
+}
+
 // /4: decim4_pair_kernel, decim4_wide_kernel (tiles of 512 outputs) and the (waves per workgroup, option bits) variants
 // of decim4_tile2_kernel, each with its own grid
 static int prof_launch_tile_variant(sxfir_plan *p, sxfir::DecimTileArgs &a, long long n_out, long long n_tiles, hipStream_t st)
@@ -108,14 +180,7 @@ static int prof_launch_tile_variant(sxfir_plan *p, sxfir::DecimTileArgs &a, long
         long long G = ((long long)p->compute_units * (p->wide ? p->occ_wide : p->occ_pair) * p->oversub) / p->nchan;
         if (G < 1) G = 1;
         if (G > n_tiles2) G = n_tiles2;
-        a.n_tiles = (int)n_tiles2;
-        a.n_waves = (int)G;
-        a.w8 = (G % 8 == 0) ? (int)(G / 8) : 0;
-        a.run_base = a.run_extra = 0;
-        {
-            const int t = (int)((n_tiles2 - 1) % G);
-            a.hist_wave = (p->sched == 0 && a.w8) ? (t % a.w8) * 8 + t / a.w8 : t;
-        }
+        set_schedule(a, n_tiles2, G, p->sched == 1 ? 2 : p->sched);          // (these kernels make strided passes only)
         dim3 grid((unsigned)G, (unsigned)p->nchan);
         const int abl = p->ablate;
         if (abl == 5)
@@ -174,6 +239,7 @@ static int prof_launch_tile_variant(sxfir_plan *p, sxfir::DecimTileArgs &a, long
     long long G = ((long long)p->compute_units * p->occ_sb * p->oversub / wpg) / p->nchan;
     if (G < 1) G = 1;
     if (G > n_super) G = n_super;
+    a.n_tiles = (int)n_tiles;
     a.w8 = (G % 8 == 0) ? (int)(G / 8) : 0;
     a.run_base = a.run_extra = 0;
     if (p->t2_opt & sxfir::T2_HCARRY) {
@@ -265,3 +331,79 @@ static int prof_launch_tile_first_gen(sxfir_plan *p, sxfir::DecimTileArgs &a, di
     }
     return 0;
 }
+
+// The /4 hooks in launch order: the pair / wide / tile2 variants, then (4-outputs-per-lane plans only) the short tail, the
+// first-generation kernel's modes and "t2s", round 3's shipped form (with one wave per workgroup both kernels take the same
+// schedule constants)
+static int prof_launch_tile(sxfir_plan *p, const LaunchGeom &geom, sxfir::DecimTileArgs &a, long long n_out, hipStream_t st)
+{
+    if (p->fmt != SXFIR_CF16)
+        if (const int pr = prof_launch_tile_variant(p, a, n_out, (n_out + 255) / 256, st)) return pr;
+    if (geom.kind != GEOM_TILE) return 0;
+    long long per_chan = geom.groups;
+    prof_short_tail(p, a, geom.n_tiles, &per_chan);                                    // SXFIR_SCHED=3
+    const dim3 grid((unsigned)per_chan, (unsigned)p->nchan);
+    if (const int pr = prof_launch_tile_first_gen(p, a, grid, per_chan, p->tile_dbuf, st)) return pr;
+    if (!(p->ntaps == 128 && p->symmetric && p->sched != 1)) return 0;
+    if (p->fmt == SXFIR_S32) hipLaunchKernelGGL((sxfir::decim4_tile2_kernel<128, 1, sxfir::T2_SHIPPED, 0, true>), grid, dim3(64), 0, st, a);
+    else hipLaunchKernelGGL((sxfir::decim4_tile2_kernel<128, 1, sxfir::T2_SHIPPED>), grid, dim3(64), 0, st, a);
+    HIPCHECK(hipGetLastError());
+    return 1;
+}
+
+// Interpolators: the x8 pass kernel with four inputs per lane (SXFIR_IPASS=4) and its vmcnt(0) form (SXFIR_IPASS_WAIT0=1), and
+// interp_tile_kernel's CF32 / S32 instances (SXFIR_IPASS=0: the A/B partners of the pass kernels since round 5)
+static int prof_launch_interp(sxfir_plan *p, const LaunchGeom &geom, const sxfir::InterpTileArgs &t, dim3 grid, bool key, hipStream_t st)
+{
+    const bool s32 = p->fmt == SXFIR_S32;
+#define SXFIR_I(K_, ...) hipLaunchKernelGGL((sxfir::K_<__VA_ARGS__>), grid, dim3(64), 0, st, t)
+    if (geom.kind == GEOM_IPASS) {
+        if (p->ratio != 8) return 0;
+        if (p->ipass_qi == 4 && s32) return fail(SXFIR_EUNSUPPORTED, "four inputs per lane: CF32 only");
+        else if (p->ipass_qi == 4 && key) SXFIR_I(interp8_pass_kernel, 4, true);
+        else if (p->ipass_qi == 4) SXFIR_I(interp8_pass_kernel, 4);
+        else if (!p->ipass_wait0) return 0;
+        else if (s32 && key) SXFIR_I(interp8_pass_kernel, 2, true, true, false);
+        else if (s32) SXFIR_I(interp8_pass_kernel, 2, false, true, false);
+        else if (key) SXFIR_I(interp8_pass_kernel, 2, true, false, false);
+        else SXFIR_I(interp8_pass_kernel, 2, false, false, false);
+    } else if (p->fmt == SXFIR_CF16) {
+        return 0;
+    } else if (geom.phase_blocks == 6) {
+        SXFIR_I(interp_tile_kernel, 16, false, false, 96);                            // SXFIR_IBLOCK16=1
+    } else {
+#define SXFIR_IT(SS, KK) \
+        switch (p->ratio) { \
+        case 4: SXFIR_I(interp_tile_kernel, 4, SS, KK); break; \
+        case 8: SXFIR_I(interp_tile_kernel, 8, SS, KK); break; \
+        case 16: SXFIR_I(interp_tile_kernel, 16, SS, KK); break; \
+        case 32: SXFIR_I(interp_tile_kernel, 32, SS, KK); break; \
+        case 48: SXFIR_I(interp_tile_kernel, 16, SS, KK, 48); break; \
+        default: SXFIR_I(interp_tile_kernel, 32, SS, KK, 96); break; \
+        }
+        if (key && s32) { SXFIR_IT(true, true) }
+        else if (key) { SXFIR_IT(false, true) }
+        else if (s32) { SXFIR_IT(true, false) }
+        else { SXFIR_IT(false, false) }
+#undef SXFIR_IT
+    }
+#undef SXFIR_I
+    HIPCHECK(hipGetLastError());
+    return 1;
+}
+
+#else  // the production library: no hook does anything
+
+static inline long long prof_tile_out(const sxfir_plan *, long long tile_out) { return tile_out; }
+static inline int prof_iblock16(const sxfir_plan *, bool, int base_l) { return base_l; }
+#define SXFIR_NO_HOOK(NAME) template <typename... A> static inline int NAME(const A &...) { return 0; }
+SXFIR_NO_HOOK(prof_oversub_forced)
+SXFIR_NO_HOOK(prof_launch_blocks)
+SXFIR_NO_HOOK(prof_join_drop_copy)
+SXFIR_NO_HOOK(prof_launch_dense)
+SXFIR_NO_HOOK(prof_launch_multi)
+SXFIR_NO_HOOK(prof_launch_tile)
+SXFIR_NO_HOOK(prof_launch_interp)
+#undef SXFIR_NO_HOOK
+
+#endif

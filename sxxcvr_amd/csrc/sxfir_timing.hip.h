@@ -21,9 +21,8 @@ static int time_passes(sxfir_plan *p, int mode, const void *in_dev, size_t n_in,
     HIPCHECK(hipEventRecord(e0, S(stream)));
     for (int i = 0; i < iters; ++i) {
         bool history_done = false;   // history buffers are not swapped: every pass filters from the same state
-        rc = mode == SXFIR_DECIMATE
-                 ? launch_decim(p, in_dev, n_in, in_stride, out_dev, out_stride, n_out, S(stream), &history_done)
-                 : launch_interp(p, in_dev, n_in, in_stride, out_dev, out_stride, n_out, S(stream), &history_done);
+        const CallIO c{in_dev, n_in, in_stride, out_dev, out_stride, n_out, S(stream)};
+        rc = mode == SXFIR_DECIMATE ? launch_decim(p, c, &history_done) : launch_interp(p, c, &history_done);
         if (rc) break;
     }
     hipError_t e = hipEventRecord(e1, S(stream));
