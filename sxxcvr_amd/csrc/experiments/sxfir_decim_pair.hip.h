@@ -25,8 +25,7 @@
 
 #include <utility>
 
-#include "../sxfir_decim_tile.hip.h"
-#include "../sxfir_decim_tile2.hip.h"
+#include "../sxfir_decim_tile.hip.h"     // DecimTileArgs (and, through it, sxfir_common.hip.h)
 
 namespace sxfir {
 
@@ -145,15 +144,7 @@ __global__ __launch_bounds__(128) void decim4_pair_kernel(const DecimTileArgs a)
                     if (cc > last_chunk) cc = last_chunk;
                     src = reinterpret_cast<const f32x4 *>(in) + cc;
                 }
-                if (j < C::NI0 || (p && (j < C::NI1 - 1 || lane < C::LAST1))) {
-                    if (n_odd && cc == last_chunk) {
-                        // the chunk's second sample lies beyond the caller's buffer: 8 bytes through a register
-                        const float2 v = *reinterpret_cast<const float2 *>(src);
-                        part[64 * j + lane] = (f32x4){v.x, v.y, 0.0f, 0.0f};
-                    } else {
-                        glds16(src, part + 64 * j);
-                    }
-                }
+                if (j < C::NI0 || (p && (j < C::NI1 - 1 || lane < C::LAST1))) stage_edge_chunk(n_odd && cc == last_chunk, lane, src, part + 64 * j);
             }
         }
     };
@@ -162,17 +153,10 @@ __global__ __launch_bounds__(128) void decim4_pair_kernel(const DecimTileArgs a)
     // so that the workgroups of one XCD (blockIdx % 8; speed only) hold a contiguous block of the pass.
     const int G = a.n_waves;                            // workgroups per channel
     const int b = blockIdx.x;
-    int tile = (a.sched == 0 && a.w8) ? (b & 7) * a.w8 + (b >> 3) : b;
+    int tile = (a.sched == 0 && a.w8) ? xcd_blocked(b, a.w8) : b;
     if (tile >= a.n_tiles) return;                      // (whole workgroups leave together)
 
-    if (b == a.hist_wave && p == 0) {
-        float *ho = a.hist_out + 2 * a.hist_stride * ch;
-        for (int j = lane; j < C::HIST; j += 64) {
-            const long long s = a.n_in - C::HIST + j;
-            const float2 v = s >= 0 ? reinterpret_cast<const float2 *>(in)[s] : reinterpret_cast<const float2 *>(hist)[s + C::HIST];
-            reinterpret_cast<float2 *>(ho)[j] = v;
-        }
-    }
+    if (b == a.hist_wave && p == 0) carry_history<8, C::HIST>(lane, in, hist, a.hist_out + 2 * a.hist_stride * ch, a.n_in);
 
     // lane l: outputs 8l..8l+7 of the tile; window from chunk 16l - 32p + 32 (a multiple of 16)
     const int u0c = 16 * lane - 32 * p + 32;

@@ -223,14 +223,8 @@ __global__ __launch_bounds__(256) void decim_blocks_kernel(const DecimMultiArgs 
         const bool interior = tile >= 1 && (ROT ? tile <= tile_hi : tile < tile_hi);
         if constexpr (HALFIN) {
             if (interior) {
-                // the descriptor is based at the wave's first byte of THIS step (64-bit base, rebuilt per step from scalars), so
-                // every offset is a small constant and a call may be as long as it likes; {DATA_FORMAT 16, NUM_FORMAT FLOAT, X <- R}
-                const unsigned long long wb = (unsigned long long)(in + SB * s_first + (SB * D * C::RPI) * ww);
-                v4i32 rs;
-                rs.x = __builtin_amdgcn_readfirstlane((int)(unsigned)wb);
-                rs.y = __builtin_amdgcn_readfirstlane((int)(unsigned)(wb >> 32)) & 0xffff;    // stride 0
-                rs.z = 1 << 20;                                                               // bytes addressable from the base
-                rs.w = 4 | (7 << 12) | (2 << 15);
+                // the descriptor is based at the wave's first byte of THIS step; 1 MiB from there
+                const v4i32 rs = typed_dma_descriptor((unsigned long long)(in + SB * s_first + (SB * D * C::RPI) * ww), 1 << 20);
                 // lanes 0-31: the 32 halves of a row's piece, lanes 32-63: of the next row's
                 unsigned voff = (unsigned)(SB * D) * (unsigned)(lane >> 5) + 2u * (unsigned)(lane & 31);
                 asm volatile("" : "+v"(voff));
@@ -241,20 +235,14 @@ __global__ __launch_bounds__(256) void decim_blocks_kernel(const DecimMultiArgs 
                         const unsigned soff = (unsigned)(SB * D * C::RPI * 4) * i0 + (unsigned)(2 * SB * D) * j;   // bytes from the wave's base
                         static_assert((SB * D * C::RPI * 4) * (C::NIW - 1) + (2 * SB * D) * 3 + SB * D + 64 < (1 << 20), "inside the descriptor");
                         const unsigned m0v = __builtin_amdgcn_readfirstlane(lds_wave_base + 16u * (unsigned)(C::dma_slot(4 * i0) + 16 * j));
-                        // (M0 is a reserved register to the compiler: writing it here needs, and admits, no clobber entry)
-                        if (NTLD && i0 >= 1 && i0 < 16)
-                            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_format_x %1, %2, %3 offen nt lds"
-                                         :: "s"(m0v), "v"(voff), "s"(rs), "s"(soff) : "memory");
-                        else
-                            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_format_x %1, %2, %3 offen lds"
-                                         :: "s"(m0v), "v"(voff), "s"(rs), "s"(soff) : "memory");
+                        if (NTLD && i0 >= 1 && i0 < 16) typed_dma_x<true>(m0v, voff, rs, soff);
+                        else typed_dma_x<false>(m0v, voff, rs, soff);
                     }
                 }
                 return;
             }
         }
-        // (structural, not left to the optimizer: an instance whose typed front end writes M0 from inline asm holds no
-        // compiler-managed LDS-DMA at all -- LLVM may hoist or merge ITS M0 set-up across an asm statement it cannot see into)
+        // (structural: an instance with the typed front end holds no compiler-managed LDS-DMA, see typed_dma_x)
         if constexpr (!HALFIN) if (interior) {
             const char *base = in + 8 * s_first + (8 * D * C::RPI) * ww;
 #pragma unroll

@@ -1,6 +1,6 @@
 // Decimate-by-4, 128 COMPLEX taps (h = a + j b), CF32: 8 outputs per lane, one wave per tile of 512 outputs (gfx950).
 // The band-pass partner of decim4_wide_kernel (sxfir_decim_wide.hip.h): the same tile, the same staged image, the same
-// stores -- and two FMA chains per window read instead of one.
+// stores -- that kernel's frame functions, called from here -- and two FMA chains per window read instead of one.
 //
 // Contract: A = a (*) x and B = b (*) x are the two REAL-tap results under the plan's real-tap contract
 // ((jsplit, cw) = (2, 4), rotation 0: P1 = taps 127..64 and P0 = taps 63..0 of each output, both chains from +0, A = P0 + P1);
@@ -17,7 +17,7 @@
 //   * the combine (A = P0 + P1, B = P0 + P1, re = A.re - B.im, im = A.im + B.re) is in registers, in front of the output
 //     transposition through the dead image;
 //   * staging (19 LDS-DMA instructions, 16 of them non-temporal), XCD-blocked tile dealing, fused history carry-over and whole-line
-//     non-temporal stores are the wide kernel's, restated here so that the real-tap kernel's text (and bits) stay untouched.
+//     non-temporal stores are the wide kernel's: the wide_* functions of sxfir_decim_wide.hip.h with the shipped parameters.
 //
 // Per tile of 512 outputs: 2048 v_pk_fma_f32 (2 chains x 8 outputs x 128 taps per lane; half of them with a scalar tap
 // operand) = twice a real-tap tile's 1024; 94 window ds_read_b128 (47 per pass) + 4 of the output transposition: 23.5 window
@@ -30,9 +30,7 @@
 
 #include <utility>
 
-#include "sxfir_decim_tile.hip.h"
-#include "sxfir_common.hip.h"            // pk_fma_s_*, slot_source_offset
-#include "sxfir_decim_wide.hip.h"       // DecimWide: the tile's constants
+#include "sxfir_decim_wide.hip.h"       // DecimWide and the wide tile's frame: schedule, staging, carry-over, stores
 
 namespace sxfir {
 
@@ -115,67 +113,21 @@ __global__ __launch_bounds__(64) void decim4_cx_kernel(const DecimTileArgs a)
     const long long last_chunk = (a.n_in - 1) >> 1;
     const int n_odd = (int)(a.n_in & 1);
 
-    // Tile schedule: in pass i the G waves of a channel cover the G consecutive tiles [i*G, (i+1)*G), dealt so
-    // that the waves of one XCD (blockIdx % 8; speed only) hold a contiguous block of the pass.
+    // the wide kernel's tile schedule, always XCD-blocked
     const int G = a.n_waves;
     const int b = blockIdx.x;
-    int tile = a.w8 ? (b & 7) * a.w8 + (b >> 3) : b;
+    int tile = wide_first_tile(b, 0, a.w8);
     if (tile >= a.n_tiles) return;
 
     unsigned boff[C::NI];
 #pragma unroll
     for (int j = 0; j < C::NI; ++j) boff[j] = slot_source_offset(64u * j + lane, C::CHUNKS);
 
-    auto stage = [&](int t) __attribute__((always_inline)) {
-        const long long c0 = ((long long)t * C::TILE_IN - C::HALO) >> 1;
-        const bool interior = (c0 >= 0) && (c0 + C::CHUNKS - 1 <= last_chunk - n_odd);
-        if (interior) {
-            const char *src = reinterpret_cast<const char *>(reinterpret_cast<const f32x4 *>(in) + c0);
-#pragma unroll
-            for (int j = 0; j < C::NI; ++j) {
-                asm volatile("" : "+v"(boff[j]));        // 32-bit offset next to its use; in place: no copy
-                const unsigned bo = boff[j];
-                if (j < C::NI - 1 || lane < C::LASTL) {
-                    // instructions 1..16 -- the rows no other tile reads -- are non-temporal loads; 0 (the re-read of the previous
-                    // tile's last kilobyte) and 17, 18 (this tile's last kilobyte, the next tile's halo) stay plain
-                    if (j >= 1 && j <= 16) glds16<2>(src + bo, img + 64 * j);
-                    else glds16(src + bo, img + 64 * j);
-                }
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < C::NI; ++j) {
-                unsigned bo = boff[j];
-                asm volatile("" : "+v"(bo));
-                long long cc = c0 + (bo >> 4);
-                const f32x4 *src;
-                if (cc < 0) {
-                    src = reinterpret_cast<const f32x4 *>(hist) + (cc + C::HIST / 2);
-                } else {
-                    if (cc > last_chunk) cc = last_chunk;
-                    src = reinterpret_cast<const f32x4 *>(in) + cc;
-                }
-                if (j < C::NI - 1 || lane < C::LASTL) {
-                    if (n_odd && cc == last_chunk) {
-                        // the chunk's second sample lies beyond the caller's buffer: 8 bytes through a register
-                        const float2 v = *reinterpret_cast<const float2 *>(src);
-                        img[64 * j + lane] = (f32x4){v.x, v.y, 0.0f, 0.0f};
-                    } else {
-                        glds16(src, img + 64 * j);
-                    }
-                }
-            }
-        }
-    };
+    // the wide kernel's staging with the shipped policy: instructions 1..16 non-temporal
+    // (through a lambda: called straight from the tile loop the function leaves the kernel's text another)
+    auto stage = [&](int t) __attribute__((always_inline)) { wide_stage_cf32<true, 0>(img, in, hist, last_chunk, n_odd, lane, boff, t); };
 
-    if (b == a.hist_wave) {
-        float *ho = a.hist_out + 2 * a.hist_stride * ch;
-        for (int j = lane; j < C::HIST; j += 64) {
-            const long long s = a.n_in - C::HIST + j;
-            const float2 v = s >= 0 ? reinterpret_cast<const float2 *>(in)[s] : reinterpret_cast<const float2 *>(hist)[s + C::HIST];
-            reinterpret_cast<float2 *>(ho)[j] = v;
-        }
-    }
+    if (b == a.hist_wave) carry_history<8, C::HIST>(lane, in, hist, a.hist_out + 2 * a.hist_stride * ch, a.n_in);
 
     // lane l: outputs 8l..8l+7 of the tile; window from chunk 16l (lane stride 17 slots: conflict free)
     const f32x4 *win = img + 17 * lane;
@@ -217,25 +169,13 @@ __global__ __launch_bounds__(64) void decim4_cx_kernel(const DecimTileArgs a)
 
         const long long m0 = (long long)tile * C::TILE_OUT;
         if (m0 + C::TILE_OUT <= a.n_out) {
-            // transposed through the dead image so that each store instruction writes 1 KiB of consecutive addresses (the wide
-            // kernel's swizzled layout: no bank conflicts either way; written and read by this wave only, in order)
+            // transposed through the dead image (the wide kernel's swizzled layout), then whole-line non-temporal stores
 #pragma unroll
             for (int k = 0; k < 4; ++k) img[4 * lane + (k ^ swz_w)] = y[k];
-            f32x4 *dst = reinterpret_cast<f32x4 *>(out + 2 * m0);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const f32x4 v = img[64 * k + (lane ^ swz_r)];
-                __builtin_nontemporal_store(v, dst + 64 * k + lane);
-            }
+            auto store_full = [&]() __attribute__((always_inline)) { wide_store_full<0>(img, out, m0, lane, swz_r); };
+            store_full();
         } else {
-            // ragged last tile of the call: element by element, straight from the registers
-            const long long m = m0 + 8 * lane;
-            float *dst = out + 2 * m;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (m + 2 * k < a.n_out) { dst[4 * k] = y[k].x; dst[4 * k + 1] = y[k].y; }
-                if (m + 2 * k + 1 < a.n_out) { dst[4 * k + 2] = y[k].z; dst[4 * k + 3] = y[k].w; }
-            }
+            wide_store_ragged(out, m0, lane, a.n_out, y);
         }
         // the next tile's DMA overwrites the image only after these LDS reads have returned
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

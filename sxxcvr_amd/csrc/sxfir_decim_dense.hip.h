@@ -61,17 +61,11 @@ struct DecimDense {
     static constexpr int dma_slot(int i) { return 64 * i + (i * RPI) / PADROWS; }
 };
 
-typedef int v4i32 __attribute__((ext_vector_type(4)));      // a buffer resource descriptor in four SGPRs
-
-__device__ __forceinline__ float half_lo_to_float(unsigned w) { return half_bits_to_float(w & 0xffffu); }
-__device__ __forceinline__ float half_hi_to_float(unsigned w) { return half_bits_to_float(w >> 16); }
-
 // two outputs (four floats) leave as 16 bytes of CF32 or, CF16 storage, as two half pairs rounded once (8 bytes)
 template <bool HALFOUT>
 __device__ __forceinline__ void store_pair(char *dst, float i0, float q0, float i1, float q1)
 {
     if constexpr (HALFOUT) {
-        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
         __builtin_nontemporal_store((u32x2){pack_half2(i0, q0), pack_half2(i1, q1)}, reinterpret_cast<u32x2 *>(dst));
     } else {
         __builtin_nontemporal_store((f32x4){i0, q0, i1, q1}, reinterpret_cast<f32x4 *>(dst));
@@ -263,17 +257,10 @@ decim_dense_kernel(const DecimMultiArgs a)
         if constexpr (ABL == 2) return;
         if constexpr (HALFIN) {
             if (interior) {
-                // Typed LDS-DMA: the wave's old instruction i = ww + 4 i0 (64 slots = 128 samples) becomes four
-                // buffer_load_format_x ... lds of 16 slots each: lane l fetches the half at byte 2 l of 128 consecutive source
-                // bytes and the texture path writes its float to LDS address M0 + 4 l.  The descriptor is based at the wave's
-                // first byte of THIS tile (64-bit base, rebuilt per tile from scalars), so every offset is a small constant
-                // and a call may be as long as it likes; {DATA_FORMAT 16, NUM_FORMAT FLOAT, X <- R}.
-                const unsigned long long wb = (unsigned long long)base;
-                v4i32 rs;
-                rs.x = __builtin_amdgcn_readfirstlane((int)(unsigned)wb);
-                rs.y = __builtin_amdgcn_readfirstlane((int)(unsigned)(wb >> 32)) & 0xffff;    // stride 0
-                rs.z = 1 << 20;                                                               // bytes addressable from the base: a tile's share and more
-                rs.w = 4 | (7 << 12) | (2 << 15);
+                // Typed LDS-DMA (typed_dma_x, sxfir_common.hip.h): the wave's old instruction i = ww + 4 i0 (64 slots = 128 samples)
+                // becomes four typed instructions of 16 slots each: lane l fetches the half at byte 2 l of 128 consecutive source
+                // bytes.  The descriptor is based at the wave's first byte of THIS tile; 1 MiB from there: a tile's share and more.
+                const v4i32 rs = typed_dma_descriptor((unsigned long long)base, 1 << 20);
                 unsigned voff = 2u * (unsigned)lane;
                 asm volatile("" : "+v"(voff));
 #pragma unroll
@@ -286,24 +273,17 @@ decim_dense_kernel(const DecimMultiArgs a)
                         if (i0 < C::NIW - 1 || i < C::NI - 1 || (i == C::NI - 1 && lane < 4 * valid)) {
                             const unsigned soff = 2048u * i0 + 128u * j;                      // bytes from the wave's base
                             const unsigned m0v = __builtin_amdgcn_readfirstlane(lds_wave_base + 16u * (unsigned)(C::dma_slot(4 * i0) + 16 * j));
-                            // (M0 is a reserved register to the compiler -- it sets it right before each of its own uses and keeps nothing
-                            // in it across an asm statement -- so writing it here needs, and admits, no clobber entry)
                             // NTLD = 2 as in the CF32 form: rows no other tile reads stream through the L2 (nt), both halos stay plain
                             constexpr int FIRST_NT_H = (31 / C::RPI + 4) / 4;
-                            if (NTLD == 2 && i0 >= FIRST_NT_H && i0 < 8)
-                                asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_format_x %1, %2, %3 offen nt lds"
-                                             :: "s"(m0v), "v"(voff), "s"(rs), "s"(soff) : "memory");
-                            else
-                                asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_format_x %1, %2, %3 offen lds"
-                                             :: "s"(m0v), "v"(voff), "s"(rs), "s"(soff) : "memory");
+                            if (NTLD == 2 && i0 >= FIRST_NT_H && i0 < 8) typed_dma_x<true>(m0v, voff, rs, soff);
+                            else typed_dma_x<false>(m0v, voff, rs, soff);
                         }
                     }
                 }
                 return;
             }
         }
-        // (structural, not left to the optimizer: an instance whose typed front end writes M0 from inline asm holds no
-        // compiler-managed LDS-DMA at all -- LLVM may hoist or merge ITS M0 set-up across an asm statement it cannot see into)
+        // (structural: an instance with the typed front end holds no compiler-managed LDS-DMA, see typed_dma_x)
         if constexpr (!HALFIN) if (interior) {
             f32x4 hv[C::NIW - 8];
             if constexpr (HC) {

@@ -30,8 +30,7 @@
 
 #include <hip/hip_fp16.h>
 
-#include "sxfir_decim_tile.hip.h"
-#include "sxfir_common.hip.h"      // DecimMultiArgs, permlane16_swap, half <-> float (shared with the shipped kernels)
+#include "sxfir_common.hip.h"      // DecimMultiArgs, pk_fma_*, permlane16/32_swap, glds16, half <-> float
 
 namespace sxfir {
 
@@ -364,7 +363,6 @@ decim_multi_kernel(const DecimMultiArgs a)
                 char *dst = out + C::SBYTES * m;
                 if (m + 2 <= a.n_out) {
                     if constexpr (HALF) {
-                        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
                         __builtin_nontemporal_store((u32x2){pack_half2(ri[0], rq[0]), pack_half2(ri[1], rq[1])},
                                                     reinterpret_cast<u32x2 *>(dst));
                     } else {

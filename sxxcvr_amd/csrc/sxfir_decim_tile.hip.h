@@ -34,9 +34,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace sxfir {
+#include "sxfir_common.hip.h"            // f32x2 / f32x4, glds16, permlane32_swap, pk_fma_*, slot_source_offset, xcd_blocked, stage_edge_chunk
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+namespace sxfir {
 
 struct DecimTileArgs {
     const float *in;        // channel 0, sample 0 of this call (16-byte aligned)
@@ -84,25 +84,6 @@ struct DecimTile4 {
     static_assert(NT % 64 == 0, "tile kernel needs NT % 64 == 0");
 };
 
-// AUX = cache policy bits of the load (0 = default, 2 = nt: streaming, 1 = sc0, 16 = sc1)
-template <int AUX = 0>
-__device__ __forceinline__ void glds16(const void *gsrc, void *ldst)
-{
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)gsrc,
-                                     (__attribute__((address_space(3))) void *)ldst, 16, 0, AUX);
-}
-
-// v_permlane32_swap_b32 vdst, src (gfx950): lanes 32-63 of vdst <-> lanes 0-31
-// of src.  Inline asm on purpose: with two DIFFERENT operands hipcc 7.2's
-// __builtin_amdgcn_permlane32_swap returns the first result register for both
-// elements of its result pair (seen in the .s: "v_permlane32_swap v1, v2" then
-// v1 used for r[0] and r[1]).  "s_nop 1" = the 2 wait states the ISA requires
-// between a VALU write of an operand and the swap.
-__device__ __forceinline__ void permlane32_swap(float &vdst, float &src)
-{
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(vdst), "+v"(src));
-}
-
 template <int NT>
 struct DecimTileCtx {
     const float *in, *hist;
@@ -114,20 +95,6 @@ struct DecimTileCtx {
     // this lane: tile-invariant, 32 bits, so that the DMA uses the SGPR-base + VGPR-offset form
     unsigned boff[DecimTile4<NT>::NLOAD];
 };
-
-// One 16-byte chunk of an edge tile.  With an odd n_in the last chunk holds one valid sample: its second
-// half lies beyond the caller's buffer (possibly beyond the allocation) and is never touched; that lane
-// fetches 8 bytes through a register instead of taking part in the DMA.
-template <int NT>
-__device__ __forceinline__ void stage_edge_chunk(const DecimTileCtx<NT> &c, long long ch, const f32x4 *src, f32x4 *slot0)
-{
-    if (c.n_odd && ch == c.last_chunk) {
-        const float2 v = *reinterpret_cast<const float2 *>(src);
-        slot0[c.lane] = (f32x4){v.x, v.y, 0.0f, 0.0f};
-    } else {
-        glds16(src, slot0);
-    }
-}
 
 // HBM -> LDS for one tile, no VGPR round trip.  Slot q = 64*i + lane of the
 // buffer holds logical chunk q - (q+1)/17 (a pad slot re-loads its left
@@ -168,12 +135,10 @@ __device__ __forceinline__ void stage_tile(const DecimTileCtx<NT> &c, int tile, 
                 if (ch > c.last_chunk) ch = c.last_chunk;
                 src = reinterpret_cast<const f32x4 *>(c.in) + ch;
             }
-            stage_edge_chunk(c, ch, src, buf + 64 * i);
+            stage_edge_chunk(c.n_odd && ch == c.last_chunk, c.lane, src, buf + 64 * i);
         }
     }
 }
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 template <int NT>
 __device__ __forceinline__ void store_tile(const DecimTileCtx<NT> &c, int tile, const float (&oi)[4],
@@ -204,31 +169,8 @@ __device__ __forceinline__ void store_tile(const DecimTileCtx<NT> &c, int tile, 
     }
 }
 
-// Same arithmetic with the I and Q FMAs of one (tap, sample) pair issued as one
-// v_pk_fma_f32 (two independent IEEE fused multiply-adds per instruction, so the
-// results are bit-identical).  The tap is broadcast to both halves by op_sel: taps
-// live in 64-bit register pairs {h[2k], h[2k+1]} and op_sel / op_sel_hi pick the
-// low or the high dword for both lanes of the packed operation.  Inline asm keeps
-// the register picture of the scalar loop (the compiler's own packing of this loop
-// needs 178 VGPRs).
-__device__ __forceinline__ void pk_fma_lo(f32x2 &acc, const f32x2 &hpair, const f32x2 &x)
-{
-    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,0,0] op_sel_hi:[0,1,1]" : "+v"(acc) : "v"(hpair), "v"(x));
-}
-__device__ __forceinline__ void pk_fma_hi(f32x2 &acc, const f32x2 &hpair, const f32x2 &x)
-{
-    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "+v"(acc) : "v"(hpair), "v"(x));
-}
-// a chain's first FMA: acc = fmaf(tap, x, +0.0f), the zero as an inline constant (no register cleared first)
-__device__ __forceinline__ void pk_fma_hi_first(f32x2 &acc, const f32x2 &hpair, const f32x2 &x)
-{
-    asm("v_pk_fma_f32 %0, %1, %2, 0 op_sel:[1,0,0] op_sel_hi:[1,1,0]" : "=v"(acc) : "v"(hpair), "v"(x));
-}
-__device__ __forceinline__ void pk_fma_lo_first(f32x2 &acc, const f32x2 &hpair, const f32x2 &x)
-{
-    asm("v_pk_fma_f32 %0, %1, %2, 0 op_sel:[0,0,0] op_sel_hi:[0,1,0]" : "=v"(acc) : "v"(hpair), "v"(x));
-}
-
+// Same arithmetic with the I and Q FMAs of one (tap, sample) pair issued as one v_pk_fma_f32 (pk_fma_lo / pk_fma_hi,
+// sxfir_common.hip.h: bit-identical results).
 template <int NT, bool S32IN = false>
 __device__ __forceinline__ void compute_tile_pk(const DecimTileCtx<NT> &c, int tile, const f32x4 *win,
                                                 const float (&h)[NT / 2], f32x4 *xbuf)
@@ -339,9 +281,7 @@ __device__ __forceinline__ void compute_tile(const DecimTileCtx<NT> &c, int tile
     store_tile<NT>(c, tile, oi, oq, xbuf);
 }
 
-// History carry-over fused into the launch (no second kernel): the wave that owns the last tile
-// copies the last HIST samples of (hist ++ in) into the plan's OTHER history buffer (the current
-// one is still being read by the wave of tile 0).
+// The tile context's form of carry_history (sxfir_common.hip.h), fully unrolled.
 template <int NT>
 __device__ __forceinline__ void write_history(const DecimTileCtx<NT> &c, float *hist_out, long long n_in)
 {
@@ -354,8 +294,6 @@ __device__ __forceinline__ void write_history(const DecimTileCtx<NT> &c, float *
         reinterpret_cast<float2 *>(hist_out)[j] = v;
     }
 }
-
-#define SXFIR_WAIT_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
 
 // ABL (profiling builds only; 3 = scalar v_fmac_f32 arithmetic instead of v_pk_fma_f32, same bits): 0 = the real kernel, 1 = stage + store but no FIR arithmetic
 // (memory side alone), 2 = FIR arithmetic on whatever LDS holds, no staging (compute side alone).
@@ -378,12 +316,7 @@ __global__ __launch_bounds__(64) void decim4_tile_kernel(const DecimTileArgs a)
     c.last_chunk = (a.n_in - 1) >> 1;                 // last input chunk holding a valid sample
     c.n_odd = (int)(a.n_in & 1);
 #pragma unroll
-    for (int i = 0; i < C::NLOAD; ++i) {
-        const unsigned q = 64u * i + c.lane;
-        unsigned off = q - (((q + 1u) * 3856u) >> 16);                    // (q+1)/17, exact for q < 4096
-        off = off < (unsigned)C::CHUNKS ? off : (unsigned)C::CHUNKS - 1u;
-        c.boff[i] = 16u * off;
-    }
+    for (int i = 0; i < C::NLOAD; ++i) c.boff[i] = slot_source_offset(64u * i + c.lane, C::CHUNKS);
 
     // taps of this lane's half, h[kl] = taps[TPL*p + kl].  All lanes of a half hold the same 64 values:
     // loading them per lane costs 16 global_load_dwordx4 that each return 1 KiB (16 KiB per wave, more
@@ -429,7 +362,7 @@ __global__ __launch_bounds__(64) void decim4_tile_kernel(const DecimTileArgs a)
     const int W = a.n_waves;
     int tile_begin, tile_end, tile_step;
     if (a.sched == 0) {
-        tile_begin = a.w8 ? (wave & 7) * a.w8 + (wave >> 3) : wave;
+        tile_begin = a.w8 ? xcd_blocked(wave, a.w8) : wave;
         tile_end = a.n_tiles;
         tile_step = W;
     } else if (a.sched == 2) {

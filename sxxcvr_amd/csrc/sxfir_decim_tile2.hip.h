@@ -45,8 +45,7 @@
 
 #include <utility>
 
-#include "sxfir_decim_tile.hip.h"
-#include "sxfir_common.hip.h"      // pk_fma_s_*, slot_source_offset, rgrp_table (shared with the shipped kernels)
+#include "sxfir_decim_tile.hip.h"       // DecimTile4, DecimTileCtx (and, through it, sxfir_common.hip.h)
 
 namespace sxfir {
 
@@ -133,7 +132,7 @@ __device__ __forceinline__ void stage_range(const DecimTileCtx<NT> &c, int tile,
                 if (ch > c.last_chunk) ch = c.last_chunk;
                 src = reinterpret_cast<const f32x4 *>(c.in) + ch;
             }
-            if (j < NI - 1 || LASTL >= 64 || c.lane < LASTL) stage_edge_chunk(c, ch, src, buf + Q0 + 64 * j);
+            if (j < NI - 1 || LASTL >= 64 || c.lane < LASTL) stage_edge_chunk(c.n_odd && ch == c.last_chunk, c.lane, src, buf + Q0 + 64 * j);
         }
     }
 }
@@ -525,18 +524,18 @@ __global__ __launch_bounds__(64 * WPG) void decim4_tile2_kernel(const DecimTileA
             // Short tail: the launch ends with one-tile waves, so that the CUs run empty over the life of a short
             // wave instead of a long one; the long waves stride over the tiles before them.
             if (b < a.long_waves) {
-                const int S = a.long_w8 ? (b & 7) * a.long_w8 + (b >> 3) : b;
+                const int S = a.long_w8 ? xcd_blocked(b, a.long_w8) : b;
                 tile = S;
                 tile_end = a.long_tiles;
                 tile_step = a.long_waves;
             } else {
                 const int bs = b - a.long_waves;
-                tile = a.long_tiles + (a.short_w8 ? (bs & 7) * a.short_w8 + (bs >> 3) : bs);
+                tile = a.long_tiles + (a.short_w8 ? xcd_blocked(bs, a.short_w8) : bs);
                 tile_end = tile + 1 < a.n_tiles ? tile + 1 : a.n_tiles;
                 tile_step = 1;
             }
         } else {
-            const int S = (a.sched == 0 && a.w8) ? (b & 7) * a.w8 + (b >> 3) : b;
+            const int S = (a.sched == 0 && a.w8) ? xcd_blocked(b, a.w8) : b;
             tile = S * WPG + ww;
             tile_end = a.n_tiles;
             tile_step = G * WPG;
@@ -688,7 +687,7 @@ __global__ __launch_bounds__(64 * WPG) void decim4_tile2_kernel(const DecimTileA
     int ntile = 0;
     if constexpr (CUQ) {
         // k-th grab of this workgroup: pass k / WPG, tile k % WPG of the workgroup's WPG consecutive tiles
-        const int S0 = (a.sched == 0 && a.w8) ? (b & 7) * a.w8 + (b >> 3) : b;
+        const int S0 = (a.sched == 0 && a.w8) ? xcd_blocked(b, a.w8) : b;
         auto grab = [&]() __attribute__((always_inline)) -> int {
             unsigned k = 0;
             if (c.lane == 0) k = __hip_atomic_fetch_add(&cuq_next, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);

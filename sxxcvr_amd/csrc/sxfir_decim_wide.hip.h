@@ -29,9 +29,7 @@
 
 #include <utility>
 
-#include "sxfir_decim_tile.hip.h"
-#include "sxfir_common.hip.h"            // pk_fma_s_* / pk_fma_sv_*, slot_source_offset
-#include "sxfir_decim_dense.hip.h"      // v4i32, half_lo_to_float / half_hi_to_float, pack_half2 (the CF16 front end)
+#include "sxfir_decim_tile.hip.h"       // DecimTileArgs (and, through it, sxfir_common.hip.h)
 
 namespace sxfir {
 
@@ -127,13 +125,69 @@ __device__ __forceinline__ void fir_wide_steps(std::integer_sequence<int, Cs...>
     (fir_wide_step<S32IN, Cs, NB, PIN, true, ASYM>(win, buf, hs, a1, a0, hv), ...);
 }
 
-// ABL (profiling): 0 = the real kernel, 1 = staging + stores without the FIR, 5 = phase stamps (per wave 8 x uint64:
-// tiles, cycles issuing DMAs, waiting for data, FIR, transposition + stores, whole wave cycles, whole wave 100 MHz
-// ticks, XCC_ID | HW_ID << 8).
+// ---- the wide tile's frame: what decim4_wide_kernel and its complex-tap partner decim4_cx_kernel (sxfir_decim_cx.hip.h) share.
+// Forced-inline functions over DecimWide; `img` is the wave's image, `in` / `hist` / `out` the channel's pointers.
+
+// Tile schedule: in pass i the G = n_waves waves of a channel cover the G consecutive tiles [i*G, (i+1)*G), dealt XCD-blocked when
+// the plan's schedule is 0 and the host passes w8 = G / 8; this is wave b's tile of pass 0, its others lie G apart.
+// (Scalars by value, not the argument struct by reference: a reference to the kernel's by-value argument changes the code.)
+__device__ __forceinline__ int wide_first_tile(int b, int sched, int w8)
+{
+    return (sched == 0 && w8) ? xcd_blocked(b, w8) : b;
+}
+
+// HBM -> LDS for tile t, CF32 / S32 words: 19 LDS-DMA instructions, the last one for LASTL lanes; boff[j] =
+// slot_source_offset(64 j + lane, CHUNKS), the byte offset (from the tile's first staged chunk) of the chunk instruction j fetches
+// for this lane: tile-invariant, filled by the kernel once.
 // NTL (round 4): DMA instructions 1..16 -- the rows no other tile reads -- are non-temporal loads; 0 (the re-read of the
 // previous tile's last kilobyte) and 17, 18 (this tile's last kilobyte, the next tile's halo) stay plain.
-// POL (profiling: which cache policy costs the least energy per byte at the power cap): low byte = policy bits OR-ed into
-// the nt staging loads (1 = sc0, 16 = sc1), next byte = the stores: 0 nt (shipped), 1 plain, 2 sc0 sc1, 3 sc0 sc1 nt, 4 sc1.
+// POL (profiling): low byte = policy bits OR-ed into the nt staging loads (1 = sc0, 16 = sc1).  Shipped: NTL = true, POL = 0.
+// Edge tiles (the call's first and last): chunk by chunk, from the history below chunk 0, clamped to the call's last chunk.
+template <bool NTL, int POL>
+__device__ __forceinline__ void wide_stage_cf32(f32x4 *img, const float *in, const float *hist, long long last_chunk, int n_odd,
+                                                int lane, unsigned (&boff)[DecimWide::NI], int t)
+{
+    using C = DecimWide;
+    const long long c0 = ((long long)t * C::TILE_IN - C::HALO) >> 1;
+    const bool interior = (c0 >= 0) && (c0 + C::CHUNKS - 1 <= last_chunk - n_odd);
+    if (interior) {
+        const char *src = reinterpret_cast<const char *>(reinterpret_cast<const f32x4 *>(in) + c0);
+#pragma unroll
+        for (int j = 0; j < C::NI; ++j) {
+            asm volatile("" : "+v"(boff[j]));        // 32-bit offset next to its use (see stage_tile); in place: no copy
+            const unsigned bo = boff[j];
+            if (j < C::NI - 1 || lane < C::LASTL) {
+                if (NTL && j >= 1 && j <= 16) glds16<2 | (POL & 0xFF)>(src + bo, img + 64 * j);
+                else glds16(src + bo, img + 64 * j);
+            }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < C::NI; ++j) {
+            unsigned bo = boff[j];
+            asm volatile("" : "+v"(bo));
+            long long cc = c0 + (bo >> 4);
+            const f32x4 *src;
+            if (cc < 0) {
+                src = reinterpret_cast<const f32x4 *>(hist) + (cc + C::HIST / 2);
+            } else {
+                if (cc > last_chunk) cc = last_chunk;
+                src = reinterpret_cast<const f32x4 *>(in) + cc;
+            }
+            if (j < C::NI - 1 || lane < C::LASTL) stage_edge_chunk(n_odd && cc == last_chunk, lane, src, img + 64 * j);
+        }
+    }
+}
+
+// The output transposition through the dead image, so that each store instruction writes 1 KiB of consecutive addresses:
+// output chunk c (256 per tile) sits at slot c ^ ((c >> 2) & 1) ^ ((c >> 3) & 3) -- no pad slots.
+// Lane l writes its chunks 4l + k at 4l + (k ^ tw), tw = (l & 1) ^ ((l >> 1) & 3): the 8 lanes a ds_write_b128 is served with
+// hit 8 different slots mod 8; lane l then reads chunks l + 64k' at 64k' + (l ^ tr), tr = ((l >> 2) & 1) ^ ((l >> 3) & 3): the
+// 16 lanes of a ds_read_b128 service group hit 16 different slots mod 16 (searched with tools/lds_bank_model.py's groups: 0
+// conflicts either way; the padded layout of rounds 2-4, c + (c >> 4), had 2-way write conflicts and one pair per read group).
+// (written and read by this wave only: LDS operations of one wave complete in order)
+
+// STP = policy of the stores: 0 nt (shipped), 1 plain, 2 sc0 sc1, 3 sc0 sc1 nt, 4 sc1 (profiling: POL's second byte)
 template <int STP>
 __device__ __forceinline__ void store16_policy(f32x4 v, f32x4 *dst)
 {
@@ -144,9 +198,36 @@ __device__ __forceinline__ void store16_policy(f32x4 v, f32x4 *dst)
     else asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(dst), "v"(v) : "memory");
 }
 
+// the read-back and the four whole-line stores of a full tile's 512 CF32 outputs, from output m0 on (swz_r: the lane's read swizzle tr)
+template <int STP>
+__device__ __forceinline__ void wide_store_full(const f32x4 *img, float *out, long long m0, int lane, int swz_r)
+{
+    f32x4 *dst = reinterpret_cast<f32x4 *>(out + 2 * m0);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const f32x4 v = img[64 * k + (lane ^ swz_r)];
+        store16_policy<STP>(v, dst + 64 * k + lane);
+    }
+}
+
+// ragged last tile of the call: element by element, straight from the registers
+__device__ __forceinline__ void wide_store_ragged(float *out, long long m0, int lane, long long n_out, const f32x4 (&y)[4])
+{
+    const long long m = m0 + 8 * lane;
+    float *dst = out + 2 * m;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (m + 2 * k < n_out) { dst[4 * k] = y[k].x; dst[4 * k + 1] = y[k].y; }
+        if (m + 2 * k + 1 < n_out) { dst[4 * k + 2] = y[k].z; dst[4 * k + 3] = y[k].w; }
+    }
+}
+
+// ABL (profiling): 0 = the real kernel, 1 = staging + stores without the FIR, 5 = phase stamps (per wave 8 x uint64:
+// tiles, cycles issuing DMAs, waiting for data, FIR, transposition + stores, whole wave cycles, whole wave 100 MHz
+// ticks, XCC_ID | HW_ID << 8).
+// NTL, POL: wide_stage_cf32's; POL's next byte = the stores' policy (store16_policy).
 // HALFIN (round 5): CF16 storage (IQ as IEEE half pairs in HBM; fp32 arithmetic; outputs rounded to half once).  The image in LDS
-// is the same CF32 image: typed LDS-DMA (buffer_load_format_x ... lds with a {16, FLOAT} descriptor, sxfir_decim_dense.hip.h) lets the
-// texture path convert on the way in -- instruction j turns source bytes [128 j, 128 j + 128) = chunks [16 j, 16 j + 16) into the
+// is the same CF32 image: typed LDS-DMA (typed_dma_x, sxfir_common.hip.h) lets the texture path convert on the way in -- instruction j turns source bytes [128 j, 128 j + 128) = chunks [16 j, 16 j + 16) into the
 // slots [17 j, 17 j + 16): the image's pad slot after every 16 chunks falls between instructions.  68 typed instructions per tile
 // instead of 19 one-kilobyte DMAs; the FIR below does not know the difference.
 template <int ABL = 0, bool S32IN = false, int NB = 24, bool NTL = true, bool PIN = false, int POL = 0, bool HALFIN = false, bool ASYM = false>
@@ -176,7 +257,7 @@ __global__ __launch_bounds__(64) void decim4_wide_kernel(const DecimTileArgs a)
     // that the waves of one XCD (blockIdx % 8; speed only) hold a contiguous block of the pass.
     const int G = a.n_waves;
     const int b = blockIdx.x;
-    int tile = (a.sched == 0 && a.w8) ? (b & 7) * a.w8 + (b >> 3) : b;
+    int tile = wide_first_tile(b, a.sched, a.w8);
     if (tile >= a.n_tiles) return;
 
     // the 64 distinct taps as SGPR pairs (scalar loads from the constant address space; S32 wire-word plans pass
@@ -202,25 +283,23 @@ __global__ __launch_bounds__(64) void decim4_wide_kernel(const DecimTileArgs a)
         }
     }
 
-    unsigned boff[HALFIN ? 1 : C::NI];
+    unsigned boff[C::NI];
     if constexpr (!HALFIN) {
 #pragma unroll
         for (int j = 0; j < C::NI; ++j) boff[j] = slot_source_offset(64u * j + lane, C::CHUNKS);
     }
     const unsigned img_base = HALFIN ? __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)img) : 0u;   // M0 of the typed DMA = this + a constant
 
+    // (the frame's functions are called through a lambda: called straight from the tile loop they leave the kernel's text another)
     auto stage = [&](int t) __attribute__((always_inline)) {
-        const long long c0 = ((long long)t * C::TILE_IN - C::HALO) >> 1;
-        const bool interior = (c0 >= 0) && (c0 + C::CHUNKS - 1 <= last_chunk - n_odd);
-        if constexpr (HALFIN) {
+        if constexpr (!HALFIN) {
+            wide_stage_cf32<NTL, POL>(img, in, hist, last_chunk, n_odd, lane, boff, t);
+        } else {
+            const long long c0 = ((long long)t * C::TILE_IN - C::HALO) >> 1;
+            const bool interior = (c0 >= 0) && (c0 + C::CHUNKS - 1 <= last_chunk - n_odd);
             if (interior) {
-                // descriptor based at the tile's first byte (64-bit base from scalars, small constant offsets): {16, FLOAT, X <- R}
-                const unsigned long long tb = (unsigned long long)(reinterpret_cast<const char *>(in) + 8 * c0);
-                v4i32 rs;
-                rs.x = __builtin_amdgcn_readfirstlane((int)(unsigned)tb);
-                rs.y = __builtin_amdgcn_readfirstlane((int)(unsigned)(tb >> 32)) & 0xffff;
-                rs.z = 1 << 20;
-                rs.w = 4 | (7 << 12) | (2 << 15);
+                // descriptor based at the tile's first byte; 1 MiB from there
+                const v4i32 rs = typed_dma_descriptor((unsigned long long)(reinterpret_cast<const char *>(in) + 8 * c0), 1 << 20);
                 unsigned voff = 2u * (unsigned)lane;
                 asm volatile("" : "+v"(voff));
 #pragma unroll
@@ -229,12 +308,8 @@ __global__ __launch_bounds__(64) void decim4_wide_kernel(const DecimTileArgs a)
                     const unsigned soff = 128u * (unsigned)j;
                     // rows 8..59 of the 68 belong to this tile alone (nt); the first 8 re-read the previous tile's last kilobyte,
                     // the last 8 are the next tile's halo: plain, as instructions 0, 17, 18 of the CF32 form
-                    if (NTL && j >= 8 && j < C::CHUNKS / 16 - 8)
-                        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_format_x %1, %2, %3 offen nt lds"
-                                     :: "s"(m0v), "v"(voff), "s"(rs), "s"(soff) : "memory");
-                    else
-                        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_format_x %1, %2, %3 offen lds"
-                                     :: "s"(m0v), "v"(voff), "s"(rs), "s"(soff) : "memory");
+                    if (NTL && j >= 8 && j < C::CHUNKS / 16 - 8) typed_dma_x<true>(m0v, voff, rs, soff);
+                    else typed_dma_x<false>(m0v, voff, rs, soff);
                 }
             } else {
                 // edge tiles: chunk by chunk through registers (v_cvt_f32_f16: what the typed DMA does for every non-NaN half)
@@ -256,57 +331,10 @@ __global__ __launch_bounds__(64) void decim4_wide_kernel(const DecimTileArgs a)
                     }
                 }
             }
-            return;
-        }
-        if (interior) {
-            const char *src = reinterpret_cast<const char *>(reinterpret_cast<const f32x4 *>(in) + c0);
-#pragma unroll
-            for (int j = 0; j < C::NI; ++j) {
-                asm volatile("" : "+v"(boff[j]));        // 32-bit offset next to its use (see stage_tile); in place: no copy
-                const unsigned bo = boff[j];
-                if (j < C::NI - 1 || lane < C::LASTL) {
-                    if (NTL && j >= 1 && j <= 16) glds16<2 | (POL & 0xFF)>(src + bo, img + 64 * j);
-                    else glds16(src + bo, img + 64 * j);
-                }
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < C::NI; ++j) {
-                unsigned bo = boff[j];
-                asm volatile("" : "+v"(bo));
-                long long cc = c0 + (bo >> 4);
-                const f32x4 *src;
-                if (cc < 0) {
-                    src = reinterpret_cast<const f32x4 *>(hist) + (cc + C::HIST / 2);
-                } else {
-                    if (cc > last_chunk) cc = last_chunk;
-                    src = reinterpret_cast<const f32x4 *>(in) + cc;
-                }
-                if (j < C::NI - 1 || lane < C::LASTL) {
-                    if (n_odd && cc == last_chunk) {
-                        // the chunk's second sample lies beyond the caller's buffer: 8 bytes through a register
-                        const float2 v = *reinterpret_cast<const float2 *>(src);
-                        img[64 * j + lane] = (f32x4){v.x, v.y, 0.0f, 0.0f};
-                    } else {
-                        glds16(src, img + 64 * j);
-                    }
-                }
-            }
         }
     };
 
-    if (b == a.hist_wave) {
-        float *ho = a.hist_out + (SB / 4) * a.hist_stride * ch;
-        for (int j = lane; j < C::HIST; j += 64) {
-            const long long s = a.n_in - C::HIST + j;
-            if constexpr (HALFIN) {
-                reinterpret_cast<unsigned *>(ho)[j] = s >= 0 ? reinterpret_cast<const unsigned *>(in)[s] : reinterpret_cast<const unsigned *>(hist)[s + C::HIST];
-            } else {
-                const float2 v = s >= 0 ? reinterpret_cast<const float2 *>(in)[s] : reinterpret_cast<const float2 *>(hist)[s + C::HIST];
-                reinterpret_cast<float2 *>(ho)[j] = v;
-            }
-        }
-    }
+    if (b == a.hist_wave) carry_history<SB, C::HIST>(lane, in, hist, a.hist_out + (SB / 4) * a.hist_stride * ch, a.n_in);
 
     // lane l: outputs 8l..8l+7 of the tile; window from chunk 16l (lane stride 17 slots: conflict free)
     const f32x4 *win = img + 17 * lane;
@@ -352,19 +380,10 @@ __global__ __launch_bounds__(64) void decim4_wide_kernel(const DecimTileArgs a)
 
         const long long m0 = (long long)tile * C::TILE_OUT;
         if (m0 + C::TILE_OUT <= a.n_out) {
-            // transposed through the dead image so that each store instruction writes 1 KiB of consecutive
-            // addresses: output chunk c (256 per tile) sits at slot c ^ ((c >> 2) & 1) ^ ((c >> 3) & 3) -- no pad slots.
-            // Lane l writes its chunks 4l + k at 4l + (k ^ tw), tw = (l & 1) ^ ((l >> 1) & 3): the 8 lanes a
-            // ds_write_b128 is served with hit 8 different slots mod 8; lane l then reads chunks l + 64k' at
-            // 64k' + (l ^ tr), tr = ((l >> 2) & 1) ^ ((l >> 3) & 3): the 16 lanes of a ds_read_b128 service group hit
-            // 16 different slots mod 16 (searched with tools/lds_bank_model.py's groups: 0 conflicts either way; the
-            // padded layout of rounds 2-4, c + (c >> 4), had 2-way write conflicts and one pair per read group).
-            // (written and read by this wave only: LDS operations of one wave complete in order)
 #pragma unroll
             for (int k = 0; k < 4; ++k) img[4 * lane + (k ^ swz_w)] = y[k];
             if constexpr (HALFIN) {
                 // two outputs per lane and store: 8 bytes of half pairs, 512 consecutive bytes per instruction
-                typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
                 u32x2 *dst = reinterpret_cast<u32x2 *>(out + m0);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
@@ -372,6 +391,8 @@ __global__ __launch_bounds__(64) void decim4_wide_kernel(const DecimTileArgs a)
                     __builtin_nontemporal_store((u32x2){pack_half2(v.x, v.y), pack_half2(v.z, v.w)}, dst + 64 * k + lane);
                 }
             } else {
+                // wide_store_full's text, in place: through the function the five store-policy instances (POL >= 512) and the two
+                // phase-stamp instances (ABL = 5) of the profiling build come out with other code (LABBOOK.md 17)
                 f32x4 *dst = reinterpret_cast<f32x4 *>(out + 2 * m0);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
@@ -379,24 +400,17 @@ __global__ __launch_bounds__(64) void decim4_wide_kernel(const DecimTileArgs a)
                     store16_policy<(POL >> 8)>(v, dst + 64 * k + lane);
                 }
             }
-        } else {
+        } else if constexpr (HALFIN) {
             // ragged last tile of the call: element by element, straight from the registers
             const long long m = m0 + 8 * lane;
-            if constexpr (HALFIN) {
-                unsigned *dst = reinterpret_cast<unsigned *>(out + m);
+            unsigned *dst = reinterpret_cast<unsigned *>(out + m);
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    if (m + 2 * k < a.n_out) dst[2 * k] = pack_half2(y[k].x, y[k].y);
-                    if (m + 2 * k + 1 < a.n_out) dst[2 * k + 1] = pack_half2(y[k].z, y[k].w);
-                }
-            } else {
-                float *dst = out + 2 * m;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    if (m + 2 * k < a.n_out) { dst[4 * k] = y[k].x; dst[4 * k + 1] = y[k].y; }
-                    if (m + 2 * k + 1 < a.n_out) { dst[4 * k + 2] = y[k].z; dst[4 * k + 3] = y[k].w; }
-                }
+            for (int k = 0; k < 4; ++k) {
+                if (m + 2 * k < a.n_out) dst[2 * k] = pack_half2(y[k].x, y[k].y);
+                if (m + 2 * k + 1 < a.n_out) dst[2 * k + 1] = pack_half2(y[k].z, y[k].w);
             }
+        } else {
+            wide_store_ragged(out, m0, lane, a.n_out, y);
         }
         // the next tile's DMA overwrites the image only after these LDS reads have returned
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

@@ -40,8 +40,7 @@
 
 #include <utility>
 
-#include "sxfir_interp_tile.hip.h"
-#include "sxfir_common.hip.h"            // pk_fma_s_lo / pk_fma_s_hi
+#include "sxfir_interp_tile.hip.h"       // InterpTileArgs (and, through it, sxfir_common.hip.h, sxfir_kernels.hip.h)
 
 namespace sxfir {
 

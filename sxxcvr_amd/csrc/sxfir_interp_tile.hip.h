@@ -24,9 +24,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "sxfir_decim_tile.hip.h"
-#include "sxfir_kernels.hip.h"
-#include "sxfir_decim_dense.hip.h"       // CF16 storage: v4i32, half_lo_to_float / half_hi_to_float, pack_half2
+#include "sxfir_common.hip.h"            // pk_fma_*, permlane32_swap, glds16, the typed LDS-DMA front end, half <-> float
+#include "sxfir_kernels.hip.h"           // tx_words
 
 namespace sxfir {
 
@@ -156,12 +155,7 @@ __global__ __launch_bounds__(64) void interp_tile_kernel(const InterpTileArgs a)
         if constexpr (HALF) {
             if (interior) {
                 // typed LDS-DMA: instruction t moves samples [32 t, 32 t + 32) of the image: 128 source bytes -> 16 slots
-                const unsigned long long wb = (unsigned long long)(reinterpret_cast<const unsigned *>(in) + (q0 - 32));
-                v4i32 rs;
-                rs.x = __builtin_amdgcn_readfirstlane((int)(unsigned)wb);
-                rs.y = __builtin_amdgcn_readfirstlane((int)(unsigned)(wb >> 32)) & 0xffff;    // stride 0
-                rs.z = 1 << 16;
-                rs.w = 4 | (7 << 12) | (2 << 15);                                             // {DATA_FORMAT 16, NUM_FORMAT FLOAT, X <- R}
+                const v4i32 rs = typed_dma_descriptor((unsigned long long)(reinterpret_cast<const unsigned *>(in) + (q0 - 32)), 1 << 16);
                 unsigned voff = 2u * (unsigned)lane;
                 asm volatile("" : "+v"(voff));
                 const unsigned lds_base = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds);
@@ -169,9 +163,7 @@ __global__ __launch_bounds__(64) void interp_tile_kernel(const InterpTileArgs a)
                 for (int t = 0; t < (C::TILE_IN + 32) / 32; ++t) {
                     const unsigned soff = 128u * t;
                     const unsigned m0v = __builtin_amdgcn_readfirstlane(lds_base + 256u * t);
-                    // (M0 is a reserved register to the compiler: writing it here needs, and admits, no clobber entry)
-                    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_format_x %1, %2, %3 offen lds"
-                                 :: "s"(m0v), "v"(voff), "s"(rs), "s"(soff) : "memory");
+                    typed_dma_x<false>(m0v, voff, rs, soff);
                 }
             }
         }
@@ -289,7 +281,6 @@ __global__ __launch_bounds__(64) void interp_tile_kernel(const InterpTileArgs a)
             // chunk oc of the sub-tile: input oc / (L / 2), chunk oc % (L / 2) of its L outputs
             const long long o = NPB == 1 ? o0 + 2 * oc : o0 + (long long)(oc / (L / 2)) * LT + 2 * (oc % (L / 2));
             if constexpr (HALF) {
-                typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
                 if (o + 2 <= o_end)
                     __builtin_nontemporal_store((u32x2){pack_half2(v.x, v.y), pack_half2(v.z, v.w)}, reinterpret_cast<u32x2 *>(out + o));
             } else {
