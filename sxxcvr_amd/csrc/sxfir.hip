@@ -2,6 +2,7 @@
 // "thin extern C shim": plan bookkeeping, kernel selection and launches.
 #include "../../include/sxfir.h"
 #include "../../include/sxfir_complex.h"
+#include "../../include/sxfir_channelizer.h"
 
 #include <hip/hip_runtime.h>
 
@@ -72,6 +73,7 @@
 #include "../../include/sxfir_prof.h"
 #endif
 #include "sxfir_kernels.hip.h"
+#include "sxfir_chan4.hip.h"                    // the 4-band channelizer (include/sxfir_channelizer.h)
 
 namespace {
 
@@ -106,3 +108,4 @@ inline size_t sample_bytes(int fmt) { return fmt == SXFIR_CF16 ? 4 : 8; }   // C
 #include "sxfir_runtime.hip.h"   // synthetic source, converters, time arithmetic, tap design, memory / stream / event helpers
 #include "sxfir_comm.hip.h"      // sxfir_comm_*: the RCCL gather
 #include "sxfir_complex.hip.h"   // sxfir_create_complex, sxfir_design_bandpass (include/sxfir_complex.h)
+#include "sxfir_channelizer.hip.h"   // sxfir_create_channelizer, sxfir_channelize (include/sxfir_channelizer.h)

@@ -38,6 +38,7 @@ struct CallIO {
     size_t out_stride;
     long long n_out;
     hipStream_t st;
+    size_t band_stride;       // channelizer plans (sxfir_channelize): outputs between the bands of a channel; else 0
 };
 // key: count the input samples [lo, hi) of channel 0 that reach the plan's keying threshold into *counter
 struct KeyedRange { unsigned long long *counter; long long lo, hi; };
@@ -66,7 +67,7 @@ struct LaunchGeom {
     int split;                // work items per tile ((tile, block) dealing of decim_blocks_kernel), else 1
     int phase_blocks;         // CF16 interpolator tile kernel: workgroups that share a tile, one per phase block (x48, x96: 3), else 1
 };
-enum { GEOM_GENERIC = 0, GEOM_MULTI = 1, GEOM_WIDE = 2, GEOM_TILE = 3, GEOM_IPASS = 4, GEOM_ITILE = 5, GEOM_CX = 6 };
+enum { GEOM_GENERIC = 0, GEOM_MULTI = 1, GEOM_WIDE = 2, GEOM_TILE = 3, GEOM_IPASS = 4, GEOM_ITILE = 5, GEOM_CX = 6, GEOM_CHAN4 = 7 };
 
 // The strided-pass constants of the /4 kernels: `groups` waves per channel over n_tiles tiles (sched 0: XCD-blocked strided passes,
 // 1: one contiguous run per wave, else plain strided passes), worked out here so that a wave's prologue has no integer division
@@ -127,11 +128,16 @@ static long long first_offset(const sxfir_plan *p)
 // `aligned`: the output is 16-byte aligned with an even channel stride (what the tiled kernels' stores need)
 static LaunchGeom decim_geom(const sxfir_plan *p, long long n_out, long long first, bool aligned, bool aligned_multi)
 {
-    LaunchGeom g{GEOM_GENERIC, p->cx ? "decim_cx_generic_kernel" : "decim_generic_kernel", 256, (n_out + 255) / 256, (n_out + 255) / 256,
+    LaunchGeom g{GEOM_GENERIC, p->bands ? "chan_generic_kernel" : p->cx ? "decim_cx_generic_kernel" : "decim_generic_kernel", 256, (n_out + 255) / 256, (n_out + 255) / 256,
                  (long long)p->compute_units * 8, 1, 1};
     const long long CU = p->compute_units;
     const bool want = p->kernel != SXFIR_KERNEL_GENERIC && first == 0;
-    if (p->cx_tiled && want && aligned) {
+    if (p->chan_tiled && want && aligned) {
+        // channelizer (sxfir_create_channelizer): chan4_kernel for 4 bands x 128 taps on CF32, tiles of 512 outputs PER BAND on the wide
+        // kernel's frame; small calls dealt as fewer generations of waves, the complex-tap rule below
+        set_tiles(g, GEOM_CHAN4, "chan4_kernel", n_out, 512, CU * p->occ_chan);
+        g.groups = clamp_groups(g.resident * generations(p, g.n_tiles, g.resident, true) / p->nchan, g.n_tiles);
+    } else if (p->cx_tiled && want && aligned) {
         // complex taps (sxfir_create_complex): decim4_cx_kernel for /4 x 128 on CF32, the generic complex kernel for everything else.
         // The wide kernel's sixteen generations of waves at the sizes they were measured at, fewer while that would leave a wave
         // under four tiles (generations(): a small call is one strided pass of resident waves)
@@ -246,6 +252,38 @@ static sxfir::DecimTileArgs decim_tile_args(const sxfir_plan *p, const CallIO &c
     return a;
 }
 
+// channelizer plans: the two argument structs of sxfir_chan4.hip.h
+static sxfir::ChanTileArgs chan_tile_args(const sxfir_plan *p, const CallIO &c, const LaunchGeom &geom)
+{
+    sxfir::DecimTileArgs s{};
+    set_schedule(s, geom.n_tiles, geom.groups, 0);          // always XCD-blocked strided passes
+    sxfir::ChanTileArgs a{};
+    a.in = (const float *)c.in;
+    a.hist = (const float *)p->hist_dev;
+    a.hist_out = (float *)p->hist_alt;
+    a.out = (float *)c.out;
+    a.taps = p->taps_dev;
+    a.n_in = (long long)c.n_in;
+    a.n_out = c.n_out;
+    a.in_stride = (long long)c.in_stride;
+    a.out_stride = (long long)c.out_stride;
+    a.band_stride = (long long)c.band_stride;
+    a.hist_stride = p->hist_len;
+    a.n_tiles = s.n_tiles;
+    a.n_waves = s.n_waves;
+    a.w8 = s.w8;
+    a.hist_wave = s.hist_wave;
+    return a;
+}
+
+static sxfir::ChanGenericArgs chan_generic_args(const sxfir_plan *p, const CallIO &c, long long first)
+{
+    sxfir::ChanGenericArgs a{};
+    a.g = generic_args(p, c, first);
+    a.band_stride = (long long)c.band_stride;
+    return a;
+}
+
 static sxfir::InterpTileArgs interp_tile_args(const sxfir_plan *p, const CallIO &c, const LaunchGeom &geom, const KeyedRange *key)
 {
     sxfir::InterpTileArgs t{};
@@ -275,7 +313,8 @@ static int launch_decim(sxfir_plan *p, const CallIO &c, bool *history_done)
     const long long first = first_offset(p);
     // LDS-DMA sources need no 16-byte alignment (verified on MI355X, tools/probe_unaligned.hip): only the
     // output, written with 16-byte stores, must be aligned
-    const bool out16 = (uintptr_t)c.out % 16 == 0;
+    // (a channelizer's bands are stored like channels: an even band stride too)
+    const bool out16 = (uintptr_t)c.out % 16 == 0 && (!p->bands || c.band_stride % 2 == 0);
     const LaunchGeom geom = decim_geom(p, c.n_out, first, out16 && (p->nchan == 1 || c.out_stride % 2 == 0),
                                        out16 && (p->nchan == 1 || c.out_stride % (p->fmt == SXFIR_CF16 ? 4 : 2) == 0));
     const dim3 grid((unsigned)geom.groups, (unsigned)p->nchan);
@@ -284,10 +323,12 @@ static int launch_decim(sxfir_plan *p, const CallIO &c, bool *history_done)
             return fail(SXFIR_EUNSUPPORTED,
                         "tiled kernel needs a 16-byte aligned output, an even output stride and a call that starts on "
                         "an output boundary");
+        if (p->bands) return launch(p->k.chan_generic, grid, 256, c.st, chan_generic_args(p, c, first));
         return launch(p->k.generic, grid, 256, c.st, generic_args(p, c, first));
     }
     if (geom.n_tiles > 0x7fffffffLL) return fail(SXFIR_EINVAL, "call too large");
     *history_done = true;
+    if (geom.kind == GEOM_CHAN4) return launch(p->k.chan4, grid, 64, c.st, chan_tile_args(p, c, geom));
     if (geom.kind == GEOM_MULTI) {
         sxfir::DecimMultiArgs a = decim_multi_args(p, c, geom);
         if (p->blocks) {
@@ -329,6 +370,7 @@ static int check_io(const sxfir_plan *p, int mode, const void *in_dev, size_t n_
 {
     if (!p) return fail(SXFIR_EINVAL, "plan is NULL");
     if (p->mode != mode) return fail(SXFIR_EINVAL, "plan was created for the other direction");
+    if (p->bands) return fail(SXFIR_EINVAL, "a channelizer plan takes sxfir_channelize (include/sxfir_channelizer.h)");
     if ((n_in && !in_dev) || (n_out > 0 && !out_dev)) return fail(SXFIR_EINVAL, "NULL device buffer");
     if (p->nchan > 1 && (in_stride < n_in || out_stride < (size_t)n_out))
         return fail(SXFIR_EINVAL, "channel stride smaller than the block");

@@ -13,12 +13,16 @@ typedef void (*DecimMultiFn)(sxfir::DecimMultiArgs);
 typedef void (*DecimBlocksFn)(sxfir::DecimMultiArgs, sxfir::DecimBlocksJoin);
 typedef void (*DecimTileFn)(sxfir::DecimTileArgs);
 typedef void (*InterpTileFn)(sxfir::InterpTileArgs);
+typedef void (*ChanTileFn)(sxfir::ChanTileArgs);
+typedef void (*ChanGenericFn)(sxfir::ChanGenericArgs);
 struct KernelTable {
     GenericFn generic;           // decim_generic_kernel / decim_cx_generic_kernel / interp_generic_kernel: every plan has one
     DecimMultiFn dense;          // decim_dense_kernel (/8, /16, /32)
     DecimBlocksFn blocks[2];     // decim_blocks_kernel (/48, /96): [0] the walking form, [1] SPLIT, (tile, block) items
     DecimTileFn tile, wide, cx;  // /4: decim4_tile_kernel, decim4_wide_kernel, decim4_cx_kernel (complex taps)
     InterpTileFn interp[2][2];   // [keyed][split]: interp8_pass_kernel; interp_tile_kernel on CF16 storage ([0][0] alone)
+    ChanTileFn chan4;            // channelizer plans (include/sxfir_channelizer.h): chan4_kernel (4 bands x 128 taps, CF32) ...
+    ChanGenericFn chan_generic;  // ... and chan_generic_kernel, which every channelizer plan has INSTEAD of `generic`
 };
 
 struct sxfir_plan {
@@ -86,6 +90,9 @@ struct sxfir_plan {
     bool cx;                  // complex taps (sxfir_create_complex, include/sxfir_complex.h): taps_dev holds a[0, ntaps) then b[0, ntaps)
     bool cx_tiled;            // ... and the shape decim4_cx_kernel takes (/4, 128 taps, CF32)
     int occ_cx;               // its resident waves per CU
+    int bands;                // channelizer plans (sxfir_create_channelizer, include/sxfir_channelizer.h): 4; every other plan: 0
+    bool chan_tiled;          // ... and the shape chan4_kernel takes (4 bands x 128 taps, CF32)
+    int occ_chan;             // its resident waves per CU
     void *hist_dev;        // current history: nchan * hist_len samples
     void *hist_alt;        // the tile kernel writes the next history here, then the two swap
     KernelTable k;         // the instances this plan launches (null: none in this build for that family)
@@ -117,6 +124,15 @@ static GenericFn generic_kernel(int mode, int fmt, bool cx)
     if (fmt == SXFIR_CF32) return interp_generic_kernel<CF32>;
     if (fmt == SXFIR_CF16) return interp_generic_kernel<CF16>;
     return interp_generic_kernel<CF32, S32>;
+}
+
+// channelizer plans: four chains and the butterflies per thread
+static ChanGenericFn chan_generic_kernel_for(int fmt)
+{
+    using namespace sxfir;
+    if (fmt == SXFIR_CF32) return chan_generic_kernel<CF32>;
+    if (fmt == SXFIR_CF16) return chan_generic_kernel<CF16>;
+    return chan_generic_kernel<S32, CF32>;
 }
 
 // /8, /16, /32 with 32 taps per phase: decim_dense_kernel, non-temporal staging loads for the image rows no other tile reads
@@ -214,6 +230,11 @@ static void resolve_kernels(sxfir_plan *p)
 {
     KernelTable &k = p->k;
     k = KernelTable{};
+    if (p->bands) {
+        k.chan_generic = chan_generic_kernel_for(p->fmt);
+        if (p->chan_tiled) k.chan4 = sxfir::chan4_kernel;
+        return;
+    }
     k.generic = generic_kernel(p->mode, p->fmt, p->cx);
     if (p->cx_tiled) k.cx = sxfir::decim4_cx_kernel;
     if (p->dense32) k.dense = dense_kernel(p->ratio, p->fmt);
@@ -719,7 +740,7 @@ int sxfir_set_kernel(sxfir_plan *p, int kernel)
 {
     if (!p) return fail(SXFIR_EINVAL, "plan is NULL");
     if (kernel < SXFIR_KERNEL_AUTO || kernel > SXFIR_KERNEL_GENERIC) return fail(SXFIR_EINVAL, "bad kernel id");
-    if (kernel == SXFIR_KERNEL_TILED && !p->tile_capable && !p->multi_capable && !p->itile_capable && !p->cx_tiled)
+    if (kernel == SXFIR_KERNEL_TILED && !p->tile_capable && !p->multi_capable && !p->itile_capable && !p->cx_tiled && !p->chan_tiled)
         return fail(SXFIR_EUNSUPPORTED, "no tiled kernel for ntaps=%d ratio=%d fmt=%d mode=%d", p->ntaps,
                     p->ratio, p->fmt, p->mode);
     p->kernel = kernel;

@@ -1,4 +1,4 @@
-"""Python face of the C ABI in include/sxfir.h and include/sxfir_complex.h.
+"""Python face of the C ABI in include/sxfir.h, include/sxfir_complex.h and include/sxfir_channelizer.h.
 
 Device memory comes either from torch (complex64 / int32 CUDA tensors, the
 current torch stream is used) or from the library's own sxfir_malloc for
@@ -140,20 +140,11 @@ class Geometry(C.Structure):
                 ("n_tiles", C.c_longlong), ("workgroups", C.c_longlong), ("resident", C.c_longlong)]
 
 
-class Resampler:
-    """One sxfir plan: `nchan` independent channels of one GPU."""
+class _Plan:
+    """What every sxfir_plan answers, whichever entry point created it: the stream state, the numeric contract, the launch
+    geometry and the kernel choice.  Resampler and Channelizer create the plan (self._plan in self._lib) and add their passes."""
 
-    def __init__(self, mode, taps, ratio, nchan=1, fmt="CF32", device=-1, profiling=False):
-        self._lib = load_sxfir(profiling)
-        self.profiling = bool(profiling)
-        self._plan = C.c_void_p()
-        # complex-dtype taps: a complex-tap (band-pass) decimator, sxfir_create_complex; real arrays take sxfir_create as ever
-        cx = np.iscomplexobj(taps)
-        taps = np.ascontiguousarray(taps, dtype=np.complex64 if cx else np.float32)
-        self.mode, self.ratio, self.nchan, self.fmt, self.ntaps = mode, int(ratio), int(nchan), _FMT[fmt], taps.size
-        create = self._lib.sxfir_create_complex if cx else self._lib.sxfir_create
-        self._ck(create(C.byref(self._plan), mode, taps.ctypes.data_as(C.c_void_p), taps.size,
-                        int(ratio), int(nchan), self.fmt, int(device)))
+    _plan = None
 
     def _ck(self, rc):
         _check(rc, self._lib)      # error text from the library this plan lives in
@@ -180,13 +171,6 @@ class Resampler:
         return Contract((a.value, b.value), r.value)
 
     @property
-    def complex_taps(self):
-        """True for a plan with complex taps (sxfir_taps_are_complex)."""
-        f = C.c_int()
-        self._ck(self._lib.sxfir_taps_are_complex(self._plan, C.byref(f)))
-        return bool(f.value)
-
-    @property
     def position(self):
         a, b = C.c_int64(), C.c_int64()
         self._ck(self._lib.sxfir_position(self._plan, C.byref(a), C.byref(b)))
@@ -208,11 +192,44 @@ class Resampler:
     def set_kernel(self, kernel):
         self._ck(self._lib.sxfir_set_kernel(self._plan, kernel))
 
-    def set_tx_threshold(self, threshold2):
-        self._ck(self._lib.sxfir_set_tx_threshold(self._plan, float(threshold2)))
-
     def reset(self, stream=None):
         self._ck(self._lib.sxfir_reset(self._plan, C.c_void_p(stream or 0)))
+
+    def set_history_ptr(self, src_ptr, n, stride, stream=0):
+        """The filter state becomes the last samples of the device block [src_ptr, src_ptr + n) of every channel
+        (sxfir_set_history): as if that block had just been processed."""
+        self._ck(self._lib.sxfir_set_history(self._plan, C.c_void_p(src_ptr), n, stride, C.c_void_p(stream)))
+
+    def set_position(self, consumed):
+        """Place the plan at input sample `consumed` of its stream (sxfir_set_position): a decimator's output phase
+        and output count of the next call follow from it."""
+        self._ck(self._lib.sxfir_set_position(self._plan, int(consumed)))
+
+
+class Resampler(_Plan):
+    """One sxfir plan: `nchan` independent channels of one GPU."""
+
+    def __init__(self, mode, taps, ratio, nchan=1, fmt="CF32", device=-1, profiling=False):
+        self._lib = load_sxfir(profiling)
+        self.profiling = bool(profiling)
+        self._plan = C.c_void_p()
+        # complex-dtype taps: a complex-tap (band-pass) decimator, sxfir_create_complex; real arrays take sxfir_create as ever
+        cx = np.iscomplexobj(taps)
+        taps = np.ascontiguousarray(taps, dtype=np.complex64 if cx else np.float32)
+        self.mode, self.ratio, self.nchan, self.fmt, self.ntaps = mode, int(ratio), int(nchan), _FMT[fmt], taps.size
+        create = self._lib.sxfir_create_complex if cx else self._lib.sxfir_create
+        self._ck(create(C.byref(self._plan), mode, taps.ctypes.data_as(C.c_void_p), taps.size,
+                        int(ratio), int(nchan), self.fmt, int(device)))
+
+    @property
+    def complex_taps(self):
+        """True for a plan with complex taps (sxfir_taps_are_complex)."""
+        f = C.c_int()
+        self._ck(self._lib.sxfir_taps_are_complex(self._plan, C.byref(f)))
+        return bool(f.value)
+
+    def set_tx_threshold(self, threshold2):
+        self._ck(self._lib.sxfir_set_tx_threshold(self._plan, float(threshold2)))
 
     # -- test hooks of the (tile, block) join of the decimators by 48 and 96 (include/sxfir_prof.h) ----------
     def _hook(self, name):
@@ -233,16 +250,6 @@ class Resampler:
     def join_set_counter(self, tile_index, value, stream=0):
         """Write one arrival counter (index: channel * tiles of the call + tile); only reset() puts the plan right again."""
         self._ck(self._hook("sxfir_debug_join_set_counter")(self._plan, int(tile_index), int(value), C.c_void_p(stream or 0)))
-
-    def set_history_ptr(self, src_ptr, n, stride, stream=0):
-        """The filter state becomes the last samples of the device block [src_ptr, src_ptr + n) of every channel
-        (sxfir_set_history): as if that block had just been processed."""
-        self._ck(self._lib.sxfir_set_history(self._plan, C.c_void_p(src_ptr), n, stride, C.c_void_p(stream)))
-
-    def set_position(self, consumed):
-        """Place the plan at input sample `consumed` of its stream (sxfir_set_position): a decimator's output phase
-        and output count of the next call follow from it."""
-        self._ck(self._lib.sxfir_set_position(self._plan, int(consumed)))
 
     # -- raw pointers ---------------------------------------------------------
     def process_ptr(self, in_ptr, n_in, in_stride, out_ptr, out_stride, stream=0):
@@ -340,6 +347,67 @@ class Resampler:
             lib.sxfir_free(din)
             lib.sxfir_free(dout)
         return y[0] if squeeze else y
+
+
+class Channelizer(_Plan):
+    """The 4-band channelizer (include/sxfir_channelizer.h): all `nbands` sub-bands of the /nbands raster out of one wideband
+    stream in one pass.  `taps`: the REAL prototype low-pass (design_lowpass(ntaps, nbands)); band k is the band that
+    design_bandpass(ntaps, nbands, k, nbands) centres, at 0 Hz of its output.  Stream state, contract, geometry and kernel
+    choice are a /nbands decimator's: the same methods as Resampler."""
+
+    def __init__(self, taps, nbands=4, nchan=1, fmt="CF32", device=-1):
+        self._lib = load_sxfir()
+        self._plan = C.c_void_p()
+        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        self.mode, self.ratio, self.nbands, self.nchan, self.fmt, self.ntaps = DECIMATE, int(nbands), int(nbands), int(nchan), _FMT[fmt], taps.size
+        self._ck(self._lib.sxfir_create_channelizer(C.byref(self._plan), taps.ctypes.data_as(C.c_void_p), taps.size, int(nbands),
+                                                    int(nchan), self.fmt, int(device)))
+
+    @property
+    def bands(self):
+        """sxfir_plan_bands: the plan's own count."""
+        n = C.c_int()
+        self._ck(self._lib.sxfir_plan_bands(self._plan, C.byref(n)))
+        return n.value
+
+    def process_ptr(self, in_ptr, n_in, in_stride, out_ptr, out_stride, band_stride, stream=0):
+        """sxfir_channelize: band k of channel c starts at out_ptr + c * out_stride + k * band_stride (samples of the output
+        format); returns the outputs PER BAND."""
+        n_out = C.c_size_t()
+        self._ck(self._lib.sxfir_channelize(self._plan, C.c_void_p(in_ptr), n_in, in_stride, C.c_void_p(out_ptr), out_stride,
+                                            band_stride, C.byref(n_out), C.c_void_p(stream)))
+        return n_out.value
+
+    def process(self, x, out=None):
+        """x: CUDA tensor [nchan, n] or [n]; complex64 (CF32), int32 words (CF16: half pairs) or int32 wire words [.., n, 2]
+        (S32, complex64 out).  Returns [nbands, n_out], or [nchan, nbands, n_out] for a 2-D x.  A caller-given `out` of that
+        shape (or longer rows) supplies its own channel and band strides."""
+        import torch
+        if self.fmt == S32:
+            x = torch.view_as_complex(x.view(torch.float32))               # same 8 bytes per sample
+        out_dtype = torch.complex64 if self.fmt == S32 else x.dtype
+        squeeze = x.dim() == 1
+        x2 = x.unsqueeze(0) if squeeze else x
+        if x2.dim() != 2 or x2.shape[0] != self.nchan or (x2.shape[1] > 1 and x2.stride(1) != 1):
+            raise ValueError("expected a [nchan=%d, n] tensor with unit sample stride" % self.nchan)
+        n_in = x2.shape[1]
+        n_out = self.outputs_for(n_in)
+        if out is None:
+            # rows of whole 16-byte units: an odd band stride would break the tiled kernel's store alignment
+            q = 4 if self.fmt == CF16 else 2
+            out = torch.empty((self.nchan, self.nbands, -(-n_out // q) * q), dtype=out_dtype, device=x2.device)
+        o3 = out.unsqueeze(0) if out.dim() == 2 else out
+        # the kernel writes through a raw pointer: a caller-supplied `out` must really hold the result
+        if (o3.dim() != 3 or o3.shape[0] != self.nchan or o3.shape[1] != self.nbands or o3.shape[2] < n_out
+                or (o3.shape[2] > 1 and o3.stride(2) != 1) or o3.dtype != out_dtype or o3.device != x2.device):
+            raise ValueError("out must be a [nchan=%d, nbands=%d, >=%d] %s tensor with unit sample stride on %s" % (
+                self.nchan, self.nbands, n_out, out_dtype, x2.device))
+        got = self.process_ptr(x2.data_ptr(), n_in, x2.stride(0) if self.nchan > 1 else n_in, o3.data_ptr(),
+                               o3.stride(0) if self.nchan > 1 else 0, max(o3.stride(1), n_out),
+                               torch.cuda.current_stream(x2.device).cuda_stream)
+        assert got == n_out
+        res = o3[:, :, :n_out]
+        return res[0] if squeeze else res
 
 
 class PipelinedResampler:
