@@ -129,6 +129,11 @@ def load_sxfir(profiling=False):
         "sxfir_create_channelizer": (ci, [P(vp), vp, ci, ci, ci, ci, ci]),
         "sxfir_channelize": (ci, [vp, vp, sz, sz, vp, sz, sz, P(sz), vp]),
         "sxfir_plan_bands": (ci, [vp, P(ci)]),
+        # include/sxfir_synthesizer.h: the 4-band synthesizer
+        "sxfir_synthesizer_abi_version": (ci, []),
+        "sxfir_create_synthesizer": (ci, [P(vp), vp, ci, ci, ci, ci, ci]),
+        "sxfir_synthesize": (ci, [vp, vp, sz, sz, sz, vp, sz, P(sz), vp]),
+        "sxfir_plan_synthesis_bands": (ci, [vp, P(ci)]),
     }
     if profiling:
         sig["sxfir_debug_clock"] = (ci, [vp, P(dbl)])

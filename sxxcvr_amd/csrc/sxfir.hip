@@ -3,6 +3,7 @@
 #include "../../include/sxfir.h"
 #include "../../include/sxfir_complex.h"
 #include "../../include/sxfir_channelizer.h"
+#include "../../include/sxfir_synthesizer.h"
 
 #include <hip/hip_runtime.h>
 
@@ -74,6 +75,7 @@
 #endif
 #include "sxfir_kernels.hip.h"
 #include "sxfir_chan4.hip.h"                    // the 4-band channelizer (include/sxfir_channelizer.h)
+#include "sxfir_synthesis4.hip.h"               // the 4-band synthesizer (include/sxfir_synthesizer.h)
 
 namespace {
 
@@ -109,3 +111,4 @@ inline size_t sample_bytes(int fmt) { return fmt == SXFIR_CF16 ? 4 : 8; }   // C
 #include "sxfir_comm.hip.h"      // sxfir_comm_*: the RCCL gather
 #include "sxfir_complex.hip.h"   // sxfir_create_complex, sxfir_design_bandpass (include/sxfir_complex.h)
 #include "sxfir_channelizer.hip.h"   // sxfir_create_channelizer, sxfir_channelize (include/sxfir_channelizer.h)
+#include "sxfir_synthesizer.hip.h"   // sxfir_create_synthesizer, sxfir_synthesize (include/sxfir_synthesizer.h)

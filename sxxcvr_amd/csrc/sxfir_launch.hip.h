@@ -38,7 +38,8 @@ struct CallIO {
     size_t out_stride;
     long long n_out;
     hipStream_t st;
-    size_t band_stride;       // channelizer plans (sxfir_channelize): outputs between the bands of a channel; else 0
+    size_t band_stride;       // channelizer plans (sxfir_channelize): outputs between the bands of a channel; synthesizer plans
+                              // (sxfir_synthesize): inputs between them; else 0
 };
 // key: count the input samples [lo, hi) of channel 0 that reach the plan's keying threshold into *counter
 struct KeyedRange { unsigned long long *counter; long long lo, hi; };
@@ -67,7 +68,7 @@ struct LaunchGeom {
     int split;                // work items per tile ((tile, block) dealing of decim_blocks_kernel), else 1
     int phase_blocks;         // CF16 interpolator tile kernel: workgroups that share a tile, one per phase block (x48, x96: 3), else 1
 };
-enum { GEOM_GENERIC = 0, GEOM_MULTI = 1, GEOM_WIDE = 2, GEOM_TILE = 3, GEOM_IPASS = 4, GEOM_ITILE = 5, GEOM_CX = 6, GEOM_CHAN4 = 7 };
+enum { GEOM_GENERIC = 0, GEOM_MULTI = 1, GEOM_WIDE = 2, GEOM_TILE = 3, GEOM_IPASS = 4, GEOM_ITILE = 5, GEOM_CX = 6, GEOM_CHAN4 = 7, GEOM_SYN4 = 8 };
 
 // The strided-pass constants of the /4 kernels: `groups` waves per channel over n_tiles tiles (sched 0: XCD-blocked strided passes,
 // 1: one contiguous run per wave, else plain strided passes), worked out here so that a wave's prologue has no integer division
@@ -166,6 +167,17 @@ static LaunchGeom decim_geom(const sxfir_plan *p, long long n_out, long long fir
 
 static LaunchGeom interp_geom(const sxfir_plan *p, long long n_in, bool aligned, bool keyed)
 {
+    if (p->syn_bands) {
+        // synthesizer (sxfir_create_synthesizer): synthesis4_kernel for 4 bands x 128 taps on CF32, tiles of 256 inputs PER BAND on the x4
+        // pass kernel's frame; one thread per input index of synthesis_generic_kernel for everything else.  Small calls dealt as fewer
+        // generations of waves, the channelizer's rule
+        LaunchGeom s{GEOM_GENERIC, "synthesis_generic_kernel", 256, (n_in + 255) / 256, (n_in + 255) / 256, (long long)p->compute_units * 8, 1, 1};
+        if (p->syn_tiled && p->kernel != SXFIR_KERNEL_GENERIC && aligned) {
+            set_tiles(s, GEOM_SYN4, "synthesis4_kernel", n_in, 256, (long long)p->compute_units * p->occ_syn);
+            s.groups = clamp_groups(s.resident * generations(p, s.n_tiles, s.resident, true) / p->nchan, s.n_tiles);
+        }
+        return s;
+    }
     const long long n_out = n_in * p->ratio;
     LaunchGeom g{GEOM_GENERIC, "interp_generic_kernel", 256, (n_out + 255) / 256, (n_out + 255) / 256,
                  (long long)p->compute_units * 8, 1, 1};
@@ -284,6 +296,34 @@ static sxfir::ChanGenericArgs chan_generic_args(const sxfir_plan *p, const CallI
     return a;
 }
 
+// synthesizer plans: the two argument structs of sxfir_synthesis4.hip.h
+static sxfir::SynTileArgs syn_tile_args(const sxfir_plan *p, const CallIO &c, const LaunchGeom &geom)
+{
+    sxfir::SynTileArgs a{};
+    a.in = (const float *)c.in;
+    a.hist = (const float *)p->hist_dev;
+    a.hist_out = (float *)p->hist_alt;
+    a.out = (float *)c.out;
+    a.taps = p->taps_scaled_dev;                    // the phase-major table
+    a.n_in = (long long)c.n_in;
+    a.in_stride = (long long)c.in_stride;
+    a.band_stride = (long long)c.band_stride;
+    a.out_stride = (long long)c.out_stride;
+    a.hist_stride = p->hist_len;
+    a.n_tiles = (int)geom.n_tiles;
+    a.n_groups = (int)geom.groups;
+    return a;
+}
+
+static sxfir::SynGenericArgs syn_generic_args(const sxfir_plan *p, const CallIO &c)
+{
+    sxfir::SynGenericArgs a{};
+    a.g = generic_args(p, c, 0);
+    a.g.hist_len = p->hist_len / p->syn_bands;      // a band's history; hist_stride stays the channel's
+    a.band_stride = (long long)c.band_stride;
+    return a;
+}
+
 static sxfir::InterpTileArgs interp_tile_args(const sxfir_plan *p, const CallIO &c, const LaunchGeom &geom, const KeyedRange *key)
 {
     sxfir::InterpTileArgs t{};
@@ -369,6 +409,7 @@ static int check_io(const sxfir_plan *p, int mode, const void *in_dev, size_t n_
                     const void *out_dev, size_t out_stride, long long n_out)
 {
     if (!p) return fail(SXFIR_EINVAL, "plan is NULL");
+    if (p->syn_bands) return fail(SXFIR_EINVAL, "a synthesizer plan takes sxfir_synthesize (include/sxfir_synthesizer.h)");
     if (p->mode != mode) return fail(SXFIR_EINVAL, "plan was created for the other direction");
     if (p->bands) return fail(SXFIR_EINVAL, "a channelizer plan takes sxfir_channelize (include/sxfir_channelizer.h)");
     if ((n_in && !in_dev) || (n_out > 0 && !out_dev)) return fail(SXFIR_EINVAL, "NULL device buffer");
@@ -431,6 +472,40 @@ static int launch_interp(sxfir_plan *p, const CallIO &c, bool *history_done, con
     return launch(p->k.interp[key != nullptr][geom.split > 1], grid, 64, c.st, t);
 }
 
+// Synthesizer plans (sxfir_synthesize): the kernel alone, as launch_interp.  The tiled kernel's LDS-DMA and edge loads need no more
+// than the sample alignment the entry point has checked (so an odd band or channel stride of the INPUT is its business too); its
+// 16-byte stores need an aligned output and, between channels, an even output stride.
+static int launch_synth(sxfir_plan *p, const CallIO &c, bool *history_done)
+{
+    *history_done = false;
+    const LaunchGeom geom = interp_geom(p, (long long)c.n_in, ((uintptr_t)c.out % 16 == 0) && (p->nchan == 1 || c.out_stride % 2 == 0), false);
+    const dim3 grid((unsigned)geom.groups, (unsigned)p->nchan);
+    if (geom.kind == GEOM_GENERIC) {
+        if (p->kernel == SXFIR_KERNEL_TILED)
+            return fail(SXFIR_EUNSUPPORTED, "tiled synthesizer needs a 16-byte aligned output and an even output stride");
+        return launch(p->k.syn_generic, grid, 256, c.st, syn_generic_args(p, c));
+    }
+    if (int rc = need_tap_table(p, TAPS_PHASE4, "synthesis4_kernel")) return rc;
+    if (geom.n_tiles > 0x7fffffffLL) return fail(SXFIR_EINVAL, "call too large");
+    *history_done = true;
+    return launch(p->k.syn4, grid, 64, c.st, syn_tile_args(p, c, geom));
+}
+
+// Generic path of a synthesizer plan: every band's history to the plan's other buffer.
+static int launch_synth_history(sxfir_plan *p, const CallIO &c)
+{
+    const int hb = p->hist_len / p->syn_bands;
+    const dim3 grid((unsigned)((hb + 255) / 256), (unsigned)p->nchan, (unsigned)p->syn_bands);
+    if (p->fmt != SXFIR_CF16)
+        hipLaunchKernelGGL(sxfir::synthesis_history_kernel<float2>, grid, dim3(256), 0, c.st, (float2 *)p->hist_alt, (const float2 *)p->hist_dev,
+                           (const float2 *)c.in, (long long)c.n_in, (long long)c.in_stride, (long long)c.band_stride, hb);
+    else
+        hipLaunchKernelGGL(sxfir::synthesis_history_kernel<uint32_t>, grid, dim3(256), 0, c.st, (uint32_t *)p->hist_alt, (const uint32_t *)p->hist_dev,
+                           (const uint32_t *)c.in, (long long)c.n_in, (long long)c.in_stride, (long long)c.band_stride, hb);
+    HIPCHECK(hipGetLastError());
+    return SXFIR_OK;
+}
+
 // Shapes the tiled kernels do not take: the keying count as a pass of its own (same rule, same counter).  Queued by
 // interpolate_impl AFTER the history launch has succeeded, with the position commit: a call that fails half way has not
 // touched the counter, so a caller that retries the block does not count it twice (on the tiled paths the count is part of
@@ -485,6 +560,7 @@ int sxfir_interpolate_keyed(sxfir_plan *p, const void *in_dev, size_t n_in, size
 {
     if (n_out_p) *n_out_p = 0;
     if (!p) return fail(SXFIR_EINVAL, "plan is NULL");
+    if (p->syn_bands) return fail(SXFIR_EINVAL, "a synthesizer plan takes sxfir_synthesize (include/sxfir_synthesizer.h): no keying count in its version 1");
     if (p->mode != SXFIR_INTERPOLATE) return fail(SXFIR_EINVAL, "not an interpolator plan");
     if (p->fmt == SXFIR_CF16) return fail(SXFIR_EUNSUPPORTED, "the keying count is defined on CF32 input");
     if (!counter || ((uintptr_t)counter & 7)) return fail(SXFIR_EINVAL, "counter must be an 8-byte aligned device word");
@@ -503,7 +579,7 @@ int sxfir_launch_geometry(const sxfir_plan *p, size_t n_in, sxfir_geometry *out)
     out->tiled = g.kind != GEOM_GENERIC;
     out->split = g.split;
     out->tile_samples = g.tile_out * p->ratio;       // wideband samples: a decimator's inputs, an interpolator's outputs
-    if (g.kind == GEOM_GENERIC) out->tile_samples = p->mode == SXFIR_DECIMATE ? 256LL * p->ratio : 256;
+    if (g.kind == GEOM_GENERIC) out->tile_samples = p->mode == SXFIR_DECIMATE ? 256LL * p->ratio : (p->syn_bands ? 1024 : 256);
     out->n_tiles = g.n_tiles;
     out->workgroups = g.groups * p->nchan;
     out->resident = g.resident;

@@ -4,7 +4,7 @@
 // Included by sxfir.hip after the kernel headers; not a stand-alone translation unit.
 #pragma once
 
-enum TapTable { TAPS_SCALED = 0, TAPS_SUBSET8 = 1, TAPS_PASS8 = 2, TAPS_BLOCKS16 = 3 };
+enum TapTable { TAPS_SCALED = 0, TAPS_SUBSET8 = 1, TAPS_PASS8 = 2, TAPS_BLOCKS16 = 3, TAPS_PHASE4 = 4 };
 
 // One typed kernel pointer per launch-argument family, and a plan's kernels: resolved once by sxfir_create /
 // sxfir_create_complex (resolve_kernels below), read by the occupancy queries there and by the launches (sxfir_launch.hip.h).
@@ -15,6 +15,8 @@ typedef void (*DecimTileFn)(sxfir::DecimTileArgs);
 typedef void (*InterpTileFn)(sxfir::InterpTileArgs);
 typedef void (*ChanTileFn)(sxfir::ChanTileArgs);
 typedef void (*ChanGenericFn)(sxfir::ChanGenericArgs);
+typedef void (*SynTileFn)(sxfir::SynTileArgs);
+typedef void (*SynGenericFn)(sxfir::SynGenericArgs);
 struct KernelTable {
     GenericFn generic;           // decim_generic_kernel / decim_cx_generic_kernel / interp_generic_kernel: every plan has one
     DecimMultiFn dense;          // decim_dense_kernel (/8, /16, /32)
@@ -23,6 +25,8 @@ struct KernelTable {
     InterpTileFn interp[2][2];   // [keyed][split]: interp8_pass_kernel; interp_tile_kernel on CF16 storage ([0][0] alone)
     ChanTileFn chan4;            // channelizer plans (include/sxfir_channelizer.h): chan4_kernel (4 bands x 128 taps, CF32) ...
     ChanGenericFn chan_generic;  // ... and chan_generic_kernel, which every channelizer plan has INSTEAD of `generic`
+    SynTileFn syn4;              // synthesizer plans (include/sxfir_synthesizer.h): synthesis4_kernel (4 bands x 128 taps, CF32) ...
+    SynGenericFn syn_generic;    // ... and synthesis_generic_kernel, which every synthesizer plan has INSTEAD of `generic`
 };
 
 struct sxfir_plan {
@@ -80,6 +84,7 @@ struct sxfir_plan {
     int tap_table;            // TAPS_SCALED: taps * 2^-31 (exact) in tap order, for the /4 scalar-tap kernels on S32 wire words;
                               // TAPS_SUBSET8: the subset-major table of decim_dense_kernel<8, ..., SUBSET> (times 2^-31 for S32 plans);
                               // TAPS_PASS8: the pass-major table of interp8_pass_kernel (pass (c, p) at 64 (2c + p), (jj, rr) at 4 jj + rr).
+                              // TAPS_PHASE4: the phase-major table of synthesis4_kernel (h[4j + r] at (ntaps / 4) r + j).
                               // Every launch that hands taps_scaled_dev to a kernel checks this first (need_tap_table).
     bool ipass;               // x8, 256 taps, CF32: interp8_pass_kernel (scalar taps, four passes per tile)
     int occ_ipass;
@@ -93,6 +98,10 @@ struct sxfir_plan {
     int bands;                // channelizer plans (sxfir_create_channelizer, include/sxfir_channelizer.h): 4; every other plan: 0
     bool chan_tiled;          // ... and the shape chan4_kernel takes (4 bands x 128 taps, CF32)
     int occ_chan;             // its resident waves per CU
+    int syn_bands;            // synthesizer plans (sxfir_create_synthesizer, include/sxfir_synthesizer.h): 4; every other plan: 0.  hist_dev
+                              // holds 4 x hist_len / 4 samples per channel, band k's at k * hist_len / 4
+    bool syn_tiled;           // ... and the shape synthesis4_kernel takes (4 bands x 128 taps, CF32)
+    int occ_syn;              // its resident waves per CU
     void *hist_dev;        // current history: nchan * hist_len samples
     void *hist_alt;        // the tile kernel writes the next history here, then the two swap
     KernelTable k;         // the instances this plan launches (null: none in this build for that family)
@@ -225,6 +234,15 @@ static InterpTileFn interp_kernel(int ratio, int fmt, bool keyed, bool split)
     return nullptr;
 }
 
+// synthesizer plans: the butterflies once per input index, four phase chains per thread
+static SynGenericFn synthesis_generic_kernel_for(int fmt)
+{
+    using namespace sxfir;
+    if (fmt == SXFIR_CF32) return synthesis_generic_kernel<CF32>;
+    if (fmt == SXFIR_CF16) return synthesis_generic_kernel<CF16>;
+    return synthesis_generic_kernel<CF32, S32>;
+}
+
 // The plan's kernels, from the capability flags sxfir_create has settled (the profiling knobs included)
 static void resolve_kernels(sxfir_plan *p)
 {
@@ -233,6 +251,11 @@ static void resolve_kernels(sxfir_plan *p)
     if (p->bands) {
         k.chan_generic = chan_generic_kernel_for(p->fmt);
         if (p->chan_tiled) k.chan4 = sxfir::chan4_kernel;
+        return;
+    }
+    if (p->syn_bands) {
+        k.syn_generic = synthesis_generic_kernel_for(p->fmt);
+        if (p->syn_tiled) k.syn4 = sxfir::synthesis4_kernel;
         return;
     }
     k.generic = generic_kernel(p->mode, p->fmt, p->cx);
@@ -716,6 +739,8 @@ int sxfir_reset(sxfir_plan *p, void *stream)
 int sxfir_set_history(sxfir_plan *p, const void *src_dev, size_t n, size_t stride, void *stream)
 {
     if (!p || !src_dev) return fail(SXFIR_EINVAL, "NULL argument");
+    if (p->syn_bands)
+        return fail(SXFIR_EUNSUPPORTED, "sxfir_set_history has one stride: it cannot name the bands and the channels of a synthesizer plan's input");
     if (n < (size_t)p->hist_len) return fail(SXFIR_EINVAL, "history needs %d samples per channel, %zu given", p->hist_len, n);
     if (p->nchan > 1 && stride < n) return fail(SXFIR_EINVAL, "channel stride %zu shorter than the block (%zu)", stride, n);
     const size_t sb = sample_bytes(p->fmt);
@@ -740,7 +765,7 @@ int sxfir_set_kernel(sxfir_plan *p, int kernel)
 {
     if (!p) return fail(SXFIR_EINVAL, "plan is NULL");
     if (kernel < SXFIR_KERNEL_AUTO || kernel > SXFIR_KERNEL_GENERIC) return fail(SXFIR_EINVAL, "bad kernel id");
-    if (kernel == SXFIR_KERNEL_TILED && !p->tile_capable && !p->multi_capable && !p->itile_capable && !p->cx_tiled && !p->chan_tiled)
+    if (kernel == SXFIR_KERNEL_TILED && !p->tile_capable && !p->multi_capable && !p->itile_capable && !p->cx_tiled && !p->chan_tiled && !p->syn_tiled)
         return fail(SXFIR_EUNSUPPORTED, "no tiled kernel for ntaps=%d ratio=%d fmt=%d mode=%d", p->ntaps,
                     p->ratio, p->fmt, p->mode);
     p->kernel = kernel;

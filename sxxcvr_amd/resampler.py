@@ -1,4 +1,4 @@
-"""Python face of the C ABI in include/sxfir.h, include/sxfir_complex.h and include/sxfir_channelizer.h.
+"""Python face of the C ABI in include/sxfir.h, include/sxfir_complex.h, include/sxfir_channelizer.h and include/sxfir_synthesizer.h.
 
 Device memory comes either from torch (complex64 / int32 CUDA tensors, the
 current torch stream is used) or from the library's own sxfir_malloc for
@@ -142,7 +142,7 @@ class Geometry(C.Structure):
 
 class _Plan:
     """What every sxfir_plan answers, whichever entry point created it: the stream state, the numeric contract, the launch
-    geometry and the kernel choice.  Resampler and Channelizer create the plan (self._plan in self._lib) and add their passes."""
+    geometry and the kernel choice.  Resampler, Channelizer and Synthesizer create the plan (self._plan in self._lib) and add their passes."""
 
     _plan = None
 
@@ -407,6 +407,68 @@ class Channelizer(_Plan):
                                torch.cuda.current_stream(x2.device).cuda_stream)
         assert got == n_out
         res = o3[:, :, :n_out]
+        return res[0] if squeeze else res
+
+
+class Synthesizer(_Plan):
+    """The 4-band synthesizer (include/sxfir_synthesizer.h): `nbands` sub-bands of the x nbands raster into one wideband stream in one
+    pass -- what Channelizer takes apart, put together.  `taps`: the REAL prototype low-pass of a x nbands interpolator
+    (design_lowpass(ntaps, nbands, gain=nbands)); band k lands at k / nbands cycles per output sample.  Stream state, contract,
+    geometry and kernel choice are a x nbands interpolator's: the same methods as Resampler (set_history_ptr is refused)."""
+
+    def __init__(self, taps, nbands=4, nchan=1, fmt="CF32", device=-1):
+        self._lib = load_sxfir()
+        self._plan = C.c_void_p()
+        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        self.mode, self.ratio, self.nbands, self.nchan, self.fmt, self.ntaps = INTERPOLATE, int(nbands), int(nbands), int(nchan), _FMT[fmt], taps.size
+        self._ck(self._lib.sxfir_create_synthesizer(C.byref(self._plan), taps.ctypes.data_as(C.c_void_p), taps.size, int(nbands),
+                                                    int(nchan), self.fmt, int(device)))
+
+    @property
+    def bands(self):
+        """sxfir_plan_synthesis_bands: the plan's own count."""
+        n = C.c_int()
+        self._ck(self._lib.sxfir_plan_synthesis_bands(self._plan, C.byref(n)))
+        return n.value
+
+    def set_tx_threshold(self, threshold2):
+        self._ck(self._lib.sxfir_set_tx_threshold(self._plan, float(threshold2)))
+
+    def process_ptr(self, in_ptr, n_in, in_stride, band_stride, out_ptr, out_stride, stream=0):
+        """sxfir_synthesize: band k of channel c is read at in_ptr + c * in_stride + k * band_stride (samples of the input format),
+        n_in inputs PER BAND; returns the wideband outputs per channel (4 n_in)."""
+        n_out = C.c_size_t()
+        self._ck(self._lib.sxfir_synthesize(self._plan, C.c_void_p(in_ptr), n_in, in_stride, band_stride, C.c_void_p(out_ptr), out_stride,
+                                            C.byref(n_out), C.c_void_p(stream)))
+        return n_out.value
+
+    def process(self, x, out=None):
+        """x: CUDA tensor [nbands, n] or [nchan, nbands, n], possibly strided between bands and channels; complex64 (CF32 and S32
+        plans) or int32 words (CF16: half pairs).  Returns [nbands * n], or [nchan, nbands * n] for a 3-D x: complex64, int32 words
+        (CF16) or int32 wire words [.., nbands * n, 2] (S32).  A caller-given `out` of that shape (or longer rows) supplies its own
+        channel stride."""
+        import torch
+        squeeze = x.dim() == 2
+        x3 = x.unsqueeze(0) if squeeze else x
+        if x3.dim() != 3 or x3.shape[0] != self.nchan or x3.shape[1] != self.nbands or (x3.shape[2] > 1 and x3.stride(2) != 1):
+            raise ValueError("expected a [nchan=%d, nbands=%d, n] tensor with unit sample stride" % (self.nchan, self.nbands))
+        n_in = x3.shape[2]
+        n_out = self.outputs_for(n_in)
+        if self.fmt == S32 and out is not None:
+            out = torch.view_as_complex(out.view(torch.float32))          # same 8 bytes per sample
+        if out is None:
+            out = torch.empty((self.nchan, n_out), dtype=x3.dtype, device=x3.device)
+        o2 = out.unsqueeze(0) if out.dim() == 1 else out
+        # the kernel writes through a raw pointer: a caller-supplied `out` must really hold the result
+        if (o2.dim() != 2 or o2.shape[0] != self.nchan or o2.shape[1] < n_out or (o2.shape[1] > 1 and o2.stride(1) != 1)
+                or o2.dtype != x3.dtype or o2.device != x3.device):
+            raise ValueError("out must be a [nchan=%d, >=%d] %s tensor with unit sample stride on %s" % (self.nchan, n_out, x3.dtype, x3.device))
+        got = self.process_ptr(x3.data_ptr(), n_in, x3.stride(0) if self.nchan > 1 else 0, max(x3.stride(1), n_in), o2.data_ptr(),
+                               o2.stride(0) if self.nchan > 1 else max(n_out, 1), torch.cuda.current_stream(x3.device).cuda_stream)
+        assert got == n_out
+        res = o2[:, :n_out]
+        if self.fmt == S32:
+            res = torch.view_as_real(res).view(torch.int32)
         return res[0] if squeeze else res
 
 
