@@ -1,25 +1,11 @@
 // Launches of the C ABI: the launch geometry of a call (which kernel family, which grid), one builder per argument struct,
-// launch_decim / launch_interp, and the streaming entry points sxfir_decimate / sxfir_interpolate / sxfir_interpolate_keyed
-// (launch, history carry-over, position commit).  WHICH instance a plan launches is not decided here: sxfir_create resolved
-// it from the kernel table (sxfir_plan.hip.h) into p->k.  The product path reads straight through; what the profiling build
-// adds sits behind the prof_* hooks of sxfir_prof_dispatch.inc.  Included by sxfir.hip after sxfir_plan.hip.h.
+// launch_decim / launch_interp / launch_synth, and the call frame every streaming entry point ends in: stream_call (launch_call,
+// history carry-over, keyed count, position commit) behind the entry point's own argument checks -- sxfir_decimate,
+// sxfir_interpolate and sxfir_interpolate_keyed here, sxfir_channelize and sxfir_synthesize in their own headers.  WHICH instance a
+// plan launches is not decided here: its creator resolved it from the kernel table (sxfir_plan.hip.h) into p->k.  The product path
+// reads straight through; what the profiling build adds sits behind the prof_* hooks of sxfir_prof_dispatch.inc.  Included by
+// sxfir.hip after sxfir_plan.hip.h.
 #pragma once
-
-// Generic path: the next call's history goes to the plan's other buffer (the caller swaps the two).
-static int launch_history(sxfir_plan *p, const void *in_dev, size_t n_in, size_t in_stride, hipStream_t st)
-{
-    const dim3 grid((unsigned)((p->hist_len + 255) / 256), (unsigned)p->nchan);
-    if (p->fmt != SXFIR_CF16)
-        hipLaunchKernelGGL(sxfir::history_kernel<float2>, grid, dim3(256), 0, st, (float2 *)p->hist_alt,
-                           (const float2 *)p->hist_dev, (const float2 *)in_dev, (long long)n_in, (long long)in_stride,
-                           (long long)p->hist_len, p->hist_len);
-    else
-        hipLaunchKernelGGL(sxfir::history_kernel<uint32_t>, grid, dim3(256), 0, st, (uint32_t *)p->hist_alt,
-                           (const uint32_t *)p->hist_dev, (const uint32_t *)in_dev, (long long)n_in,
-                           (long long)in_stride, (long long)p->hist_len, p->hist_len);
-    HIPCHECK(hipGetLastError());
-    return SXFIR_OK;
-}
 
 // A launch that hands taps_scaled_dev to a kernel states which layout that kernel reads; sxfir_create chose the layout
 // from the same plan flags, so a mismatch means the two sides were changed apart: refuse instead of filtering with
@@ -41,6 +27,41 @@ struct CallIO {
     size_t band_stride;       // channelizer plans (sxfir_channelize): outputs between the bands of a channel; synthesizer plans
                               // (sxfir_synthesize): inputs between them; else 0
 };
+
+// What the tiled kernels' 16-byte stores need: an aligned output and, between channels, an even stride -- whole 16-byte units of
+// halves (a stride of 4) for the multi-column and dense kernels on CF16 storage; a channelizer's bands are stored like channels:
+// an even band stride too.  (LDS-DMA sources need no 16-byte alignment -- verified on MI355X, tools/probe_unaligned.hip -- and the
+// edge loads go sample by sample: the input's alignment and strides are the entry point's business alone.)  The stride of 4 holds
+// for every kernel of a multi_capable CF16 plan; that is right only while no CF16 plan is both multi_capable and tile_capable
+// (sxfir_create: half4_wide excludes multi, the `mu` knob is CF32 only) -- a shape with both would need 2 for its tile kernel.
+static bool stores_aligned(const sxfir_plan *p, const CallIO &c)
+{
+    const size_t q = p->multi_capable && p->fmt == SXFIR_CF16 ? 4 : 2;
+    return (uintptr_t)c.out % 16 == 0 && (p->nchan == 1 || c.out_stride % q == 0) && (p->kind != KIND_CHANNELIZER || c.band_stride % 2 == 0);
+}
+
+// Generic path: the next call's history goes to the plan's other buffer (stream_call swaps the two); a synthesizer's, band by band
+template <typename T>
+static void launch_history_of(sxfir_plan *p, const CallIO &c)
+{
+    T *next = (T *)p->hist_alt;
+    const T *hist = (const T *)p->hist_dev, *in = (const T *)c.in;
+    if (p->kind == KIND_SYNTHESIZER) {
+        const int hb = p->hist_len / p->bands;
+        hipLaunchKernelGGL(sxfir::synthesis_history_kernel<T>, dim3((unsigned)((hb + 255) / 256), (unsigned)p->nchan, (unsigned)p->bands), dim3(256), 0, c.st,
+                           next, hist, in, (long long)c.n_in, (long long)c.in_stride, (long long)c.band_stride, hb);
+    } else {
+        hipLaunchKernelGGL(sxfir::history_kernel<T>, dim3((unsigned)((p->hist_len + 255) / 256), (unsigned)p->nchan), dim3(256), 0, c.st,
+                           next, hist, in, (long long)c.n_in, (long long)c.in_stride, (long long)p->hist_len, p->hist_len);
+    }
+}
+static int launch_history(sxfir_plan *p, const CallIO &c)
+{
+    if (p->fmt != SXFIR_CF16) launch_history_of<float2>(p, c);
+    else launch_history_of<uint32_t>(p, c);
+    HIPCHECK(hipGetLastError());
+    return SXFIR_OK;
+}
 // key: count the input samples [lo, hi) of channel 0 that reach the plan's keying threshold into *counter
 struct KeyedRange { unsigned long long *counter; long long lo, hi; };
 
@@ -126,25 +147,22 @@ static long long first_offset(const sxfir_plan *p)
     return ((p->consumed + D - 1) / D) * D - p->consumed;
 }
 
-// `aligned`: the output is 16-byte aligned with an even channel stride (what the tiled kernels' stores need)
-static LaunchGeom decim_geom(const sxfir_plan *p, long long n_out, long long first, bool aligned, bool aligned_multi)
+// `aligned`: stores_aligned() of the call
+static LaunchGeom decim_geom(const sxfir_plan *p, long long n_out, long long first, bool aligned)
 {
-    LaunchGeom g{GEOM_GENERIC, p->bands ? "chan_generic_kernel" : p->cx ? "decim_cx_generic_kernel" : "decim_generic_kernel", 256, (n_out + 255) / 256, (n_out + 255) / 256,
-                 (long long)p->compute_units * 8, 1, 1};
+    const bool chan = p->kind == KIND_CHANNELIZER;
+    LaunchGeom g{GEOM_GENERIC, chan ? "chan_generic_kernel" : p->kind == KIND_COMPLEX ? "decim_cx_generic_kernel" : "decim_generic_kernel", 256,
+                 (n_out + 255) / 256, (n_out + 255) / 256, (long long)p->compute_units * 8, 1, 1};
     const long long CU = p->compute_units;
     const bool want = p->kernel != SXFIR_KERNEL_GENERIC && first == 0;
-    if (p->chan_tiled && want && aligned) {
-        // channelizer (sxfir_create_channelizer): chan4_kernel for 4 bands x 128 taps on CF32, tiles of 512 outputs PER BAND on the wide
-        // kernel's frame; small calls dealt as fewer generations of waves, the complex-tap rule below
-        set_tiles(g, GEOM_CHAN4, "chan4_kernel", n_out, 512, CU * p->occ_chan);
+    if (p->ext_tiled && want && aligned) {
+        // complex taps: decim4_cx_kernel for /4 x 128 on CF32; channelizer: chan4_kernel for 4 bands x 128 taps on CF32, tiles of 512
+        // outputs PER BAND; the generic kernel of the kind for everything else.  Both on the wide kernel's frame: its sixteen
+        // generations of waves at the sizes they were measured at, fewer while that would leave a wave under four tiles
+        // (generations(): a small call is one strided pass of resident waves)
+        set_tiles(g, chan ? GEOM_CHAN4 : GEOM_CX, chan ? "chan4_kernel" : "decim4_cx_kernel", n_out, 512, CU * p->occ_ext);
         g.groups = clamp_groups(g.resident * generations(p, g.n_tiles, g.resident, true) / p->nchan, g.n_tiles);
-    } else if (p->cx_tiled && want && aligned) {
-        // complex taps (sxfir_create_complex): decim4_cx_kernel for /4 x 128 on CF32, the generic complex kernel for everything else.
-        // The wide kernel's sixteen generations of waves at the sizes they were measured at, fewer while that would leave a wave
-        // under four tiles (generations(): a small call is one strided pass of resident waves)
-        set_tiles(g, GEOM_CX, "decim4_cx_kernel", n_out, 512, CU * p->occ_cx);
-        g.groups = clamp_groups(g.resident * generations(p, g.n_tiles, g.resident, true) / p->nchan, g.n_tiles);
-    } else if (p->multi_capable && want && aligned_multi) {
+    } else if (p->multi_capable && want && aligned) {
         set_tiles(g, GEOM_MULTI, p->blocks ? "decim_blocks_kernel" : p->dense32 ? "decim_dense_kernel" : "decim_multi_kernel", n_out,
                   p->blocks ? 512 : p->multi_waves * 8 * (64 / (p->multi_ps * (p->ratio / 4))), CU * p->occ_multi);
         g.groups = clamp_groups(g.resident * generations(p, g.n_tiles, g.resident, p->dense32 && !p->dense_subset) / p->nchan, g.n_tiles);
@@ -167,13 +185,13 @@ static LaunchGeom decim_geom(const sxfir_plan *p, long long n_out, long long fir
 
 static LaunchGeom interp_geom(const sxfir_plan *p, long long n_in, bool aligned, bool keyed)
 {
-    if (p->syn_bands) {
+    if (p->kind == KIND_SYNTHESIZER) {
         // synthesizer (sxfir_create_synthesizer): synthesis4_kernel for 4 bands x 128 taps on CF32, tiles of 256 inputs PER BAND on the x4
         // pass kernel's frame; one thread per input index of synthesis_generic_kernel for everything else.  Small calls dealt as fewer
         // generations of waves, the channelizer's rule
         LaunchGeom s{GEOM_GENERIC, "synthesis_generic_kernel", 256, (n_in + 255) / 256, (n_in + 255) / 256, (long long)p->compute_units * 8, 1, 1};
-        if (p->syn_tiled && p->kernel != SXFIR_KERNEL_GENERIC && aligned) {
-            set_tiles(s, GEOM_SYN4, "synthesis4_kernel", n_in, 256, (long long)p->compute_units * p->occ_syn);
+        if (p->ext_tiled && p->kernel != SXFIR_KERNEL_GENERIC && aligned) {
+            set_tiles(s, GEOM_SYN4, "synthesis4_kernel", n_in, 256, (long long)p->compute_units * p->occ_ext);
             s.groups = clamp_groups(s.resident * generations(p, s.n_tiles, s.resident, true) / p->nchan, s.n_tiles);
         }
         return s;
@@ -319,7 +337,7 @@ static sxfir::SynGenericArgs syn_generic_args(const sxfir_plan *p, const CallIO 
 {
     sxfir::SynGenericArgs a{};
     a.g = generic_args(p, c, 0);
-    a.g.hist_len = p->hist_len / p->syn_bands;      // a band's history; hist_stride stays the channel's
+    a.g.hist_len = p->hist_len / p->bands;      // a band's history; hist_stride stays the channel's
     a.band_stride = (long long)c.band_stride;
     return a;
 }
@@ -351,19 +369,14 @@ static int launch_decim(sxfir_plan *p, const CallIO &c, bool *history_done)
 {
     *history_done = false;
     const long long first = first_offset(p);
-    // LDS-DMA sources need no 16-byte alignment (verified on MI355X, tools/probe_unaligned.hip): only the
-    // output, written with 16-byte stores, must be aligned
-    // (a channelizer's bands are stored like channels: an even band stride too)
-    const bool out16 = (uintptr_t)c.out % 16 == 0 && (!p->bands || c.band_stride % 2 == 0);
-    const LaunchGeom geom = decim_geom(p, c.n_out, first, out16 && (p->nchan == 1 || c.out_stride % 2 == 0),
-                                       out16 && (p->nchan == 1 || c.out_stride % (p->fmt == SXFIR_CF16 ? 4 : 2) == 0));
+    const LaunchGeom geom = decim_geom(p, c.n_out, first, stores_aligned(p, c));
     const dim3 grid((unsigned)geom.groups, (unsigned)p->nchan);
     if (geom.kind == GEOM_GENERIC) {
         if (p->kernel == SXFIR_KERNEL_TILED)
             return fail(SXFIR_EUNSUPPORTED,
                         "tiled kernel needs a 16-byte aligned output, an even output stride and a call that starts on "
                         "an output boundary");
-        if (p->bands) return launch(p->k.chan_generic, grid, 256, c.st, chan_generic_args(p, c, first));
+        if (p->kind == KIND_CHANNELIZER) return launch(p->k.chan_generic, grid, 256, c.st, chan_generic_args(p, c, first));
         return launch(p->k.generic, grid, 256, c.st, generic_args(p, c, first));
     }
     if (geom.n_tiles > 0x7fffffffLL) return fail(SXFIR_EINVAL, "call too large");
@@ -405,55 +418,11 @@ static int launch_decim(sxfir_plan *p, const CallIO &c, bool *history_done)
 
 extern "C" {
 
-static int check_io(const sxfir_plan *p, int mode, const void *in_dev, size_t n_in, size_t in_stride,
-                    const void *out_dev, size_t out_stride, long long n_out)
-{
-    if (!p) return fail(SXFIR_EINVAL, "plan is NULL");
-    if (p->syn_bands) return fail(SXFIR_EINVAL, "a synthesizer plan takes sxfir_synthesize (include/sxfir_synthesizer.h)");
-    if (p->mode != mode) return fail(SXFIR_EINVAL, "plan was created for the other direction");
-    if (p->bands) return fail(SXFIR_EINVAL, "a channelizer plan takes sxfir_channelize (include/sxfir_channelizer.h)");
-    if ((n_in && !in_dev) || (n_out > 0 && !out_dev)) return fail(SXFIR_EINVAL, "NULL device buffer");
-    if (p->nchan > 1 && (in_stride < n_in || out_stride < (size_t)n_out))
-        return fail(SXFIR_EINVAL, "channel stride smaller than the block");
-    if ((uintptr_t)in_dev % sample_bytes(p->fmt) || (uintptr_t)out_dev % sample_bytes(p->fmt))
-        return fail(SXFIR_EINVAL, "buffers must be aligned to one complex sample");
-    return SXFIR_OK;
-}
-
-int sxfir_decimate(sxfir_plan *p, const void *in_dev, size_t n_in, size_t in_stride, void *out_dev,
-                   size_t out_stride, size_t *n_out_p, void *stream)
-{
-    if (n_out_p) *n_out_p = 0;
-    if (!p) return fail(SXFIR_EINVAL, "plan is NULL");
-    const long long n_out = outputs_for(p, (long long)n_in);
-    int rc = check_io(p, SXFIR_DECIMATE, in_dev, n_in, in_stride, out_dev, out_stride, n_out);
-    if (rc) return rc;
-    if (n_in == 0) return SXFIR_OK;
-    HIPCHECK(hipSetDevice(p->device));
-    bool history_done = false;
-    if (n_out > 0) {
-        rc = launch_decim(p, CallIO{in_dev, n_in, in_stride, out_dev, out_stride, n_out, S(stream)}, &history_done);
-        // a (tile, block) launch that failed may have left arrival counters half way: the next launch starts from zero again
-        if (rc == SXFIR_EHIP && p->join_arrived)
-            (void)hipMemsetAsync(p->join_arrived, 0, sizeof(unsigned) * (size_t)p->join_tiles, S(stream));
-        if (rc) return rc;
-    }
-    if (!history_done) {
-        rc = launch_history(p, in_dev, n_in, in_stride, S(stream));
-        if (rc) return rc;
-    }
-    std::swap(p->hist_dev, p->hist_alt);
-    p->consumed += (long long)n_in;
-    p->produced += n_out;
-    if (n_out_p) *n_out_p = (size_t)n_out;
-    return SXFIR_OK;
-}
-
 // Launch only the interpolation kernel (no history swap, no position change).
-static int launch_interp(sxfir_plan *p, const CallIO &c, bool *history_done, const KeyedRange *key = nullptr, bool *key_pending = nullptr)
+static int launch_interp(sxfir_plan *p, const CallIO &c, bool *history_done, const KeyedRange *key, bool *key_pending)
 {
     *history_done = false;
-    const LaunchGeom geom = interp_geom(p, (long long)c.n_in, ((uintptr_t)c.out % 16 == 0) && (p->nchan == 1 || c.out_stride % 2 == 0), key != nullptr);
+    const LaunchGeom geom = interp_geom(p, (long long)c.n_in, stores_aligned(p, c), key != nullptr);
     const dim3 grid((unsigned)geom.groups, (unsigned)p->nchan);
     if (geom.kind == GEOM_GENERIC) {
         if (p->kernel == SXFIR_KERNEL_TILED)
@@ -472,13 +441,11 @@ static int launch_interp(sxfir_plan *p, const CallIO &c, bool *history_done, con
     return launch(p->k.interp[key != nullptr][geom.split > 1], grid, 64, c.st, t);
 }
 
-// Synthesizer plans (sxfir_synthesize): the kernel alone, as launch_interp.  The tiled kernel's LDS-DMA and edge loads need no more
-// than the sample alignment the entry point has checked (so an odd band or channel stride of the INPUT is its business too); its
-// 16-byte stores need an aligned output and, between channels, an even output stride.
+// Synthesizer plans (sxfir_synthesize): the kernel alone, as launch_interp.
 static int launch_synth(sxfir_plan *p, const CallIO &c, bool *history_done)
 {
     *history_done = false;
-    const LaunchGeom geom = interp_geom(p, (long long)c.n_in, ((uintptr_t)c.out % 16 == 0) && (p->nchan == 1 || c.out_stride % 2 == 0), false);
+    const LaunchGeom geom = interp_geom(p, (long long)c.n_in, stores_aligned(p, c), false);
     const dim3 grid((unsigned)geom.groups, (unsigned)p->nchan);
     if (geom.kind == GEOM_GENERIC) {
         if (p->kernel == SXFIR_KERNEL_TILED)
@@ -491,23 +458,8 @@ static int launch_synth(sxfir_plan *p, const CallIO &c, bool *history_done)
     return launch(p->k.syn4, grid, 64, c.st, syn_tile_args(p, c, geom));
 }
 
-// Generic path of a synthesizer plan: every band's history to the plan's other buffer.
-static int launch_synth_history(sxfir_plan *p, const CallIO &c)
-{
-    const int hb = p->hist_len / p->syn_bands;
-    const dim3 grid((unsigned)((hb + 255) / 256), (unsigned)p->nchan, (unsigned)p->syn_bands);
-    if (p->fmt != SXFIR_CF16)
-        hipLaunchKernelGGL(sxfir::synthesis_history_kernel<float2>, grid, dim3(256), 0, c.st, (float2 *)p->hist_alt, (const float2 *)p->hist_dev,
-                           (const float2 *)c.in, (long long)c.n_in, (long long)c.in_stride, (long long)c.band_stride, hb);
-    else
-        hipLaunchKernelGGL(sxfir::synthesis_history_kernel<uint32_t>, grid, dim3(256), 0, c.st, (uint32_t *)p->hist_alt, (const uint32_t *)p->hist_dev,
-                           (const uint32_t *)c.in, (long long)c.n_in, (long long)c.in_stride, (long long)c.band_stride, hb);
-    HIPCHECK(hipGetLastError());
-    return SXFIR_OK;
-}
-
 // Shapes the tiled kernels do not take: the keying count as a pass of its own (same rule, same counter).  Queued by
-// interpolate_impl AFTER the history launch has succeeded, with the position commit: a call that fails half way has not
+// stream_call AFTER the history launch has succeeded, with the position commit: a call that fails half way has not
 // touched the counter, so a caller that retries the block does not count it twice (on the tiled paths the count is part of
 // the one kernel launch).
 static int launch_keyed_count(sxfir_plan *p, const void *in_dev, const KeyedRange *key, hipStream_t st)
@@ -520,38 +472,84 @@ static int launch_keyed_count(sxfir_plan *p, const void *in_dev, const KeyedRang
     return SXFIR_OK;
 }
 
-static int interpolate_impl(sxfir_plan *p, const void *in_dev, size_t n_in, size_t in_stride, void *out_dev,
-                            size_t out_stride, size_t *n_out_p, void *stream, const KeyedRange *key)
+// The resampling kernel of a call alone (no history pass, no position change): what sxfir_time_* repeats
+static int launch_call(sxfir_plan *p, const CallIO &c, bool *history_done, const KeyedRange *key = nullptr, bool *key_pending = nullptr)
+{
+    if (p->kind == KIND_SYNTHESIZER) return launch_synth(p, c, history_done);
+    if (p->mode == SXFIR_DECIMATE) return launch_decim(p, c, history_done);
+    return launch_interp(p, c, history_done, key, key_pending);
+}
+
+// Everything behind an entry point's argument checks (which have set *n_out_p to 0).  A call that fails changes nothing: the
+// history buffers are swapped and the positions advanced once every launch is queued.
+static int stream_call(sxfir_plan *p, const CallIO &c, size_t *n_out_p, const KeyedRange *key = nullptr)
+{
+    if (c.n_in == 0) return SXFIR_OK;
+    HIPCHECK(hipSetDevice(p->device));
+    bool history_done = false, key_pending = false;
+    if (c.n_out > 0) {                  // (a decimator call that completes no output only carries its samples into the history)
+        const int rc = launch_call(p, c, &history_done, key, &key_pending);
+        // a (tile, block) launch that failed may have left arrival counters half way: the next launch starts from zero again
+        if (rc == SXFIR_EHIP && p->join_arrived)
+            (void)hipMemsetAsync(p->join_arrived, 0, sizeof(unsigned) * (size_t)p->join_tiles, c.st);
+        if (rc) return rc;
+    }
+    if (!history_done)
+        if (int rc = launch_history(p, c)) return rc;
+    if (key_pending)
+        if (int rc = launch_keyed_count(p, c.in, key, c.st)) return rc;
+    std::swap(p->hist_dev, p->hist_alt);
+    p->consumed += (long long)c.n_in;
+    p->produced += c.n_out;
+    if (n_out_p) *n_out_p = (size_t)c.n_out;
+    return SXFIR_OK;
+}
+
+// Two strides name a band plan's bands and channels (`side`: "in" / "out", the side that has bands): a channel's bands in a row,
+// channel after channel -- or a band's channels in a row, band after band
+static int check_band_layout(const sxfir_plan *p, const char *side, size_t chan_stride, size_t band_stride, size_t n)
+{
+    const size_t nb = (size_t)p->bands, nc = (size_t)p->nchan;
+    const bool bands_inside = chan_stride >= (nb - 1) * band_stride + n;
+    const bool channels_inside = chan_stride >= n && band_stride >= (nc - 1) * chan_stride + n;
+    if (nc == 1 || bands_inside || channels_inside) return SXFIR_OK;
+    return fail(SXFIR_EINVAL, "bands and channels overlap (%s_stride %zu, band_stride %zu, %zu %sputs per band)", side, chan_stride, band_stride, n, side);
+}
+
+// sxfir_decimate, sxfir_interpolate and sxfir_time_*: real and complex taps
+static int check_io(const sxfir_plan *p, int mode, const CallIO &c)
+{
+    if (p->kind == KIND_SYNTHESIZER) return fail(SXFIR_EINVAL, "a synthesizer plan takes sxfir_synthesize (include/sxfir_synthesizer.h)");
+    if (p->mode != mode) return fail(SXFIR_EINVAL, "plan was created for the other direction");
+    if (p->kind == KIND_CHANNELIZER) return fail(SXFIR_EINVAL, "a channelizer plan takes sxfir_channelize (include/sxfir_channelizer.h)");
+    if ((c.n_in && !c.in) || (c.n_out > 0 && !c.out)) return fail(SXFIR_EINVAL, "NULL device buffer");
+    if (p->nchan > 1 && (c.in_stride < c.n_in || c.out_stride < (size_t)c.n_out))
+        return fail(SXFIR_EINVAL, "channel stride smaller than the block");
+    if ((uintptr_t)c.in % sample_bytes(p->fmt) || (uintptr_t)c.out % sample_bytes(p->fmt))
+        return fail(SXFIR_EINVAL, "buffers must be aligned to one complex sample");
+    return SXFIR_OK;
+}
+
+static int resample(sxfir_plan *p, int mode, const void *in_dev, size_t n_in, size_t in_stride, void *out_dev, size_t out_stride,
+                    size_t *n_out_p, void *stream, const KeyedRange *key)
 {
     if (n_out_p) *n_out_p = 0;
     if (!p) return fail(SXFIR_EINVAL, "plan is NULL");
-    const long long n_out = outputs_for(p, (long long)n_in);
-    int rc = check_io(p, SXFIR_INTERPOLATE, in_dev, n_in, in_stride, out_dev, out_stride, n_out);
-    if (rc) return rc;
-    if (n_in == 0) return SXFIR_OK;
-    HIPCHECK(hipSetDevice(p->device));
-    bool history_done = false, key_pending = false;
-    rc = launch_interp(p, CallIO{in_dev, n_in, in_stride, out_dev, out_stride, n_out, S(stream)}, &history_done, key, &key_pending);
-    if (rc) return rc;
-    if (!history_done) {
-        rc = launch_history(p, in_dev, n_in, in_stride, S(stream));
-        if (rc) return rc;
-    }
-    if (key_pending) {
-        rc = launch_keyed_count(p, in_dev, key, S(stream));
-        if (rc) return rc;
-    }
-    std::swap(p->hist_dev, p->hist_alt);
-    p->consumed += (long long)n_in;
-    p->produced += n_out;
-    if (n_out_p) *n_out_p = (size_t)n_out;
-    return SXFIR_OK;
+    const CallIO c{in_dev, n_in, in_stride, out_dev, out_stride, outputs_for(p, (long long)n_in), S(stream)};
+    if (int rc = check_io(p, mode, c)) return rc;
+    return stream_call(p, c, n_out_p, key);
+}
+
+int sxfir_decimate(sxfir_plan *p, const void *in_dev, size_t n_in, size_t in_stride, void *out_dev,
+                   size_t out_stride, size_t *n_out_p, void *stream)
+{
+    return resample(p, SXFIR_DECIMATE, in_dev, n_in, in_stride, out_dev, out_stride, n_out_p, stream, nullptr);
 }
 
 int sxfir_interpolate(sxfir_plan *p, const void *in_dev, size_t n_in, size_t in_stride, void *out_dev,
                       size_t out_stride, size_t *n_out_p, void *stream)
 {
-    return interpolate_impl(p, in_dev, n_in, in_stride, out_dev, out_stride, n_out_p, stream, nullptr);
+    return resample(p, SXFIR_INTERPOLATE, in_dev, n_in, in_stride, out_dev, out_stride, n_out_p, stream, nullptr);
 }
 
 int sxfir_interpolate_keyed(sxfir_plan *p, const void *in_dev, size_t n_in, size_t in_stride, void *out_dev,
@@ -560,26 +558,26 @@ int sxfir_interpolate_keyed(sxfir_plan *p, const void *in_dev, size_t n_in, size
 {
     if (n_out_p) *n_out_p = 0;
     if (!p) return fail(SXFIR_EINVAL, "plan is NULL");
-    if (p->syn_bands) return fail(SXFIR_EINVAL, "a synthesizer plan takes sxfir_synthesize (include/sxfir_synthesizer.h): no keying count in its version 1");
+    if (p->kind == KIND_SYNTHESIZER) return fail(SXFIR_EINVAL, "a synthesizer plan takes sxfir_synthesize (include/sxfir_synthesizer.h): no keying count in its version 1");
     if (p->mode != SXFIR_INTERPOLATE) return fail(SXFIR_EINVAL, "not an interpolator plan");
     if (p->fmt == SXFIR_CF16) return fail(SXFIR_EUNSUPPORTED, "the keying count is defined on CF32 input");
     if (!counter || ((uintptr_t)counter & 7)) return fail(SXFIR_EINVAL, "counter must be an 8-byte aligned device word");
     if (key_first > n_in || key_count > n_in - key_first) return fail(SXFIR_EINVAL, "keying range outside the block");
     const KeyedRange key{counter, (long long)key_first, (long long)(key_first + key_count)};
-    return interpolate_impl(p, in_dev, n_in, in_stride, out_dev, out_stride, n_out_p, stream, key_count ? &key : nullptr);
+    return resample(p, SXFIR_INTERPOLATE, in_dev, n_in, in_stride, out_dev, out_stride, n_out_p, stream, key_count ? &key : nullptr);
 }
 
 int sxfir_launch_geometry(const sxfir_plan *p, size_t n_in, sxfir_geometry *out)
 {
     if (!p || !out) return fail(SXFIR_EINVAL, "NULL argument");
     memset(out, 0, sizeof(*out));
-    const LaunchGeom g = p->mode == SXFIR_DECIMATE ? decim_geom(p, outputs_for(p, (long long)n_in), first_offset(p), true, true)
+    const LaunchGeom g = p->mode == SXFIR_DECIMATE ? decim_geom(p, outputs_for(p, (long long)n_in), first_offset(p), true)
                                                    : interp_geom(p, (long long)n_in, true, false);
     snprintf(out->kernel, sizeof(out->kernel), "%s", g.kernel);
     out->tiled = g.kind != GEOM_GENERIC;
     out->split = g.split;
     out->tile_samples = g.tile_out * p->ratio;       // wideband samples: a decimator's inputs, an interpolator's outputs
-    if (g.kind == GEOM_GENERIC) out->tile_samples = p->mode == SXFIR_DECIMATE ? 256LL * p->ratio : (p->syn_bands ? 1024 : 256);
+    if (g.kind == GEOM_GENERIC) out->tile_samples = p->mode == SXFIR_DECIMATE ? 256LL * p->ratio : (p->kind == KIND_SYNTHESIZER ? 1024 : 256);
     out->n_tiles = g.n_tiles;
     out->workgroups = g.groups * p->nchan;
     out->resident = g.resident;

@@ -1,13 +1,19 @@
-// Plan bookkeeping of the C ABI (include/sxfir.h): what a plan holds, the kernel table (which instance a shape
-// launches: the one statement of it, for the occupancy queries and the launches), how sxfir_create settles a plan's
-// flags and lays out its tap tables, and the small state entry points (reset, history, position, contract).
+// Plan bookkeeping of the C ABI (include/sxfir.h): what a plan holds and which of the four kinds it is, the kernel table (which
+// instance a shape launches: the one statement of it, for the occupancy queries and the launches), the creation frame every
+// sxfir_create* goes through (argument checks, the device, the plan's common fields, the real-tap contract, the plan's device
+// memory and the one list of what to free), how sxfir_create settles a real-tap plan's flags and lays out its tap tables, and
+// the small state entry points (reset, history, position, contract).
 // Included by sxfir.hip after the kernel headers; not a stand-alone translation unit.
 #pragma once
 
+// What created the plan: sxfir_create, sxfir_create_complex (sxfir_complex.hip.h), sxfir_create_channelizer
+// (sxfir_channelizer.hip.h), sxfir_create_synthesizer (sxfir_synthesizer.hip.h).  A complex-tap plan is a decimator whose taps_dev
+// holds a[0, ntaps) then b[0, ntaps); the band kinds are a /bands decimator and a x bands interpolator in everything about the stream.
+enum PlanKind { KIND_REAL = 0, KIND_COMPLEX = 1, KIND_CHANNELIZER = 2, KIND_SYNTHESIZER = 3 };
 enum TapTable { TAPS_SCALED = 0, TAPS_SUBSET8 = 1, TAPS_PASS8 = 2, TAPS_BLOCKS16 = 3, TAPS_PHASE4 = 4 };
 
-// One typed kernel pointer per launch-argument family, and a plan's kernels: resolved once by sxfir_create /
-// sxfir_create_complex (resolve_kernels below), read by the occupancy queries there and by the launches (sxfir_launch.hip.h).
+// One typed kernel pointer per launch-argument family, and a plan's kernels: resolved once by the plan's creator
+// (resolve_kernels below), read by the occupancy queries there and by the launches (sxfir_launch.hip.h).
 typedef void (*GenericFn)(sxfir::GenericArgs);
 typedef void (*DecimMultiFn)(sxfir::DecimMultiArgs);
 typedef void (*DecimBlocksFn)(sxfir::DecimMultiArgs, sxfir::DecimBlocksJoin);
@@ -30,7 +36,10 @@ struct KernelTable {
 };
 
 struct sxfir_plan {
+    int kind;              // PlanKind
     int mode, ntaps, ratio, nchan, fmt, device;
+    int bands;             // the band kinds: 4 (= ratio); else 0.  A synthesizer's hist_dev holds bands x hist_len / bands samples per
+                           // channel, band k's at k * hist_len / bands
     int kernel;            // SXFIR_KERNEL_*
     int hist_len;          // samples of history kept per channel
     int blocks;            // /48, /96: sixteen-column blocks of decim_blocks_kernel (3, 6), else 0
@@ -92,16 +101,9 @@ struct sxfir_plan {
     bool ipass_wait0;         // (profiling) SXFIR_IPASS_WAIT0=1: its vmcnt(0) form (A/B partner of the counted wait)
     float taps_k[64];         // the first 64 taps (times 2^-31 for S32 plans) for kernels that take them by value
     bool symmetric;           // taps[k] == taps[ntaps-1-k] bit for bit (every linear-phase design)
-    bool cx;                  // complex taps (sxfir_create_complex, include/sxfir_complex.h): taps_dev holds a[0, ntaps) then b[0, ntaps)
-    bool cx_tiled;            // ... and the shape decim4_cx_kernel takes (/4, 128 taps, CF32)
-    int occ_cx;               // its resident waves per CU
-    int bands;                // channelizer plans (sxfir_create_channelizer, include/sxfir_channelizer.h): 4; every other plan: 0
-    bool chan_tiled;          // ... and the shape chan4_kernel takes (4 bands x 128 taps, CF32)
-    int occ_chan;             // its resident waves per CU
-    int syn_bands;            // synthesizer plans (sxfir_create_synthesizer, include/sxfir_synthesizer.h): 4; every other plan: 0.  hist_dev
-                              // holds 4 x hist_len / 4 samples per channel, band k's at k * hist_len / 4
-    bool syn_tiled;           // ... and the shape synthesis4_kernel takes (4 bands x 128 taps, CF32)
-    int occ_syn;              // its resident waves per CU
+    bool ext_tiled;           // the other kinds: the shape their tiled kernel takes (decim4_cx_kernel: /4, 128 taps, CF32; chan4_kernel and
+                              // synthesis4_kernel: 4 bands x 128 taps, CF32)
+    int occ_ext;              // its resident waves per CU
     void *hist_dev;        // current history: nchan * hist_len samples
     void *hist_alt;        // the tile kernel writes the next history here, then the two swap
     KernelTable k;         // the instances this plan launches (null: none in this build for that family)
@@ -243,23 +245,23 @@ static SynGenericFn synthesis_generic_kernel_for(int fmt)
     return synthesis_generic_kernel<CF32, S32>;
 }
 
-// The plan's kernels, from the capability flags sxfir_create has settled (the profiling knobs included)
+// The plan's kernels, from its kind and the capability flags its creator has settled (the profiling knobs included)
 static void resolve_kernels(sxfir_plan *p)
 {
     KernelTable &k = p->k;
     k = KernelTable{};
-    if (p->bands) {
+    if (p->kind == KIND_CHANNELIZER) {
         k.chan_generic = chan_generic_kernel_for(p->fmt);
-        if (p->chan_tiled) k.chan4 = sxfir::chan4_kernel;
+        if (p->ext_tiled) k.chan4 = sxfir::chan4_kernel;
         return;
     }
-    if (p->syn_bands) {
+    if (p->kind == KIND_SYNTHESIZER) {
         k.syn_generic = synthesis_generic_kernel_for(p->fmt);
-        if (p->syn_tiled) k.syn4 = sxfir::synthesis4_kernel;
+        if (p->ext_tiled) k.syn4 = sxfir::synthesis4_kernel;
         return;
     }
-    k.generic = generic_kernel(p->mode, p->fmt, p->cx);
-    if (p->cx_tiled) k.cx = sxfir::decim4_cx_kernel;
+    k.generic = generic_kernel(p->mode, p->fmt, p->kind == KIND_COMPLEX);
+    if (p->ext_tiled) k.cx = sxfir::decim4_cx_kernel;
     if (p->dense32) k.dense = dense_kernel(p->ratio, p->fmt);
     for (int split = 0; split < 2; ++split) k.blocks[split] = blocks_kernel(p->blocks, p->fmt, split != 0);
     if (p->tile_capable) k.tile = tile_kernel(p->ntaps, p->fmt);
@@ -275,6 +277,144 @@ static void query_occupancy(int *occ, Fn kernel, int threads, size_t dynamic_lds
 {
     int nb = 0;
     if (kernel && hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kernel, threads, dynamic_lds) == hipSuccess && nb > 0) *occ = nb;
+}
+
+// ---- The creation frame.  A creator is: check_create_args, its own refusals, new_plan, its own fields and tap layout,
+// resolve_kernels and the occupancy of its tiled kernel, plan_to_device.  Every argument error comes before the device is looked at.
+
+// `ratio_name`: what the caller calls it ("ratio", "nbands")
+static int check_create_args(sxfir_plan **out, const float *taps, int mode, int ntaps, const char *ratio_name, int ratio, int nchan, int fmt)
+{
+    if (!out || !taps) return fail(SXFIR_EINVAL, "NULL argument");
+    *out = nullptr;
+    if (mode != SXFIR_DECIMATE && mode != SXFIR_INTERPOLATE) return fail(SXFIR_EINVAL, "bad mode %d", mode);
+    if (ntaps < 1 || ntaps > 65536) return fail(SXFIR_EINVAL, "ntaps %d out of range", ntaps);
+    if (ratio < 1 || ratio > 4096) return fail(SXFIR_EINVAL, "%s %d out of range", ratio_name, ratio);
+    if (nchan < 1 || nchan > 65535) return fail(SXFIR_EINVAL, "nchan %d out of range", nchan);
+    if (fmt != SXFIR_CF32 && fmt != SXFIR_CF16 && fmt != SXFIR_S32) return fail(SXFIR_EINVAL, "bad format %d", fmt);
+    return SXFIR_OK;
+}
+
+// *device < 0: the current one.  Makes it current and hands back its properties; only gfx950 passes.
+static int open_device(int *device, hipDeviceProp_t *prop)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return fail(SXFIR_ENODEVICE, "no HIP device visible; this library has no CPU path");
+    if (*device < 0) HIPCHECK(hipGetDevice(device));
+    if (*device >= ndev) return fail(SXFIR_EINVAL, "device %d of %d", *device, ndev);
+    HIPCHECK(hipSetDevice(*device));
+    HIPCHECK(hipGetDeviceProperties(prop, *device));
+    if (strncmp(prop->gcnArchName, "gfx950", 6) != 0)
+        return fail(SXFIR_ENODEVICE, "device %d is %s; kernels are built for gfx950 only", *device, prop->gcnArchName);
+    return SXFIR_OK;
+}
+
+// A plan on `device` with what every kind sets; everything else is zero (value-initialised: no kernel family is enabled, no
+// pointer, counter or knob is set)
+static int new_plan(sxfir_plan **pp, int kind, int mode, int ntaps, int ratio, int nchan, int fmt, int device)
+{
+    hipDeviceProp_t prop;
+    if (int rc = open_device(&device, &prop)) return rc;
+    sxfir_plan *p = new (std::nothrow) sxfir_plan();
+    if (!p) return fail(SXFIR_ENOMEM, "out of host memory");
+    p->kind = kind;
+    p->mode = mode;
+    p->ntaps = ntaps;
+    p->ratio = ratio;
+    p->nchan = nchan;
+    p->fmt = fmt;
+    p->device = device;
+    p->bands = kind == KIND_CHANNELIZER || kind == KIND_SYNTHESIZER ? ratio : 0;
+    p->kernel = SXFIR_KERNEL_AUTO;
+    p->compute_units = prop.multiProcessorCount;
+    p->thr2 = 1.0e-3f * 1.0e-3f;
+    p->oversub = 16;
+    p->occ_ext = 8;
+#ifdef SXFIR_PROFILING
+    p->join_drop = -1;
+#endif
+    *pp = p;
+    return SXFIR_OK;
+}
+
+// The numeric contract of a real-tap plan of (mode, ntaps, ratio).  Decimators: two row halves and column groups of 4
+// when the shape allows the adjacent-pair trees, i.e. whole, even rows and a power-of-two number (<= 32) of column groups;
+// otherwise one chain over all taps.  /48 and /96 with 32 taps per phase (the reference's rates master clock / 768 and / 1536,
+// SoapySX.cpp:180-208) run decim_blocks_kernel, sixteen-column blocks of whole input lines under the ROTATED contract (slot k'
+// holds tap (k' + 1) mod ntaps: sxfir_contract_rotation); 12 / 24 column groups meet in the adjacent-pair tree whose odd element
+// at the end of a level moves up unchanged (oracle B and the generic kernel state the same tree and rotation).  Interpolators:
+// a phase's taps in two halves when their count is even.
+static void real_tap_contract(sxfir_plan *p)
+{
+    const int ntaps = p->ntaps, ratio = p->ratio;
+    p->rot = 0;
+    if (p->mode == SXFIR_INTERPOLATE) {
+        p->jsplit = ((ntaps / ratio) % 2 == 0) ? 2 : 1;
+        p->cw = 1;
+        return;
+    }
+    const int jt = (ntaps + ratio - 1) / ratio;
+    const int ncol4 = ratio / 4;
+    const bool pow2_cols = ratio % 4 == 0 && (ncol4 & (ncol4 - 1)) == 0 && ncol4 <= 32;
+    const bool blocks = ntaps == 32 * ratio && (ratio == 48 || ratio == 96);
+    p->rot = blocks ? 1 : 0;
+    if (ntaps % ratio == 0 && (pow2_cols || blocks) && jt % 2 == 0) {
+        p->jsplit = 2;
+        p->cw = 4;
+    } else {
+        p->jsplit = 1;
+        p->cw = ratio;
+    }
+}
+
+// The one list of what a plan owns
+static void free_plan(sxfir_plan *p)
+{
+    (void)hipFree(p->taps_dev);
+    (void)hipFree(p->taps_scaled_dev);
+    (void)hipFree(p->hist_dev);
+    (void)hipFree(p->hist_alt);
+    (void)hipFree(p->join_partials);
+    (void)hipFree(p->join_arrived);
+#ifdef SXFIR_PROFILING
+    (void)hipFree(p->join_shadow);
+#endif
+    (void)hipFree(p->stamps_dev);          // the profiling build's clock stamps; null in the product
+    delete p;
+}
+
+static hipError_t upload(float **dev, const float *host, size_t n)
+{
+    const hipError_t e = hipMalloc((void **)dev, sizeof(float) * n);
+    return e != hipSuccess ? e : hipMemcpy(*dev, host, sizeof(float) * n, hipMemcpyHostToDevice);
+}
+
+// The plan's device memory: the tap table (`taps`: ntaps floats; `second`: p->ntaps floats for taps_scaled_dev too, in the layout
+// p->tap_table names), the two history buffers, the current one zeroed, and for /48 and /96 the join scratch.  The last step of
+// every creator: *out is the plan, or the plan is freed.
+static int plan_to_device(sxfir_plan **out, sxfir_plan *p, const float *taps, size_t ntaps, const float *second)
+{
+    const size_t hist_bytes = sample_bytes(p->fmt) * (size_t)p->hist_len * (size_t)p->nchan;
+    hipError_t e = upload(&p->taps_dev, taps, ntaps);
+    if (e == hipSuccess && second) e = upload(&p->taps_scaled_dev, second, (size_t)p->ntaps);
+    if (e == hipSuccess) e = hipMalloc(&p->hist_dev, hist_bytes);
+    if (e == hipSuccess) e = hipMalloc(&p->hist_alt, hist_bytes);
+    if (e == hipSuccess) e = hipMemset(p->hist_dev, 0, hist_bytes);
+    if (e == hipSuccess && p->blocks) {
+        e = hipMalloc(&p->join_partials, (size_t)p->join_tiles * (size_t)p->blocks * 4096);
+        if (e == hipSuccess) e = hipMalloc((void **)&p->join_arrived, sizeof(unsigned) * (size_t)p->join_tiles);
+        if (e == hipSuccess) e = hipMemset(p->join_arrived, 0, sizeof(unsigned) * (size_t)p->join_tiles);
+#ifdef SXFIR_PROFILING
+        if (e == hipSuccess && p->join_drop >= 0) e = hipMalloc(&p->join_shadow, (size_t)p->join_tiles * 4096);
+#endif
+    }
+    if (e != hipSuccess) {
+        free_plan(p);
+        return fail(SXFIR_EHIP, "plan allocation failed: %s", hipGetErrorString(e));
+    }
+    *out = p;
+    return SXFIR_OK;
 }
 
 extern "C" {
@@ -325,48 +465,19 @@ int sxfir_device_pci_bus_id(int device, char *bdf, size_t bdf_bytes)
 int sxfir_create(sxfir_plan **out, int mode, const float *taps, int ntaps, int ratio, int nchan, int fmt,
                  int device)
 {
-    if (!out || !taps) return fail(SXFIR_EINVAL, "NULL argument");
-    *out = nullptr;
-    if (mode != SXFIR_DECIMATE && mode != SXFIR_INTERPOLATE) return fail(SXFIR_EINVAL, "bad mode %d", mode);
-    if (ntaps < 1 || ntaps > 65536) return fail(SXFIR_EINVAL, "ntaps %d out of range", ntaps);
-    if (ratio < 1 || ratio > 4096) return fail(SXFIR_EINVAL, "ratio %d out of range", ratio);
-    if (nchan < 1 || nchan > 65535) return fail(SXFIR_EINVAL, "nchan %d out of range", nchan);
-    if (fmt != SXFIR_CF32 && fmt != SXFIR_CF16 && fmt != SXFIR_S32) return fail(SXFIR_EINVAL, "bad format %d", fmt);
+    if (int rc = check_create_args(out, taps, mode, ntaps, "ratio", ratio, nchan, fmt)) return rc;
     if (mode == SXFIR_INTERPOLATE && ntaps % ratio)
         return fail(SXFIR_EINVAL, "interpolator needs ntaps %% ratio == 0 (%d, %d)", ntaps, ratio);
-
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return fail(SXFIR_ENODEVICE, "no HIP device visible; this library has no CPU path");
-    if (device < 0) HIPCHECK(hipGetDevice(&device));
-    if (device >= ndev) return fail(SXFIR_EINVAL, "device %d of %d", device, ndev);
-    HIPCHECK(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    HIPCHECK(hipGetDeviceProperties(&prop, device));
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(SXFIR_ENODEVICE, "device %d is %s; kernels are built for gfx950 only", device,
-                    prop.gcnArchName);
-
-    sxfir_plan *p = new (std::nothrow) sxfir_plan();       // value-initialised: every flag, pointer, counter and knob starts at zero
-    if (!p) return fail(SXFIR_ENOMEM, "out of host memory");
-    p->mode = mode;
-    p->ntaps = ntaps;
-    p->ratio = ratio;
-    p->nchan = nchan;
-    p->fmt = fmt;
-    p->device = device;
-    p->kernel = SXFIR_KERNEL_AUTO;
-    p->compute_units = prop.multiProcessorCount;
+    sxfir_plan *p = nullptr;
+    if (int rc = new_plan(&p, KIND_REAL, mode, ntaps, ratio, nchan, fmt, device)) return rc;
     p->occ_ipass = 16;
     p->ipass_qi = 2;
     p->symmetric = true;
     for (int k = 0; k < ntaps / 2; ++k)
         if (memcmp(&taps[k], &taps[ntaps - 1 - k], sizeof(float)) != 0) p->symmetric = false;
     p->blocks_split = true;
-#ifdef SXFIR_PROFILING
-    p->join_drop = -1;
-#endif
     p->ipass_split = true;
+    real_tap_contract(p);
 
     if (mode == SXFIR_DECIMATE) {
         p->hist_len = (ntaps + 1) & ~1;
@@ -378,59 +489,32 @@ int sxfir_create(sxfir_plan **out, int mode, const float *taps, int ntaps, int r
         p->multi_capable = (ntaps == 32 * ratio) && !half4_wide &&
                            (((fmt == SXFIR_CF32 || fmt == SXFIR_S32) && (ratio == 8 || ratio == 16 || ratio == 32)) ||
                             (fmt == SXFIR_CF16 && (ratio == 4 || ratio == 8 || ratio == 16 || ratio == 32)));
-        // Numeric contract: two row halves and column groups of 4 when the shape allows the
-        // adjacent-pair trees, i.e. whole, even rows and a power-of-two number (<= 32) of column groups;
-        // otherwise one chain over all taps.
-        const int jt = (ntaps + ratio - 1) / ratio;
-        const int ncol4 = ratio / 4;
-        const bool pow2_cols = ratio % 4 == 0 && (ncol4 & (ncol4 - 1)) == 0 && ncol4 <= 32;
-        // /48 and /96 with 32 taps per phase (the reference's rates master clock / 768 and / 1536, SoapySX.cpp:180-208):
-        // decim_blocks_kernel, sixteen-column blocks of whole input lines under the ROTATED contract (slot k' holds tap
-        // (k' + 1) mod ntaps: sxfir_contract_rotation); 12 / 24 column groups meet in the adjacent-pair tree whose odd element
-        // at the end of a level moves up unchanged (oracle B and the generic kernel state the same tree and rotation)
-        p->blocks = (ntaps == 32 * ratio && (ratio == 48 || ratio == 96)) ? ratio / 16 : 0;      // CF32, S32 words, CF16 storage
+        // /48 and /96 with 32 taps per phase (the rotated contract): decim_blocks_kernel on CF32, S32 words and CF16 storage
+        p->blocks = p->rot ? ratio / 16 : 0;
 #ifdef SXFIR_PROFILING
         // experiment (round 6): /16 and /32 CF32 through the sixteen-column-block form too (one / two blocks per row, scalar taps,
-        // the ROTATED contract): would config 5's shape gain what /48 and /96 gained over the VGPR-tap dense kernel?
+        // the ROTATED contract, or with SXFIR_BLOCKS_SMALL=2 the unrotated one): would config 5's shape gain what /48 and /96
+        // gained over the VGPR-tap dense kernel?
         if (getenv("SXFIR_BLOCKS_SMALL") && atoi(getenv("SXFIR_BLOCKS_SMALL")) && fmt == SXFIR_CF32 && ntaps == 32 * ratio &&
             (ratio == 16 || ratio == 32)) {
             p->blocks = ratio / 16;
             p->blocks_split = false;
+            p->rot = atoi(getenv("SXFIR_BLOCKS_SMALL")) == 2 ? 0 : 1;
         }
 #endif
-        if (p->blocks) {
-            p->multi_capable = true;
-            p->rot = 1;
-#ifdef SXFIR_PROFILING
-            if (p->blocks < 3 && atoi(getenv("SXFIR_BLOCKS_SMALL")) == 2) p->rot = 0;      // ... under the unrotated contract
-#endif
-        }
-        if (ntaps % ratio == 0 && (pow2_cols || p->blocks) && jt % 2 == 0) {
-            p->jsplit = 2;
-            p->cw = 4;
-        } else {
-            p->jsplit = 1;
-            p->cw = ratio;
-        }
+        if (p->blocks) p->multi_capable = true;
     } else {
-        const int jt = ntaps / ratio;
-        p->hist_len = (jt + 1) & ~1;
-        p->tile_capable = false;
-        p->multi_capable = false;
+        p->hist_len = (ntaps / ratio + 1) & ~1;
         // (x48, x96 -- the reference's rates master clock / 768 and / 1536 -- as three / six phase blocks of the x16 kernel)
         // (CF16 storage, round 5: interp_tile_kernel<.., HALF> at every one of these ratios)
         p->itile_capable = ((fmt == SXFIR_CF32 || fmt == SXFIR_S32 || fmt == SXFIR_CF16) && ntaps == 32 * ratio &&
                             (ratio == 4 || ratio == 8 || ratio == 16 || ratio == 32 || ratio == 48 || ratio == 96));
-        p->jsplit = (jt % 2 == 0) ? 2 : 1;
-        p->cw = 1;
     }
 
     // measured on MI355X (tools/kbench.py): single-buffered LDS-DMA at 16 waves/CU, 16 generations
     // of short-lived waves (4 tiles each at 2^28 samples), strided XCD-blocked passes; the
     // double-buffered variant at 8 waves/CU and long contiguous runs are slower
     p->occ_sb = p->occ_db = 8;
-    p->oversub = 16;
-    p->thr2 = 1.0e-3f * 1.0e-3f;
     // waves per workgroup of the multi-column kernel, measured (tools/kbench.py, KB_D, specs "w1".."w8"):
     // the choice that brings the LDS image down to 10 KiB per wave (16 waves per CU) while the 31-row
     // halo stays a small part of the staging
@@ -520,7 +604,7 @@ int sxfir_create(sxfir_plan **out, int mode, const float *taps, int ntaps, int r
         }
 #endif
         if (!k) {
-            delete p;
+            free_plan(p);
             return fail(SXFIR_EUNSUPPORTED, "no multi-column kernel for ratio %d with %d waves per workgroup", ratio, W);
         }
         query_occupancy(&p->occ_multi, k, 64 * W);
@@ -616,7 +700,7 @@ int sxfir_create(sxfir_plan **out, int mode, const float *taps, int ntaps, int r
 #undef SXFIR_X
                     }
                     if (!k || ((opt & sxfir::T2_SCALAR) && !p->symmetric)) {
-                        delete p;
+                        free_plan(p);
                         return fail(SXFIR_EUNSUPPORTED, "no tile2 variant %d:%d for these taps", wpg, opt);
                     }
                     p->t2_wpg = wpg;
@@ -637,90 +721,48 @@ int sxfir_create(sxfir_plan **out, int mode, const float *taps, int ntaps, int r
 #endif
     }
 
-    hipError_t e = hipMalloc((void **)&p->taps_dev, sizeof(float) * (size_t)ntaps);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->taps_scaled_dev, sizeof(float) * (size_t)ntaps);
-
+    std::vector<float> scaled(taps, taps + ntaps);
     for (int k = 0; k < 64; ++k) p->taps_k[k] = k < ntaps ? (fmt == SXFIR_S32 ? taps[k] * 4.656612873077393e-10f : taps[k]) : 0.0f;
-    if (e == hipSuccess) {
-        std::vector<float> scaled(taps, taps + ntaps);
-        // the layout follows the kernel the plan will launch (the same flags launch_decim / launch_interp branch on),
-        // not the shape: a plan whose /8 scalar-tap form was switched off (profiling knobs) keeps the plain table
-        p->tap_table = p->blocks ? TAPS_BLOCKS16 : p->dense_subset ? TAPS_SUBSET8 : (mode == SXFIR_INTERPOLATE && p->ipass) ? TAPS_PASS8 : TAPS_SCALED;
-        if (p->tap_table == TAPS_SUBSET8) {
-            // /8 scalar-tap form (decim_dense_kernel<8, ..., SUBSET>): subset s = 2c + p at 64 s, (jj, rr) at 4 jj + rr
-            for (int c = 0; c < 2; ++c)
+    // the layout follows the kernel the plan will launch (the same flags launch_decim / launch_interp branch on),
+    // not the shape: a plan whose /8 scalar-tap form was switched off (profiling knobs) keeps the plain table
+    p->tap_table = p->blocks ? TAPS_BLOCKS16 : p->dense_subset ? TAPS_SUBSET8 : (mode == SXFIR_INTERPOLATE && p->ipass) ? TAPS_PASS8 : TAPS_SCALED;
+    if (p->tap_table == TAPS_SUBSET8) {
+        // /8 scalar-tap form (decim_dense_kernel<8, ..., SUBSET>): subset s = 2c + p at 64 s, (jj, rr) at 4 jj + rr
+        for (int c = 0; c < 2; ++c)
+            for (int ph = 0; ph < 2; ++ph)
+                for (int jj = 0; jj < 16; ++jj)
+                    for (int rr = 0; rr < 4; ++rr)
+                        scaled[(size_t)(64 * (2 * c + ph) + 4 * jj + rr)] =
+                            taps[8 * (16 * ph + jj) + 4 * c + rr] * (fmt == SXFIR_S32 ? 4.656612873077393e-10f : 1.0f);   // 2^-31: exact
+    } else if (p->tap_table == TAPS_BLOCKS16) {
+        // decim_blocks_kernel: the ROTATED taps (slot k' holds tap (k' + 1) mod ntaps); block b (columns 16 b .. 16 b + 15)
+        // at 512 b, subset s = 2c + p at 64 s inside it, (jj, rr) at 4 jj + rr
+        for (int b = 0; b < p->blocks; ++b)
+            for (int c = 0; c < 4; ++c)
                 for (int ph = 0; ph < 2; ++ph)
                     for (int jj = 0; jj < 16; ++jj)
-                        for (int rr = 0; rr < 4; ++rr)
-                            scaled[(size_t)(64 * (2 * c + ph) + 4 * jj + rr)] =
-                                taps[8 * (16 * ph + jj) + 4 * c + rr] * (fmt == SXFIR_S32 ? 4.656612873077393e-10f : 1.0f);   // 2^-31: exact
-        } else if (p->tap_table == TAPS_BLOCKS16) {
-            // decim_blocks_kernel: the ROTATED taps (slot k' holds tap (k' + 1) mod ntaps); block b (columns 16 b .. 16 b + 15)
-            // at 512 b, subset s = 2c + p at 64 s inside it, (jj, rr) at 4 jj + rr
-            for (int b = 0; b < p->blocks; ++b)
-                for (int c = 0; c < 4; ++c)
-                    for (int ph = 0; ph < 2; ++ph)
-                        for (int jj = 0; jj < 16; ++jj)
-                            for (int rr = 0; rr < 4; ++rr) {
-                                const int slot = ratio * (16 * ph + jj) + 16 * b + 4 * c + rr;
-                                scaled[(size_t)(512 * b + 64 * (2 * c + ph) + 4 * jj + rr)] =
-                                    taps[(slot + p->rot) % ntaps] * (fmt == SXFIR_S32 ? 4.656612873077393e-10f : 1.0f);
-                            }
-        } else if (p->tap_table == TAPS_PASS8) {
-            const int ll = ratio >= 16 ? 16 : ratio;            // phases per (block of the) pass kernel
-            for (int b = 0; b < ratio / ll; ++b)
-            for (int c = 0; c < ll / 4; ++c)                    // x8: two phase groups; x4: one; x16 blocks: four
-                for (int ph = 0; ph < 2; ++ph)
-                    for (int jj = 0; jj < 16; ++jj)
-                        for (int rr = 0; rr < 4; ++rr)
-                            scaled[(size_t)(32 * ll * b + 64 * (2 * c + ph) + 4 * jj + rr)] = taps[(16 * ph + jj) * ratio + ll * b + 4 * c + rr];
-        } else {
-            for (float &t : scaled) t *= 4.656612873077393e-10f;      // 2^-31: exact
-        }
-        e = hipMemcpy(p->taps_scaled_dev, scaled.data(), sizeof(float) * (size_t)ntaps, hipMemcpyHostToDevice);
+                        for (int rr = 0; rr < 4; ++rr) {
+                            const int slot = ratio * (16 * ph + jj) + 16 * b + 4 * c + rr;
+                            scaled[(size_t)(512 * b + 64 * (2 * c + ph) + 4 * jj + rr)] =
+                                taps[(slot + p->rot) % ntaps] * (fmt == SXFIR_S32 ? 4.656612873077393e-10f : 1.0f);
+                        }
+    } else if (p->tap_table == TAPS_PASS8) {
+        const int ll = ratio >= 16 ? 16 : ratio;            // phases per (block of the) pass kernel
+        for (int b = 0; b < ratio / ll; ++b)
+        for (int c = 0; c < ll / 4; ++c)                    // x8: two phase groups; x4: one; x16 blocks: four
+            for (int ph = 0; ph < 2; ++ph)
+                for (int jj = 0; jj < 16; ++jj)
+                    for (int rr = 0; rr < 4; ++rr)
+                        scaled[(size_t)(32 * ll * b + 64 * (2 * c + ph) + 4 * jj + rr)] = taps[(16 * ph + jj) * ratio + ll * b + 4 * c + rr];
+    } else {
+        for (float &t : scaled) t *= 4.656612873077393e-10f;      // 2^-31: exact
     }
-    if (e == hipSuccess && p->blocks) {
-        e = hipMalloc(&p->join_partials, (size_t)p->join_tiles * (size_t)p->blocks * 4096);
-        if (e == hipSuccess) e = hipMalloc((void **)&p->join_arrived, sizeof(unsigned) * (size_t)p->join_tiles);
-        if (e == hipSuccess) e = hipMemset(p->join_arrived, 0, sizeof(unsigned) * (size_t)p->join_tiles);
-#ifdef SXFIR_PROFILING
-        if (e == hipSuccess && p->join_drop >= 0) e = hipMalloc(&p->join_shadow, (size_t)p->join_tiles * 4096);
-#endif
-    }
-    if (e == hipSuccess) e = hipMalloc(&p->hist_dev, sample_bytes(fmt) * (size_t)p->hist_len * (size_t)nchan);
-    if (e == hipSuccess) e = hipMalloc(&p->hist_alt, sample_bytes(fmt) * (size_t)p->hist_len * (size_t)nchan);
-    if (e == hipSuccess) e = hipMemcpy(p->taps_dev, taps, sizeof(float) * (size_t)ntaps, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(p->hist_dev, 0, sample_bytes(fmt) * (size_t)p->hist_len * (size_t)nchan);
-    if (e != hipSuccess) {
-        if (p->taps_dev) (void)hipFree(p->taps_dev);
-        if (p->taps_scaled_dev) (void)hipFree(p->taps_scaled_dev);
-        if (p->hist_dev) (void)hipFree(p->hist_dev);
-        if (p->hist_alt) (void)hipFree(p->hist_alt);
-        if (p->join_partials) (void)hipFree(p->join_partials);
-        if (p->join_arrived) (void)hipFree(p->join_arrived);
-#ifdef SXFIR_PROFILING
-        if (p->join_shadow) (void)hipFree(p->join_shadow);
-#endif
-        delete p;
-        return fail(SXFIR_EHIP, "plan allocation failed: %s", hipGetErrorString(e));
-    }
-    *out = p;
-    return SXFIR_OK;
+    return plan_to_device(out, p, taps, (size_t)ntaps, scaled.data());
 }
 
 int sxfir_destroy(sxfir_plan *p)
 {
-    if (!p) return SXFIR_OK;
-    (void)hipFree(p->taps_dev);
-    (void)hipFree(p->taps_scaled_dev);
-    (void)hipFree(p->hist_dev);
-    (void)hipFree(p->hist_alt);
-    if (p->join_partials) (void)hipFree(p->join_partials);
-    if (p->join_arrived) (void)hipFree(p->join_arrived);
-#ifdef SXFIR_PROFILING
-    if (p->join_shadow) (void)hipFree(p->join_shadow);
-#endif
-    delete p;
+    if (p) free_plan(p);
     return SXFIR_OK;
 }
 
@@ -739,7 +781,7 @@ int sxfir_reset(sxfir_plan *p, void *stream)
 int sxfir_set_history(sxfir_plan *p, const void *src_dev, size_t n, size_t stride, void *stream)
 {
     if (!p || !src_dev) return fail(SXFIR_EINVAL, "NULL argument");
-    if (p->syn_bands)
+    if (p->kind == KIND_SYNTHESIZER)
         return fail(SXFIR_EUNSUPPORTED, "sxfir_set_history has one stride: it cannot name the bands and the channels of a synthesizer plan's input");
     if (n < (size_t)p->hist_len) return fail(SXFIR_EINVAL, "history needs %d samples per channel, %zu given", p->hist_len, n);
     if (p->nchan > 1 && stride < n) return fail(SXFIR_EINVAL, "channel stride %zu shorter than the block (%zu)", stride, n);
@@ -765,7 +807,7 @@ int sxfir_set_kernel(sxfir_plan *p, int kernel)
 {
     if (!p) return fail(SXFIR_EINVAL, "plan is NULL");
     if (kernel < SXFIR_KERNEL_AUTO || kernel > SXFIR_KERNEL_GENERIC) return fail(SXFIR_EINVAL, "bad kernel id");
-    if (kernel == SXFIR_KERNEL_TILED && !p->tile_capable && !p->multi_capable && !p->itile_capable && !p->cx_tiled && !p->chan_tiled && !p->syn_tiled)
+    if (kernel == SXFIR_KERNEL_TILED && !p->tile_capable && !p->multi_capable && !p->itile_capable && !p->ext_tiled)
         return fail(SXFIR_EUNSUPPORTED, "no tiled kernel for ntaps=%d ratio=%d fmt=%d mode=%d", p->ntaps,
                     p->ratio, p->fmt, p->mode);
     p->kernel = kernel;

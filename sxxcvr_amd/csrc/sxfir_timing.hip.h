@@ -1,5 +1,5 @@
-// Measurement entry points of the C ABI: back-to-back timed passes of a plan's kernel (HIP events on the launch
-// stream; bench.py's kernel_ms) and the in-kernel shader-clock probe.  Included by sxfir.hip after sxfir_launch.hip.h.
+// Measurement entry points of the C ABI: back-to-back timed passes of a plan's kernel (launch_call of the call frame between HIP
+// events on the launch stream; bench.py's kernel_ms) and the in-kernel shader-clock probe.  Included by sxfir.hip after sxfir_launch.hip.h.
 #pragma once
 
 extern "C" {
@@ -10,10 +10,10 @@ static int time_passes(sxfir_plan *p, int mode, const void *in_dev, size_t n_in,
                        size_t out_stride, int iters, void *stream, float *ms_per_pass)
 {
     if (!p || !ms_per_pass || iters < 1) return fail(SXFIR_EINVAL, "bad argument");
-    const long long n_out = outputs_for(p, (long long)n_in);
-    int rc = check_io(p, mode, in_dev, n_in, in_stride, out_dev, out_stride, n_out);
+    const CallIO c{in_dev, n_in, in_stride, out_dev, out_stride, outputs_for(p, (long long)n_in), S(stream)};
+    int rc = check_io(p, mode, c);
     if (rc) return rc;
-    if (n_out < 1) return fail(SXFIR_EINVAL, "nothing to do");
+    if (c.n_out < 1) return fail(SXFIR_EINVAL, "nothing to do");
     HIPCHECK(hipSetDevice(p->device));
     hipEvent_t e0, e1;
     HIPCHECK(hipEventCreate(&e0));
@@ -21,8 +21,7 @@ static int time_passes(sxfir_plan *p, int mode, const void *in_dev, size_t n_in,
     HIPCHECK(hipEventRecord(e0, S(stream)));
     for (int i = 0; i < iters; ++i) {
         bool history_done = false;   // history buffers are not swapped: every pass filters from the same state
-        const CallIO c{in_dev, n_in, in_stride, out_dev, out_stride, n_out, S(stream)};
-        rc = mode == SXFIR_DECIMATE ? launch_decim(p, c, &history_done) : launch_interp(p, c, &history_done);
+        rc = launch_call(p, c, &history_done);
         if (rc) break;
     }
     hipError_t e = hipEventRecord(e1, S(stream));

@@ -34,6 +34,61 @@ def to_cpu(t):
     return t.cpu().numpy()
 
 
+# ---- the band plans' references (tests/test_gpu_channelizer.py, test_gpu_synthesizer.py, test_gpu_call_frame.py) -------------
+def chan_ref(oracle, h, x, threads=None):
+    """[4, n_out] complex64: the four bands of one channelizer pass over x from zero history."""
+    h = np.ascontiguousarray(h, dtype=np.float32)
+    u = []
+    for r in range(4):
+        hr = np.zeros_like(h)                               # +0.0
+        hr[r::4] = h[r::4]
+        u.append(oracle.decim_f32(hr, 4, x, 1, 1, threads=threads))
+    f = np.float32
+    s0re, s0im, s1re, s1im = u[0].real + u[2].real, u[0].imag + u[2].imag, u[0].real - u[2].real, u[0].imag - u[2].imag
+    t0re, t0im, t1re, t1im = u[1].real + u[3].real, u[1].imag + u[3].imag, u[1].real - u[3].real, u[1].imag - u[3].imag
+    assert s0re.dtype == f and t1im.dtype == f
+    y = np.empty((4, u[0].size), dtype=np.complex64)
+    y[0].real, y[0].imag = s0re + t0re, s0im + t0im
+    y[1].real, y[1].imag = s1re - t1im, s1im + t1re
+    y[2].real, y[2].imag = s0re - t0re, s0im - t0im
+    y[3].real, y[3].imag = s1re + t1im, s1im - t1re
+    return y
+
+
+def assert_bands(got, ref, what):
+    assert got.shape == ref.shape, (what, got.shape, ref.shape)
+    for k in range(4):
+        assert_bit_exact(got[k], ref[k], "%s, band %d" % (what, k))
+
+
+def butterflies_f32(x):
+    """[4, n] complex64 -> the four streams v_r of the synthesizer, float32 arithmetic."""
+    f = np.float32
+    re = [np.ascontiguousarray(x[k].real) for k in range(4)]
+    im = [np.ascontiguousarray(x[k].imag) for k in range(4)]
+    a0re, a0im, a1re, a1im = re[0] + re[2], im[0] + im[2], re[0] - re[2], im[0] - im[2]
+    b0re, b0im, b1re, b1im = re[1] + re[3], im[1] + im[3], re[1] - re[3], im[1] - im[3]
+    assert a0re.dtype == f and b1im.dtype == f
+    v = np.empty((4, x.shape[1]), dtype=np.complex64)
+    v[0].real, v[0].imag = a0re + b0re, a0im + b0im
+    v[1].real, v[1].imag = a1re - b1im, a1im + b1re
+    v[2].real, v[2].imag = a0re - b0re, a0im - b0im
+    v[3].real, v[3].imag = a1re + b1im, a1im - b1re
+    return v
+
+
+def syn_ref(oracle, h, x, jsplit, threads=None):
+    """[4 n] complex64: one synthesizer pass over the four bands x [4, n] from zero history."""
+    h = np.ascontiguousarray(h, dtype=np.float32)
+    x = np.ascontiguousarray(x, dtype=np.complex64)
+    v = butterflies_f32(x)
+    w = np.empty(4 * x.shape[1], dtype=np.complex64)
+    for r in range(4):
+        y = oracle.interp_f32(h, 4, v[r], jsplit) if threads is None else oracle.interp_f32_mt(h, 4, v[r], jsplit, threads=threads)
+        w[r::4] = y[r::4]
+    return w
+
+
 # ---- the (tile, block) join of the decimators by 48 and 96 (decim_blocks_kernel<..., SPLIT>) --------------------------------
 # One checker for tests/test_gpu_join.py and tools/soak_split.py.  The dealt form hands 4 KiB block values from workgroup to
 # workgroup through the plan's scratch; what could go wrong there is a joiner that reads a block value of an EARLIER launch (stale),

@@ -11,39 +11,13 @@ import pytest
 import sxxcvr_amd
 from sxxcvr_amd import design_lowpass
 from sxxcvr_amd.resampler import DECIMATE, KERNEL_GENERIC, KERNEL_TILED
-from gpu_util import OUT_FILL, assert_bit_exact, to_cpu, to_gpu
+from gpu_util import OUT_FILL, assert_bands, assert_bit_exact, chan_ref, to_cpu, to_gpu
 
 pytestmark = pytest.mark.gpu
 
 SEED = 0xC4A77E1
 TILE_IN = 2048
 TILED, GENERIC = "chan4_kernel", "chan_generic_kernel"
-
-
-def chan_ref(oracle, h, x, threads=None):
-    """[4, n_out] complex64: the four bands of one pass over x from zero history."""
-    h = np.ascontiguousarray(h, dtype=np.float32)
-    u = []
-    for r in range(4):
-        hr = np.zeros_like(h)                               # +0.0
-        hr[r::4] = h[r::4]
-        u.append(oracle.decim_f32(hr, 4, x, 1, 1, threads=threads))
-    f = np.float32
-    s0re, s0im, s1re, s1im = u[0].real + u[2].real, u[0].imag + u[2].imag, u[0].real - u[2].real, u[0].imag - u[2].imag
-    t0re, t0im, t1re, t1im = u[1].real + u[3].real, u[1].imag + u[3].imag, u[1].real - u[3].real, u[1].imag - u[3].imag
-    assert s0re.dtype == f and t1im.dtype == f
-    y = np.empty((4, u[0].size), dtype=np.complex64)
-    y[0].real, y[0].imag = s0re + t0re, s0im + t0im
-    y[1].real, y[1].imag = s1re - t1im, s1im + t1re
-    y[2].real, y[2].imag = s0re - t0re, s0im - t0im
-    y[3].real, y[3].imag = s1re + t1im, s1im - t1re
-    return y
-
-
-def assert_bands(got, ref, what):
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    for k in range(4):
-        assert_bit_exact(got[k], ref[k], "%s, band %d" % (what, k))
 
 
 def random_taps(n, seed=5):

@@ -29,7 +29,8 @@ pytestmark = pytest.mark.gpu
 @functools.lru_cache(maxsize=None)
 def shapes():
     """name -> (mode, ratio, taps): both modes at ratios 4 .. 96 with 32 taps per phase, /4 with 64 taps, /4 with 128 taps
-    that are not bit-symmetric, one shape only the generic kernels take, and the two complex-tap plans."""
+    that are not bit-symmetric, one shape only the generic kernels take, the two complex-tap plans, and the band plans
+    ("chan...": created through Channelizer, "syn...": through Synthesizer) with the tiled kernels' 128 taps and with 64."""
     import sxxcvr_amd
     from sxxcvr_amd.resampler import DECIMATE, INTERPOLATE
     out = {}
@@ -44,11 +45,15 @@ def shapes():
     out["interp5x40"] = (INTERPOLATE, 5, sxxcvr_amd.design_lowpass(40, 5, 8.0, 5.0))
     out["cx4x128"] = (DECIMATE, 4, sxxcvr_amd.design_bandpass(128, 4, 1, 4))
     out["cx8x256"] = (DECIMATE, 8, sxxcvr_amd.design_bandpass(256, 8, 1, 8))
+    for n in (128, 64):
+        out["chan4x%d" % n] = (DECIMATE, 4, sxxcvr_amd.design_lowpass(n, 4))
+        out["syn4x%d" % n] = (INTERPOLATE, 4, sxxcvr_amd.design_lowpass(n, 4, 8.0, 4.0))
     return out
 
 
 SHAPE_NAMES = ["decim%d" % r for r in (4, 8, 16, 32, 48, 96)] + ["interp%d" % r for r in (4, 8, 16, 32, 48, 96)] + \
-              ["decim4x64", "decim4asym", "decim5x40", "interp5x40", "cx4x128", "cx8x256"]
+              ["decim4x64", "decim4asym", "decim5x40", "interp5x40", "cx4x128", "cx8x256"] + \
+              ["chan4x128", "chan4x64", "syn4x128", "syn4x64"]
 
 
 def call_sizes(plan, mode, ratio, nchan):
@@ -69,10 +74,19 @@ def call_sizes(plan, mode, ratio, nchan):
     return sorted(s for s in sizes if s >= 1)
 
 
-def rows_for(name, fmt, nchan, sizes=None):
+def make_plan(name, fmt, nchan):
     import sxxcvr_amd
     mode, ratio, taps = shapes()[name]
-    plan = sxxcvr_amd.Resampler(mode, taps, ratio, nchan=nchan, fmt=fmt)
+    if name.startswith("chan"):
+        return sxxcvr_amd.Channelizer(taps, ratio, nchan=nchan, fmt=fmt)
+    if name.startswith("syn"):
+        return sxxcvr_amd.Synthesizer(taps, ratio, nchan=nchan, fmt=fmt)
+    return sxxcvr_amd.Resampler(mode, taps, ratio, nchan=nchan, fmt=fmt)
+
+
+def rows_for(name, fmt, nchan, sizes=None):
+    mode, ratio, taps = shapes()[name]
+    plan = make_plan(name, fmt, nchan)
     try:
         sizes = sizes if sizes is not None else call_sizes(plan, mode, ratio, nchan)
         return [[n] + [plan.geometry(n)[f] for f in FIELDS] for n in sizes]

@@ -11,7 +11,7 @@ import pytest
 import sxxcvr_amd
 from sxxcvr_amd import design_lowpass
 from sxxcvr_amd.resampler import DECIMATE, INTERPOLATE, KERNEL_GENERIC, KERNEL_TILED
-from gpu_util import OUT_FILL, assert_bit_exact, to_cpu, to_gpu
+from gpu_util import OUT_FILL, assert_bit_exact, syn_ref, to_cpu, to_gpu
 from test_synthesizer_host import band_tone, tone_and_rest, wideband_tone
 
 pytestmark = pytest.mark.gpu
@@ -19,34 +19,6 @@ pytestmark = pytest.mark.gpu
 SEED = 0x5E7A11
 T = 256                                                     # inputs per band of a tile
 TILED, GENERIC = "synthesis4_kernel", "synthesis_generic_kernel"
-
-
-def butterflies_f32(x):
-    """[4, n] complex64 -> the four streams v_r, float32 arithmetic."""
-    f = np.float32
-    re = [np.ascontiguousarray(x[k].real) for k in range(4)]
-    im = [np.ascontiguousarray(x[k].imag) for k in range(4)]
-    a0re, a0im, a1re, a1im = re[0] + re[2], im[0] + im[2], re[0] - re[2], im[0] - im[2]
-    b0re, b0im, b1re, b1im = re[1] + re[3], im[1] + im[3], re[1] - re[3], im[1] - im[3]
-    assert a0re.dtype == f and b1im.dtype == f
-    v = np.empty((4, x.shape[1]), dtype=np.complex64)
-    v[0].real, v[0].imag = a0re + b0re, a0im + b0im
-    v[1].real, v[1].imag = a1re - b1im, a1im + b1re
-    v[2].real, v[2].imag = a0re - b0re, a0im - b0im
-    v[3].real, v[3].imag = a1re + b1im, a1im - b1re
-    return v
-
-
-def syn_ref(oracle, h, x, jsplit, threads=None):
-    """[4 n] complex64: one pass over the four bands x [4, n] from zero history."""
-    h = np.ascontiguousarray(h, dtype=np.float32)
-    x = np.ascontiguousarray(x, dtype=np.complex64)
-    v = butterflies_f32(x)
-    w = np.empty(4 * x.shape[1], dtype=np.complex64)
-    for r in range(4):
-        y = oracle.interp_f32(h, 4, v[r], jsplit) if threads is None else oracle.interp_f32_mt(h, 4, v[r], jsplit, threads=threads)
-        w[r::4] = y[r::4]
-    return w
 
 
 def random_taps(n, seed=5):
