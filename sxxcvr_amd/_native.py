@@ -129,6 +129,10 @@ def load_sxfir(profiling=False):
         "sxfir_create_channelizer": (ci, [P(vp), vp, ci, ci, ci, ci, ci]),
         "sxfir_channelize": (ci, [vp, vp, sz, sz, vp, sz, sz, P(sz), vp]),
         "sxfir_plan_bands": (ci, [vp, P(ci)]),
+        # include/sxfir_channelizer_os.h: the 2x oversampled 4-band channelizer
+        "sxfir_channelizer_os_abi_version": (ci, []),
+        "sxfir_create_channelizer_os": (ci, [P(vp), vp, ci, ci, ci, ci, ci, ci]),
+        "sxfir_plan_oversampling": (ci, [vp, P(ci)]),
         # include/sxfir_synthesizer.h: the 4-band synthesizer
         "sxfir_synthesizer_abi_version": (ci, []),
         "sxfir_create_synthesizer": (ci, [P(vp), vp, ci, ci, ci, ci, ci]),

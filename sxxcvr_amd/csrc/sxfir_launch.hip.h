@@ -30,7 +30,7 @@ struct CallIO {
 
 // What the tiled kernels' 16-byte stores need: an aligned output and, between channels, an even stride -- whole 16-byte units of
 // halves (a stride of 4) for the multi-column and dense kernels on CF16 storage; a channelizer's bands are stored like channels:
-// an even band stride too.  (LDS-DMA sources need no 16-byte alignment -- verified on MI355X, tools/probe_unaligned.hip -- and the
+// an even band stride too (critically sampled or oversampled).  (LDS-DMA sources need no 16-byte alignment -- verified on MI355X, tools/probe_unaligned.hip -- and the
 // edge loads go sample by sample: the input's alignment and strides are the entry point's business alone.)  The stride of 4 holds
 // for every kernel of a multi_capable CF16 plan; that is right only while no CF16 plan is both multi_capable and tile_capable
 // (sxfir_create: half4_wide excludes multi, the `mu` knob is CF32 only) -- a shape with both would need 2 for its tile kernel.
@@ -89,7 +89,7 @@ struct LaunchGeom {
     int split;                // work items per tile ((tile, block) dealing of decim_blocks_kernel), else 1
     int phase_blocks;         // CF16 interpolator tile kernel: workgroups that share a tile, one per phase block (x48, x96: 3), else 1
 };
-enum { GEOM_GENERIC = 0, GEOM_MULTI = 1, GEOM_WIDE = 2, GEOM_TILE = 3, GEOM_IPASS = 4, GEOM_ITILE = 5, GEOM_CX = 6, GEOM_CHAN4 = 7, GEOM_SYN4 = 8 };
+enum { GEOM_GENERIC = 0, GEOM_MULTI = 1, GEOM_WIDE = 2, GEOM_TILE = 3, GEOM_IPASS = 4, GEOM_ITILE = 5, GEOM_CX = 6, GEOM_CHAN4 = 7, GEOM_SYN4 = 8, GEOM_CHAN4X2 = 9 };
 
 // The strided-pass constants of the /4 kernels: `groups` waves per channel over n_tiles tiles (sched 0: XCD-blocked strided passes,
 // 1: one contiguous run per wave, else plain strided passes), worked out here so that a wave's prologue has no integer division
@@ -151,11 +151,20 @@ static long long first_offset(const sxfir_plan *p)
 static LaunchGeom decim_geom(const sxfir_plan *p, long long n_out, long long first, bool aligned)
 {
     const bool chan = p->kind == KIND_CHANNELIZER;
-    LaunchGeom g{GEOM_GENERIC, chan ? "chan_generic_kernel" : p->kind == KIND_COMPLEX ? "decim_cx_generic_kernel" : "decim_generic_kernel", 256,
+    const bool chan_os = chan && p->oversample == 2;
+    LaunchGeom g{GEOM_GENERIC, chan_os ? "chan4x2_generic_kernel" : chan ? "chan_generic_kernel" : p->kind == KIND_COMPLEX ? "decim_cx_generic_kernel" : "decim_generic_kernel", 256,
                  (n_out + 255) / 256, (n_out + 255) / 256, (long long)p->compute_units * 8, 1, 1};
     const long long CU = p->compute_units;
     const bool want = p->kernel != SXFIR_KERNEL_GENERIC && first == 0;
-    if (p->ext_tiled && want && aligned) {
+    if (chan_os) {
+        // 2x oversampled channelizer (ratio 2): chan4x2_kernel for 4 bands x 128 taps on CF32, tiles of 1024 outputs PER BAND = 2048
+        // inputs.  `first == 0` says the call starts on an output; the tiled kernel's lane map also needs that output's index to be
+        // EVEN, i.e. a stream position that is a multiple of 4.  Generations as for chan4_kernel
+        if (p->ext_tiled && want && aligned && p->consumed % 4 == 0) {
+            set_tiles(g, GEOM_CHAN4X2, "chan4x2_kernel", n_out, 1024, CU * p->occ_ext);
+            g.groups = clamp_groups(g.resident * generations(p, g.n_tiles, g.resident, true) / p->nchan, g.n_tiles);
+        }
+    } else if (p->ext_tiled && want && aligned) {
         // complex taps: decim4_cx_kernel for /4 x 128 on CF32; channelizer: chan4_kernel for 4 bands x 128 taps on CF32, tiles of 512
         // outputs PER BAND; the generic kernel of the kind for everything else.  Both on the wide kernel's frame: its sixteen
         // generations of waves at the sizes they were measured at, fewer while that would leave a wave under four tiles
@@ -306,6 +315,17 @@ static sxfir::ChanTileArgs chan_tile_args(const sxfir_plan *p, const CallIO &c, 
     return a;
 }
 
+// 2x oversampled channelizer plans: ChanTileArgs for chan4x2_kernel (chan_tile_args), and the generic kernel's struct of
+// sxfir_chan4x2.hip.h -- `first` samples into the call lies the output of absolute index (consumed + first) / ratio
+static sxfir::ChanOsGenericArgs chan_os_generic_args(const sxfir_plan *p, const CallIO &c, long long first)
+{
+    sxfir::ChanOsGenericArgs a{};
+    a.g = generic_args(p, c, first);
+    a.band_stride = (long long)c.band_stride;
+    a.m_first = (p->consumed + first) / p->ratio;
+    return a;
+}
+
 static sxfir::ChanGenericArgs chan_generic_args(const sxfir_plan *p, const CallIO &c, long long first)
 {
     sxfir::ChanGenericArgs a{};
@@ -375,13 +395,15 @@ static int launch_decim(sxfir_plan *p, const CallIO &c, bool *history_done)
         if (p->kernel == SXFIR_KERNEL_TILED)
             return fail(SXFIR_EUNSUPPORTED,
                         "tiled kernel needs a 16-byte aligned output, an even output stride and a call that starts on "
-                        "an output boundary");
+                        "an output boundary%s", p->kind == KIND_CHANNELIZER && p->oversample == 2 ? " of even index (a stream position that is a multiple of 4)" : "");
+        if (p->kind == KIND_CHANNELIZER && p->oversample == 2) return launch(p->k.chan4x2_generic, grid, 256, c.st, chan_os_generic_args(p, c, first));
         if (p->kind == KIND_CHANNELIZER) return launch(p->k.chan_generic, grid, 256, c.st, chan_generic_args(p, c, first));
         return launch(p->k.generic, grid, 256, c.st, generic_args(p, c, first));
     }
     if (geom.n_tiles > 0x7fffffffLL) return fail(SXFIR_EINVAL, "call too large");
     *history_done = true;
     if (geom.kind == GEOM_CHAN4) return launch(p->k.chan4, grid, 64, c.st, chan_tile_args(p, c, geom));
+    if (geom.kind == GEOM_CHAN4X2) return launch(p->k.chan4x2, grid, 64, c.st, chan_tile_args(p, c, geom));
     if (geom.kind == GEOM_MULTI) {
         sxfir::DecimMultiArgs a = decim_multi_args(p, c, geom);
         if (p->blocks) {

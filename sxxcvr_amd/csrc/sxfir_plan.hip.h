@@ -7,8 +7,9 @@
 #pragma once
 
 // What created the plan: sxfir_create, sxfir_create_complex (sxfir_complex.hip.h), sxfir_create_channelizer
-// (sxfir_channelizer.hip.h), sxfir_create_synthesizer (sxfir_synthesizer.hip.h).  A complex-tap plan is a decimator whose taps_dev
-// holds a[0, ntaps) then b[0, ntaps); the band kinds are a /bands decimator and a x bands interpolator in everything about the stream.
+// (sxfir_channelizer.hip.h), sxfir_create_synthesizer (sxfir_synthesizer.hip.h), sxfir_create_channelizer_os
+// (sxfir_channelizer_os.hip.h: KIND_CHANNELIZER with ratio = bands / oversample).  A complex-tap plan is a decimator whose taps_dev
+// holds a[0, ntaps) then b[0, ntaps); the band kinds are a /ratio decimator and a x bands interpolator in everything about the stream.
 enum PlanKind { KIND_REAL = 0, KIND_COMPLEX = 1, KIND_CHANNELIZER = 2, KIND_SYNTHESIZER = 3 };
 enum TapTable { TAPS_SCALED = 0, TAPS_SUBSET8 = 1, TAPS_PASS8 = 2, TAPS_BLOCKS16 = 3, TAPS_PHASE4 = 4 };
 
@@ -21,6 +22,7 @@ typedef void (*DecimTileFn)(sxfir::DecimTileArgs);
 typedef void (*InterpTileFn)(sxfir::InterpTileArgs);
 typedef void (*ChanTileFn)(sxfir::ChanTileArgs);
 typedef void (*ChanGenericFn)(sxfir::ChanGenericArgs);
+typedef void (*ChanOsGenericFn)(sxfir::ChanOsGenericArgs);
 typedef void (*SynTileFn)(sxfir::SynTileArgs);
 typedef void (*SynGenericFn)(sxfir::SynGenericArgs);
 struct KernelTable {
@@ -31,6 +33,8 @@ struct KernelTable {
     InterpTileFn interp[2][2];   // [keyed][split]: interp8_pass_kernel; interp_tile_kernel on CF16 storage ([0][0] alone)
     ChanTileFn chan4;            // channelizer plans (include/sxfir_channelizer.h): chan4_kernel (4 bands x 128 taps, CF32) ...
     ChanGenericFn chan_generic;  // ... and chan_generic_kernel, which every channelizer plan has INSTEAD of `generic`
+    ChanTileFn chan4x2;          // 2x oversampled channelizer plans (include/sxfir_channelizer_os.h): chan4x2_kernel (4 bands x 128 taps, CF32) ...
+    ChanOsGenericFn chan4x2_generic;   // ... and chan4x2_generic_kernel, which every such plan has INSTEAD of `generic` and `chan_generic`
     SynTileFn syn4;              // synthesizer plans (include/sxfir_synthesizer.h): synthesis4_kernel (4 bands x 128 taps, CF32) ...
     SynGenericFn syn_generic;    // ... and synthesis_generic_kernel, which every synthesizer plan has INSTEAD of `generic`
 };
@@ -38,8 +42,10 @@ struct KernelTable {
 struct sxfir_plan {
     int kind;              // PlanKind
     int mode, ntaps, ratio, nchan, fmt, device;
-    int bands;             // the band kinds: 4 (= ratio); else 0.  A synthesizer's hist_dev holds bands x hist_len / bands samples per
-                           // channel, band k's at k * hist_len / bands
+    int bands;             // the band kinds: 4 (= ratio, but for the oversampled channelizer); else 0.  A synthesizer's hist_dev holds
+                           // bands x hist_len / bands samples per channel, band k's at k * hist_len / bands
+    int oversample;        // channelizer plans: bands / ratio -- 1 critically sampled (sxfir_create_channelizer), 2 each band at fs/2
+                           // (sxfir_create_channelizer_os: ratio 2, bands 4); else 0
     int kernel;            // SXFIR_KERNEL_*
     int hist_len;          // samples of history kept per channel
     int blocks;            // /48, /96: sixteen-column blocks of decim_blocks_kernel (3, 6), else 0
@@ -101,8 +107,8 @@ struct sxfir_plan {
     bool ipass_wait0;         // (profiling) SXFIR_IPASS_WAIT0=1: its vmcnt(0) form (A/B partner of the counted wait)
     float taps_k[64];         // the first 64 taps (times 2^-31 for S32 plans) for kernels that take them by value
     bool symmetric;           // taps[k] == taps[ntaps-1-k] bit for bit (every linear-phase design)
-    bool ext_tiled;           // the other kinds: the shape their tiled kernel takes (decim4_cx_kernel: /4, 128 taps, CF32; chan4_kernel and
-                              // synthesis4_kernel: 4 bands x 128 taps, CF32)
+    bool ext_tiled;           // the other kinds: the shape their tiled kernel takes (decim4_cx_kernel: /4, 128 taps, CF32; chan4_kernel,
+                              // chan4x2_kernel and synthesis4_kernel: 4 bands x 128 taps, CF32)
     int occ_ext;              // its resident waves per CU
     void *hist_dev;        // current history: nchan * hist_len samples
     void *hist_alt;        // the tile kernel writes the next history here, then the two swap
@@ -236,6 +242,15 @@ static InterpTileFn interp_kernel(int ratio, int fmt, bool keyed, bool split)
     return nullptr;
 }
 
+// 2x oversampled channelizer plans: four chains and the butterflies of the output's parity per thread
+static ChanOsGenericFn chan4x2_generic_kernel_for(int fmt)
+{
+    using namespace sxfir;
+    if (fmt == SXFIR_CF32) return chan4x2_generic_kernel<CF32>;
+    if (fmt == SXFIR_CF16) return chan4x2_generic_kernel<CF16>;
+    return chan4x2_generic_kernel<S32, CF32>;
+}
+
 // synthesizer plans: the butterflies once per input index, four phase chains per thread
 static SynGenericFn synthesis_generic_kernel_for(int fmt)
 {
@@ -250,6 +265,11 @@ static void resolve_kernels(sxfir_plan *p)
 {
     KernelTable &k = p->k;
     k = KernelTable{};
+    if (p->kind == KIND_CHANNELIZER && p->oversample == 2) {
+        k.chan4x2_generic = chan4x2_generic_kernel_for(p->fmt);
+        if (p->ext_tiled) k.chan4x2 = sxfir::chan4x2_kernel;
+        return;
+    }
     if (p->kind == KIND_CHANNELIZER) {
         k.chan_generic = chan_generic_kernel_for(p->fmt);
         if (p->ext_tiled) k.chan4 = sxfir::chan4_kernel;
@@ -326,6 +346,7 @@ static int new_plan(sxfir_plan **pp, int kind, int mode, int ntaps, int ratio, i
     p->fmt = fmt;
     p->device = device;
     p->bands = kind == KIND_CHANNELIZER || kind == KIND_SYNTHESIZER ? ratio : 0;
+    p->oversample = kind == KIND_CHANNELIZER ? 1 : 0;
     p->kernel = SXFIR_KERNEL_AUTO;
     p->compute_units = prop.multiProcessorCount;
     p->thr2 = 1.0e-3f * 1.0e-3f;

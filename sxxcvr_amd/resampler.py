@@ -353,21 +353,38 @@ class Channelizer(_Plan):
     """The 4-band channelizer (include/sxfir_channelizer.h): all `nbands` sub-bands of the /nbands raster out of one wideband
     stream in one pass.  `taps`: the REAL prototype low-pass (design_lowpass(ntaps, nbands)); band k is the band that
     design_bandpass(ntaps, nbands, k, nbands) centres, at 0 Hz of its output.  Stream state, contract, geometry and kernel
-    choice are a /nbands decimator's: the same methods as Resampler."""
+    choice are a /nbands decimator's: the same methods as Resampler.
 
-    def __init__(self, taps, nbands=4, nchan=1, fmt="CF32", device=-1):
+    `oversample=2` (include/sxfir_channelizer_os.h): the same bands and centres, each leaving at fs/2 instead of fs/4 -- alias-free
+    across its whole width.  Even-time outputs have the bits of the critically sampled plan's; the plan is a /(nbands // oversample)
+    decimator in everything about the stream."""
+
+    def __init__(self, taps, nbands=4, nchan=1, fmt="CF32", device=-1, oversample=1):
         self._lib = load_sxfir()
         self._plan = C.c_void_p()
         taps = np.ascontiguousarray(taps, dtype=np.float32)
-        self.mode, self.ratio, self.nbands, self.nchan, self.fmt, self.ntaps = DECIMATE, int(nbands), int(nbands), int(nchan), _FMT[fmt], taps.size
-        self._ck(self._lib.sxfir_create_channelizer(C.byref(self._plan), taps.ctypes.data_as(C.c_void_p), taps.size, int(nbands),
-                                                    int(nchan), self.fmt, int(device)))
+        self.mode, self.nbands, self.nchan, self.fmt, self.ntaps = DECIMATE, int(nbands), int(nchan), _FMT[fmt], taps.size
+        if int(oversample) == 1:
+            self.ratio = int(nbands)
+            self._ck(self._lib.sxfir_create_channelizer(C.byref(self._plan), taps.ctypes.data_as(C.c_void_p), taps.size, int(nbands),
+                                                        int(nchan), self.fmt, int(device)))
+        else:
+            self.ratio = int(nbands) // int(oversample) if int(oversample) > 0 else 0
+            self._ck(self._lib.sxfir_create_channelizer_os(C.byref(self._plan), taps.ctypes.data_as(C.c_void_p), taps.size, int(nbands),
+                                                           int(oversample), int(nchan), self.fmt, int(device)))
 
     @property
     def bands(self):
         """sxfir_plan_bands: the plan's own count."""
         n = C.c_int()
         self._ck(self._lib.sxfir_plan_bands(self._plan, C.byref(n)))
+        return n.value
+
+    @property
+    def oversampling(self):
+        """sxfir_plan_oversampling: 1 for the critically sampled plan, 2 for the oversampled one."""
+        n = C.c_int()
+        self._ck(self._lib.sxfir_plan_oversampling(self._plan, C.byref(n)))
         return n.value
 
     def process_ptr(self, in_ptr, n_in, in_stride, out_ptr, out_stride, band_stride, stream=0):
