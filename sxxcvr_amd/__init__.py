@@ -3,7 +3,8 @@ SoapySDR ``driver=sx`` Device/Stream surface of tejeez/sxxcvr.
 
 The product is native: hand-written HIP kernels (gfx950) behind a C ABI
 (include/sxfir.h, include/sxfir_complex.h, include/sxfir_channelizer.h,
-include/sxfir_channelizer_os.h, include/sxfir_synthesizer.h, include/sx_device.h).  This package only loads those
+include/sxfir_channelizer_os.h, include/sxfir_synthesizer.h, include/sxfir_synthesizer_os.h, include/sx_device.h).
+This package only loads those
 libraries and mirrors the reference's Python-facing call pattern; there is no
 CPU implementation and nothing here imports the oracle.
 """

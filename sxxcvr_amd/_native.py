@@ -138,6 +138,10 @@ def load_sxfir(profiling=False):
         "sxfir_create_synthesizer": (ci, [P(vp), vp, ci, ci, ci, ci, ci]),
         "sxfir_synthesize": (ci, [vp, vp, sz, sz, sz, vp, sz, P(sz), vp]),
         "sxfir_plan_synthesis_bands": (ci, [vp, P(ci)]),
+        # include/sxfir_synthesizer_os.h: the 2x oversampled 4-band synthesizer
+        "sxfir_synthesizer_os_abi_version": (ci, []),
+        "sxfir_create_synthesizer_os": (ci, [P(vp), vp, ci, ci, ci, ci, ci, ci]),
+        "sxfir_plan_synthesis_oversampling": (ci, [vp, P(ci)]),
     }
     if profiling:
         sig["sxfir_debug_clock"] = (ci, [vp, P(dbl)])

@@ -5,6 +5,7 @@
 #include "../../include/sxfir_channelizer.h"
 #include "../../include/sxfir_channelizer_os.h"
 #include "../../include/sxfir_synthesizer.h"
+#include "../../include/sxfir_synthesizer_os.h"
 
 #include <hip/hip_runtime.h>
 
@@ -78,6 +79,7 @@
 #include "sxfir_chan4.hip.h"                    // the 4-band channelizer (include/sxfir_channelizer.h)
 #include "sxfir_synthesis4.hip.h"               // the 4-band synthesizer (include/sxfir_synthesizer.h)
 #include "sxfir_chan4x2.hip.h"                  // the 2x oversampled 4-band channelizer (include/sxfir_channelizer_os.h)
+#include "sxfir_synthesis4x2.hip.h"             // the 2x oversampled 4-band synthesizer (include/sxfir_synthesizer_os.h)
 
 namespace {
 
@@ -115,3 +117,4 @@ inline size_t sample_bytes(int fmt) { return fmt == SXFIR_CF16 ? 4 : 8; }   // C
 #include "sxfir_channelizer.hip.h"   // sxfir_create_channelizer, sxfir_channelize (include/sxfir_channelizer.h)
 #include "sxfir_synthesizer.hip.h"   // sxfir_create_synthesizer, sxfir_synthesize (include/sxfir_synthesizer.h)
 #include "sxfir_channelizer_os.hip.h"   // sxfir_create_channelizer_os, sxfir_plan_oversampling (include/sxfir_channelizer_os.h)
+#include "sxfir_synthesizer_os.hip.h"   // sxfir_create_synthesizer_os, sxfir_plan_synthesis_oversampling (include/sxfir_synthesizer_os.h)

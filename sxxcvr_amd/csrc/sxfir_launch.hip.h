@@ -89,7 +89,7 @@ struct LaunchGeom {
     int split;                // work items per tile ((tile, block) dealing of decim_blocks_kernel), else 1
     int phase_blocks;         // CF16 interpolator tile kernel: workgroups that share a tile, one per phase block (x48, x96: 3), else 1
 };
-enum { GEOM_GENERIC = 0, GEOM_MULTI = 1, GEOM_WIDE = 2, GEOM_TILE = 3, GEOM_IPASS = 4, GEOM_ITILE = 5, GEOM_CX = 6, GEOM_CHAN4 = 7, GEOM_SYN4 = 8, GEOM_CHAN4X2 = 9 };
+enum { GEOM_GENERIC = 0, GEOM_MULTI = 1, GEOM_WIDE = 2, GEOM_TILE = 3, GEOM_IPASS = 4, GEOM_ITILE = 5, GEOM_CX = 6, GEOM_CHAN4 = 7, GEOM_SYN4 = 8, GEOM_CHAN4X2 = 9, GEOM_SYN4X2 = 10 };
 
 // The strided-pass constants of the /4 kernels: `groups` waves per channel over n_tiles tiles (sched 0: XCD-blocked strided passes,
 // 1: one contiguous run per wave, else plain strided passes), worked out here so that a wave's prologue has no integer division
@@ -198,9 +198,14 @@ static LaunchGeom interp_geom(const sxfir_plan *p, long long n_in, bool aligned,
         // synthesizer (sxfir_create_synthesizer): synthesis4_kernel for 4 bands x 128 taps on CF32, tiles of 256 inputs PER BAND on the x4
         // pass kernel's frame; one thread per input index of synthesis_generic_kernel for everything else.  Small calls dealt as fewer
         // generations of waves, the channelizer's rule
-        LaunchGeom s{GEOM_GENERIC, "synthesis_generic_kernel", 256, (n_in + 255) / 256, (n_in + 255) / 256, (long long)p->compute_units * 8, 1, 1};
+        // 2x oversampled (sxfir_create_synthesizer_os, ratio 2): synthesis4x2_kernel, tiles of 512 inputs PER BAND, and
+        // synthesis_os_generic_kernel.  The tiled kernel takes a call that starts at any per-band index: the start's parity is its argument
+        const bool os = p->oversample == 2;
+        LaunchGeom s{GEOM_GENERIC, os ? "synthesis_os_generic_kernel" : "synthesis_generic_kernel", 256, (n_in + 255) / 256, (n_in + 255) / 256,
+                     (long long)p->compute_units * 8, 1, 1};
         if (p->ext_tiled && p->kernel != SXFIR_KERNEL_GENERIC && aligned) {
-            set_tiles(s, GEOM_SYN4, "synthesis4_kernel", n_in, 256, (long long)p->compute_units * p->occ_ext);
+            if (os) set_tiles(s, GEOM_SYN4X2, "synthesis4x2_kernel", n_in, sxfir::Syn4x2::TILE_IN, (long long)p->compute_units * p->occ_ext);
+            else set_tiles(s, GEOM_SYN4, "synthesis4_kernel", n_in, 256, (long long)p->compute_units * p->occ_ext);
             s.groups = clamp_groups(s.resident * generations(p, s.n_tiles, s.resident, true) / p->nchan, s.n_tiles);
         }
         return s;
@@ -342,7 +347,7 @@ static sxfir::SynTileArgs syn_tile_args(const sxfir_plan *p, const CallIO &c, co
     a.hist = (const float *)p->hist_dev;
     a.hist_out = (float *)p->hist_alt;
     a.out = (float *)c.out;
-    a.taps = p->taps_scaled_dev;                    // the phase-major table
+    a.taps = p->taps_scaled_dev;                    // the phase-major table (2x oversampled: the parity-major one)
     a.n_in = (long long)c.n_in;
     a.in_stride = (long long)c.in_stride;
     a.band_stride = (long long)c.band_stride;
@@ -359,6 +364,24 @@ static sxfir::SynGenericArgs syn_generic_args(const sxfir_plan *p, const CallIO 
     a.g = generic_args(p, c, 0);
     a.g.hist_len = p->hist_len / p->bands;      // a band's history; hist_stride stays the channel's
     a.band_stride = (long long)c.band_stride;
+    return a;
+}
+
+// 2x oversampled synthesizer plans: the two argument structs of sxfir_synthesis4x2.hip.h -- the call's first input has the
+// absolute per-band index `consumed`
+static sxfir::SynOsTileArgs syn_os_tile_args(const sxfir_plan *p, const CallIO &c, const LaunchGeom &geom)
+{
+    sxfir::SynOsTileArgs a{};
+    a.s = syn_tile_args(p, c, geom);
+    a.par = (int)(p->consumed & 1);
+    return a;
+}
+
+static sxfir::SynOsGenericArgs syn_os_generic_args(const sxfir_plan *p, const CallIO &c)
+{
+    sxfir::SynOsGenericArgs a{};
+    a.s = syn_generic_args(p, c);
+    a.m_first = p->consumed;
     return a;
 }
 
@@ -472,10 +495,16 @@ static int launch_synth(sxfir_plan *p, const CallIO &c, bool *history_done)
     if (geom.kind == GEOM_GENERIC) {
         if (p->kernel == SXFIR_KERNEL_TILED)
             return fail(SXFIR_EUNSUPPORTED, "tiled synthesizer needs a 16-byte aligned output and an even output stride");
+        if (p->oversample == 2) return launch(p->k.syn4x2_generic, grid, 256, c.st, syn_os_generic_args(p, c));
         return launch(p->k.syn_generic, grid, 256, c.st, syn_generic_args(p, c));
     }
-    if (int rc = need_tap_table(p, TAPS_PHASE4, "synthesis4_kernel")) return rc;
     if (geom.n_tiles > 0x7fffffffLL) return fail(SXFIR_EINVAL, "call too large");
+    if (geom.kind == GEOM_SYN4X2) {
+        if (int rc = need_tap_table(p, TAPS_PARITY2, "synthesis4x2_kernel")) return rc;
+        *history_done = true;
+        return launch(p->k.syn4x2, grid, 64, c.st, syn_os_tile_args(p, c, geom));
+    }
+    if (int rc = need_tap_table(p, TAPS_PHASE4, "synthesis4_kernel")) return rc;
     *history_done = true;
     return launch(p->k.syn4, grid, 64, c.st, syn_tile_args(p, c, geom));
 }
@@ -599,7 +628,7 @@ int sxfir_launch_geometry(const sxfir_plan *p, size_t n_in, sxfir_geometry *out)
     out->tiled = g.kind != GEOM_GENERIC;
     out->split = g.split;
     out->tile_samples = g.tile_out * p->ratio;       // wideband samples: a decimator's inputs, an interpolator's outputs
-    if (g.kind == GEOM_GENERIC) out->tile_samples = p->mode == SXFIR_DECIMATE ? 256LL * p->ratio : (p->kind == KIND_SYNTHESIZER ? 1024 : 256);
+    if (g.kind == GEOM_GENERIC) out->tile_samples = p->mode == SXFIR_DECIMATE ? 256LL * p->ratio : (p->kind == KIND_SYNTHESIZER ? 256LL * p->ratio : 256);
     out->n_tiles = g.n_tiles;
     out->workgroups = g.groups * p->nchan;
     out->resident = g.resident;

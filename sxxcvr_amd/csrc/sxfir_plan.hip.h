@@ -8,10 +8,11 @@
 
 // What created the plan: sxfir_create, sxfir_create_complex (sxfir_complex.hip.h), sxfir_create_channelizer
 // (sxfir_channelizer.hip.h), sxfir_create_synthesizer (sxfir_synthesizer.hip.h), sxfir_create_channelizer_os
-// (sxfir_channelizer_os.hip.h: KIND_CHANNELIZER with ratio = bands / oversample).  A complex-tap plan is a decimator whose taps_dev
-// holds a[0, ntaps) then b[0, ntaps); the band kinds are a /ratio decimator and a x bands interpolator in everything about the stream.
+// (sxfir_channelizer_os.hip.h: KIND_CHANNELIZER with ratio = bands / oversample), sxfir_create_synthesizer_os
+// (sxfir_synthesizer_os.hip.h: KIND_SYNTHESIZER with ratio = bands / oversample).  A complex-tap plan is a decimator whose taps_dev
+// holds a[0, ntaps) then b[0, ntaps); the band kinds are a /ratio decimator and a x ratio interpolator in everything about the stream.
 enum PlanKind { KIND_REAL = 0, KIND_COMPLEX = 1, KIND_CHANNELIZER = 2, KIND_SYNTHESIZER = 3 };
-enum TapTable { TAPS_SCALED = 0, TAPS_SUBSET8 = 1, TAPS_PASS8 = 2, TAPS_BLOCKS16 = 3, TAPS_PHASE4 = 4 };
+enum TapTable { TAPS_SCALED = 0, TAPS_SUBSET8 = 1, TAPS_PASS8 = 2, TAPS_BLOCKS16 = 3, TAPS_PHASE4 = 4, TAPS_PARITY2 = 5 };
 
 // One typed kernel pointer per launch-argument family, and a plan's kernels: resolved once by the plan's creator
 // (resolve_kernels below), read by the occupancy queries there and by the launches (sxfir_launch.hip.h).
@@ -25,6 +26,8 @@ typedef void (*ChanGenericFn)(sxfir::ChanGenericArgs);
 typedef void (*ChanOsGenericFn)(sxfir::ChanOsGenericArgs);
 typedef void (*SynTileFn)(sxfir::SynTileArgs);
 typedef void (*SynGenericFn)(sxfir::SynGenericArgs);
+typedef void (*SynOsTileFn)(sxfir::SynOsTileArgs);
+typedef void (*SynOsGenericFn)(sxfir::SynOsGenericArgs);
 struct KernelTable {
     GenericFn generic;           // decim_generic_kernel / decim_cx_generic_kernel / interp_generic_kernel: every plan has one
     DecimMultiFn dense;          // decim_dense_kernel (/8, /16, /32)
@@ -37,15 +40,18 @@ struct KernelTable {
     ChanOsGenericFn chan4x2_generic;   // ... and chan4x2_generic_kernel, which every such plan has INSTEAD of `generic` and `chan_generic`
     SynTileFn syn4;              // synthesizer plans (include/sxfir_synthesizer.h): synthesis4_kernel (4 bands x 128 taps, CF32) ...
     SynGenericFn syn_generic;    // ... and synthesis_generic_kernel, which every synthesizer plan has INSTEAD of `generic`
+    SynOsTileFn syn4x2;          // 2x oversampled synthesizer plans (include/sxfir_synthesizer_os.h): synthesis4x2_kernel (4 bands x 128 taps, CF32) ...
+    SynOsGenericFn syn4x2_generic;     // ... and synthesis_os_generic_kernel, which every such plan has INSTEAD of `generic` and `syn_generic`
 };
 
 struct sxfir_plan {
     int kind;              // PlanKind
     int mode, ntaps, ratio, nchan, fmt, device;
-    int bands;             // the band kinds: 4 (= ratio, but for the oversampled channelizer); else 0.  A synthesizer's hist_dev holds
+    int bands;             // the band kinds: 4 (= ratio, but for the oversampled plans); else 0.  A synthesizer's hist_dev holds
                            // bands x hist_len / bands samples per channel, band k's at k * hist_len / bands
     int oversample;        // channelizer plans: bands / ratio -- 1 critically sampled (sxfir_create_channelizer), 2 each band at fs/2
-                           // (sxfir_create_channelizer_os: ratio 2, bands 4); else 0
+                           // (sxfir_create_channelizer_os: ratio 2, bands 4); synthesizer plans likewise: 1 each band at fs/4
+                           // (sxfir_create_synthesizer), 2 each band at fs/2 (sxfir_create_synthesizer_os: ratio 2, bands 4); else 0
     int kernel;            // SXFIR_KERNEL_*
     int hist_len;          // samples of history kept per channel
     int blocks;            // /48, /96: sixteen-column blocks of decim_blocks_kernel (3, 6), else 0
@@ -100,6 +106,7 @@ struct sxfir_plan {
                               // TAPS_SUBSET8: the subset-major table of decim_dense_kernel<8, ..., SUBSET> (times 2^-31 for S32 plans);
                               // TAPS_PASS8: the pass-major table of interp8_pass_kernel (pass (c, p) at 64 (2c + p), (jj, rr) at 4 jj + rr).
                               // TAPS_PHASE4: the phase-major table of synthesis4_kernel (h[4j + r] at (ntaps / 4) r + j).
+                              // TAPS_PARITY2: the parity-major table of synthesis4x2_kernel (h[2i + q] at (ntaps / 2) q + i).
                               // Every launch that hands taps_scaled_dev to a kernel checks this first (need_tap_table).
     bool ipass;               // x8, 256 taps, CF32: interp8_pass_kernel (scalar taps, four passes per tile)
     int occ_ipass;
@@ -108,7 +115,7 @@ struct sxfir_plan {
     float taps_k[64];         // the first 64 taps (times 2^-31 for S32 plans) for kernels that take them by value
     bool symmetric;           // taps[k] == taps[ntaps-1-k] bit for bit (every linear-phase design)
     bool ext_tiled;           // the other kinds: the shape their tiled kernel takes (decim4_cx_kernel: /4, 128 taps, CF32; chan4_kernel,
-                              // chan4x2_kernel and synthesis4_kernel: 4 bands x 128 taps, CF32)
+                              // chan4x2_kernel, synthesis4_kernel and synthesis4x2_kernel: 4 bands x 128 taps, CF32)
     int occ_ext;              // its resident waves per CU
     void *hist_dev;        // current history: nchan * hist_len samples
     void *hist_alt;        // the tile kernel writes the next history here, then the two swap
@@ -260,6 +267,15 @@ static SynGenericFn synthesis_generic_kernel_for(int fmt)
     return synthesis_generic_kernel<CF32, S32>;
 }
 
+// 2x oversampled synthesizer plans: the two DFT outputs an input index needs, two chains per thread
+static SynOsGenericFn synthesis_os_generic_kernel_for(int fmt)
+{
+    using namespace sxfir;
+    if (fmt == SXFIR_CF32) return synthesis_os_generic_kernel<CF32>;
+    if (fmt == SXFIR_CF16) return synthesis_os_generic_kernel<CF16>;
+    return synthesis_os_generic_kernel<CF32, S32>;
+}
+
 // The plan's kernels, from its kind and the capability flags its creator has settled (the profiling knobs included)
 static void resolve_kernels(sxfir_plan *p)
 {
@@ -273,6 +289,11 @@ static void resolve_kernels(sxfir_plan *p)
     if (p->kind == KIND_CHANNELIZER) {
         k.chan_generic = chan_generic_kernel_for(p->fmt);
         if (p->ext_tiled) k.chan4 = sxfir::chan4_kernel;
+        return;
+    }
+    if (p->kind == KIND_SYNTHESIZER && p->oversample == 2) {
+        k.syn4x2_generic = synthesis_os_generic_kernel_for(p->fmt);
+        if (p->ext_tiled) k.syn4x2 = sxfir::synthesis4x2_kernel;
         return;
     }
     if (p->kind == KIND_SYNTHESIZER) {
@@ -346,7 +367,7 @@ static int new_plan(sxfir_plan **pp, int kind, int mode, int ntaps, int ratio, i
     p->fmt = fmt;
     p->device = device;
     p->bands = kind == KIND_CHANNELIZER || kind == KIND_SYNTHESIZER ? ratio : 0;
-    p->oversample = kind == KIND_CHANNELIZER ? 1 : 0;
+    p->oversample = kind == KIND_CHANNELIZER || kind == KIND_SYNTHESIZER ? 1 : 0;
     p->kernel = SXFIR_KERNEL_AUTO;
     p->compute_units = prop.multiProcessorCount;
     p->thr2 = 1.0e-3f * 1.0e-3f;

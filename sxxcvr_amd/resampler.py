@@ -431,15 +431,25 @@ class Synthesizer(_Plan):
     """The 4-band synthesizer (include/sxfir_synthesizer.h): `nbands` sub-bands of the x nbands raster into one wideband stream in one
     pass -- what Channelizer takes apart, put together.  `taps`: the REAL prototype low-pass of a x nbands interpolator
     (design_lowpass(ntaps, nbands, gain=nbands)); band k lands at k / nbands cycles per output sample.  Stream state, contract,
-    geometry and kernel choice are a x nbands interpolator's: the same methods as Resampler (set_history_ptr is refused)."""
+    geometry and kernel choice are a x nbands interpolator's: the same methods as Resampler (set_history_ptr is refused).
 
-    def __init__(self, taps, nbands=4, nchan=1, fmt="CF32", device=-1):
+    `oversample=2` (include/sxfir_synthesizer_os.h): the bands arrive at fs/2 each instead of fs/4 -- what
+    Channelizer(..., oversample=2) hands out -- and the prototype is a x2 interpolator's with the /4 band edge
+    (design_lowpass(ntaps, nbands, gain=2)); the plan is a x(nbands // oversample) interpolator in everything about the stream."""
+
+    def __init__(self, taps, nbands=4, nchan=1, fmt="CF32", device=-1, oversample=1):
         self._lib = load_sxfir()
         self._plan = C.c_void_p()
         taps = np.ascontiguousarray(taps, dtype=np.float32)
-        self.mode, self.ratio, self.nbands, self.nchan, self.fmt, self.ntaps = INTERPOLATE, int(nbands), int(nbands), int(nchan), _FMT[fmt], taps.size
-        self._ck(self._lib.sxfir_create_synthesizer(C.byref(self._plan), taps.ctypes.data_as(C.c_void_p), taps.size, int(nbands),
-                                                    int(nchan), self.fmt, int(device)))
+        self.mode, self.nbands, self.nchan, self.fmt, self.ntaps = INTERPOLATE, int(nbands), int(nchan), _FMT[fmt], taps.size
+        if int(oversample) == 1:
+            self.ratio = int(nbands)
+            self._ck(self._lib.sxfir_create_synthesizer(C.byref(self._plan), taps.ctypes.data_as(C.c_void_p), taps.size, int(nbands),
+                                                        int(nchan), self.fmt, int(device)))
+        else:
+            self.ratio = int(nbands) // int(oversample) if int(oversample) > 0 else 0
+            self._ck(self._lib.sxfir_create_synthesizer_os(C.byref(self._plan), taps.ctypes.data_as(C.c_void_p), taps.size, int(nbands),
+                                                           int(oversample), int(nchan), self.fmt, int(device)))
 
     @property
     def bands(self):
@@ -448,12 +458,19 @@ class Synthesizer(_Plan):
         self._ck(self._lib.sxfir_plan_synthesis_bands(self._plan, C.byref(n)))
         return n.value
 
+    @property
+    def oversampling(self):
+        """sxfir_plan_synthesis_oversampling: 1 for the critically sampled plan, 2 for the oversampled one."""
+        n = C.c_int()
+        self._ck(self._lib.sxfir_plan_synthesis_oversampling(self._plan, C.byref(n)))
+        return n.value
+
     def set_tx_threshold(self, threshold2):
         self._ck(self._lib.sxfir_set_tx_threshold(self._plan, float(threshold2)))
 
     def process_ptr(self, in_ptr, n_in, in_stride, band_stride, out_ptr, out_stride, stream=0):
         """sxfir_synthesize: band k of channel c is read at in_ptr + c * in_stride + k * band_stride (samples of the input format),
-        n_in inputs PER BAND; returns the wideband outputs per channel (4 n_in)."""
+        n_in inputs PER BAND; returns the wideband outputs per channel (ratio x n_in)."""
         n_out = C.c_size_t()
         self._ck(self._lib.sxfir_synthesize(self._plan, C.c_void_p(in_ptr), n_in, in_stride, band_stride, C.c_void_p(out_ptr), out_stride,
                                             C.byref(n_out), C.c_void_p(stream)))
@@ -461,8 +478,8 @@ class Synthesizer(_Plan):
 
     def process(self, x, out=None):
         """x: CUDA tensor [nbands, n] or [nchan, nbands, n], possibly strided between bands and channels; complex64 (CF32 and S32
-        plans) or int32 words (CF16: half pairs).  Returns [nbands * n], or [nchan, nbands * n] for a 3-D x: complex64, int32 words
-        (CF16) or int32 wire words [.., nbands * n, 2] (S32).  A caller-given `out` of that shape (or longer rows) supplies its own
+        plans) or int32 words (CF16: half pairs).  Returns [ratio * n], or [nchan, ratio * n] for a 3-D x: complex64, int32 words
+        (CF16) or int32 wire words [.., ratio * n, 2] (S32).  A caller-given `out` of that shape (or longer rows) supplies its own
         channel stride."""
         import torch
         squeeze = x.dim() == 2

@@ -2,7 +2,8 @@
 
     python3 tools/shipped_isa.py [substring of the kernel name] [--json]
 
-(`chan4` lists the channelizer kernels of DESIGN.md 5.6, `chan4x2` the oversampled channelizer's of 5.8, `synthesis` the synthesizer's.)
+(`chan4` lists the channelizer kernels of DESIGN.md 5.6, `chan4x2` the oversampled channelizer's of 5.8, `synthesis` the synthesizer's,
+`synthesis4x2` the oversampled synthesizer's of 5.9.)
 
 Registers / LDS / scratch come from the code object's metadata notes, instruction counts from its disassembly:
 v_pk_fma_f32, ds_read_b128, global_load_lds_dwordx4 (and how many of those carry `nt`), s_barrier, v_mfma, DPP and
