@@ -1,5 +1,5 @@
 // The 4-band channelizer of the C ABI (include/sxfir_channelizer.h): plan creation and the streaming entry point.  The plan is
-// of KIND_CHANNELIZER: a /4 decimator in everything about the stream, created through the frame of sxfir_plan.hip.h -- the kernel
+// of KIND_CHANNELIZER: a /4 decimator in everything about the stream, created by create_band_plan (sxfir_plan.hip.h) -- the kernel
 // table gives it chan4_kernel and chan_generic_kernel, decim_geom / launch_decim (sxfir_launch.hip.h) choose between the two per
 // call, the state entry points take it as it is; sxfir_decimate and its kin refuse it (check_io).  sxfir_channelize is its own
 // argument checks in front of stream_call.  Included by sxfir.hip last; not a stand-alone translation unit.
@@ -11,20 +11,7 @@ int sxfir_channelizer_abi_version(void) { return SXFIR_CHANNELIZER_ABI_VERSION; 
 
 int sxfir_create_channelizer(sxfir_plan **out, const float *taps, int ntaps, int nbands, int nchan, int fmt, int device)
 {
-    if (int rc = check_create_args(out, taps, SXFIR_DECIMATE, ntaps, "nbands", nbands, nchan, fmt)) return rc;
-    if (nbands != 4)
-        return fail(SXFIR_EUNSUPPORTED, "channelizer: 4 bands only (the twiddles of %d bands are not exact: no rounding rule for them)", nbands);
-    if (ntaps % nbands) return fail(SXFIR_EINVAL, "channelizer needs ntaps %% nbands == 0 (%d, %d)", ntaps, nbands);
-    sxfir_plan *p = nullptr;      // critically sampled: everything about the stream is a /nbands decimator's
-    if (int rc = new_plan(&p, KIND_CHANNELIZER, SXFIR_DECIMATE, ntaps, nbands, nchan, fmt, device)) return rc;
-    p->hist_len = ntaps;                                    // (a multiple of 4)
-    p->ext_tiled = fmt == SXFIR_CF32 && ntaps == 128;
-    // the numeric contract of a branch sum: one chain per phase, no tree, no rotation
-    p->jsplit = 1;
-    p->cw = 1;
-    resolve_kernels(p);
-    query_occupancy(&p->occ_ext, p->k.chan4, 64);
-    return plan_to_device(out, p, taps, (size_t)ntaps, nullptr);      // (no second tap table)
+    return create_band_plan(out, KIND_CHANNELIZER, "channelizer", taps, ntaps, nbands, 1, nchan, fmt, device);   // critically sampled
 }
 
 int sxfir_plan_bands(const sxfir_plan *p, int *nbands)

@@ -80,7 +80,7 @@ static int launch(void (*kernel)(P...), dim3 grid, unsigned threads, hipStream_t
 // once.  One statement of it for launch_decim / launch_interp and for sxfir_launch_geometry (tools/sizebench.py, the Device's
 // log line for plans that fall to the generic kernels).
 struct LaunchGeom {
-    int kind;                 // GEOM_*
+    int kind;                 // GEOM_* (sxfir_plan.hip.h)
     const char *kernel;
     long long tile_out;       // decimator: outputs per tile; interpolator: inputs per tile
     long long n_tiles;        // per channel
@@ -89,7 +89,6 @@ struct LaunchGeom {
     int split;                // work items per tile ((tile, block) dealing of decim_blocks_kernel), else 1
     int phase_blocks;         // CF16 interpolator tile kernel: workgroups that share a tile, one per phase block (x48, x96: 3), else 1
 };
-enum { GEOM_GENERIC = 0, GEOM_MULTI = 1, GEOM_WIDE = 2, GEOM_TILE = 3, GEOM_IPASS = 4, GEOM_ITILE = 5, GEOM_CX = 6, GEOM_CHAN4 = 7, GEOM_SYN4 = 8, GEOM_CHAN4X2 = 9, GEOM_SYN4X2 = 10 };
 
 // The strided-pass constants of the /4 kernels: `groups` waves per channel over n_tiles tiles (sched 0: XCD-blocked strided passes,
 // 1: one contiguous run per wave, else plain strided passes), worked out here so that a wave's prologue has no integer division
@@ -150,26 +149,18 @@ static long long first_offset(const sxfir_plan *p)
 // `aligned`: stores_aligned() of the call
 static LaunchGeom decim_geom(const sxfir_plan *p, long long n_out, long long first, bool aligned)
 {
-    const bool chan = p->kind == KIND_CHANNELIZER;
-    const bool chan_os = chan && p->oversample == 2;
-    LaunchGeom g{GEOM_GENERIC, chan_os ? "chan4x2_generic_kernel" : chan ? "chan_generic_kernel" : p->kind == KIND_COMPLEX ? "decim_cx_generic_kernel" : "decim_generic_kernel", 256,
+    const BandForm *f = p->form;          // channelizer plans
+    LaunchGeom g{GEOM_GENERIC, f ? f->generic : p->kind == KIND_COMPLEX ? "decim_cx_generic_kernel" : "decim_generic_kernel", 256,
                  (n_out + 255) / 256, (n_out + 255) / 256, (long long)p->compute_units * 8, 1, 1};
     const long long CU = p->compute_units;
     const bool want = p->kernel != SXFIR_KERNEL_GENERIC && first == 0;
-    if (chan_os) {
-        // 2x oversampled channelizer (ratio 2): chan4x2_kernel for 4 bands x 128 taps on CF32, tiles of 1024 outputs PER BAND = 2048
-        // inputs.  `first == 0` says the call starts on an output; the tiled kernel's lane map also needs that output's index to be
-        // EVEN, i.e. a stream position that is a multiple of 4.  Generations as for chan4_kernel
-        if (p->ext_tiled && want && aligned && p->consumed % 4 == 0) {
-            set_tiles(g, GEOM_CHAN4X2, "chan4x2_kernel", n_out, 1024, CU * p->occ_ext);
-            g.groups = clamp_groups(g.resident * generations(p, g.n_tiles, g.resident, true) / p->nchan, g.n_tiles);
-        }
-    } else if (p->ext_tiled && want && aligned) {
-        // complex taps: decim4_cx_kernel for /4 x 128 on CF32; channelizer: chan4_kernel for 4 bands x 128 taps on CF32, tiles of 512
-        // outputs PER BAND; the generic kernel of the kind for everything else.  Both on the wide kernel's frame: its sixteen
-        // generations of waves at the sizes they were measured at, fewer while that would leave a wave under four tiles
-        // (generations(): a small call is one strided pass of resident waves)
-        set_tiles(g, chan ? GEOM_CHAN4 : GEOM_CX, chan ? "chan4_kernel" : "decim4_cx_kernel", n_out, 512, CU * p->occ_ext);
+    if (p->ext_tiled && want && aligned && (!f || p->consumed % f->start_multiple == 0)) {
+        // complex taps: decim4_cx_kernel for /4 x 128 on CF32; channelizer: the form's tiled kernel for 4 bands x 128 taps on CF32 (its
+        // tile PER BAND and the positions it starts at: BAND_FORMS); the generic kernel of the kind for everything else.  All on the wide
+        // kernel's frame: its sixteen generations of waves at the sizes they were measured at, fewer while that would leave a wave
+        // under four tiles (generations(): a small call is one strided pass of resident waves)
+        if (f) set_tiles(g, f->geom, f->tiled, n_out, f->tile, CU * p->occ_ext);
+        else set_tiles(g, GEOM_CX, "decim4_cx_kernel", n_out, 512, CU * p->occ_ext);
         g.groups = clamp_groups(g.resident * generations(p, g.n_tiles, g.resident, true) / p->nchan, g.n_tiles);
     } else if (p->multi_capable && want && aligned) {
         set_tiles(g, GEOM_MULTI, p->blocks ? "decim_blocks_kernel" : p->dense32 ? "decim_dense_kernel" : "decim_multi_kernel", n_out,
@@ -195,17 +186,13 @@ static LaunchGeom decim_geom(const sxfir_plan *p, long long n_out, long long fir
 static LaunchGeom interp_geom(const sxfir_plan *p, long long n_in, bool aligned, bool keyed)
 {
     if (p->kind == KIND_SYNTHESIZER) {
-        // synthesizer (sxfir_create_synthesizer): synthesis4_kernel for 4 bands x 128 taps on CF32, tiles of 256 inputs PER BAND on the x4
-        // pass kernel's frame; one thread per input index of synthesis_generic_kernel for everything else.  Small calls dealt as fewer
+        // synthesizer: the form's tiled kernel for 4 bands x 128 taps on CF32 (its tile of inputs PER BAND: BAND_FORMS; both forms start
+        // at any position); one thread per input index of the form's generic kernel for everything else.  Small calls dealt as fewer
         // generations of waves, the channelizer's rule
-        // 2x oversampled (sxfir_create_synthesizer_os, ratio 2): synthesis4x2_kernel, tiles of 512 inputs PER BAND, and
-        // synthesis_os_generic_kernel.  The tiled kernel takes a call that starts at any per-band index: the start's parity is its argument
-        const bool os = p->oversample == 2;
-        LaunchGeom s{GEOM_GENERIC, os ? "synthesis_os_generic_kernel" : "synthesis_generic_kernel", 256, (n_in + 255) / 256, (n_in + 255) / 256,
-                     (long long)p->compute_units * 8, 1, 1};
+        const BandForm *f = p->form;
+        LaunchGeom s{GEOM_GENERIC, f->generic, 256, (n_in + 255) / 256, (n_in + 255) / 256, (long long)p->compute_units * 8, 1, 1};
         if (p->ext_tiled && p->kernel != SXFIR_KERNEL_GENERIC && aligned) {
-            if (os) set_tiles(s, GEOM_SYN4X2, "synthesis4x2_kernel", n_in, sxfir::Syn4x2::TILE_IN, (long long)p->compute_units * p->occ_ext);
-            else set_tiles(s, GEOM_SYN4, "synthesis4_kernel", n_in, 256, (long long)p->compute_units * p->occ_ext);
+            set_tiles(s, f->geom, f->tiled, n_in, f->tile, (long long)p->compute_units * p->occ_ext);
             s.groups = clamp_groups(s.resident * generations(p, s.n_tiles, s.resident, true) / p->nchan, s.n_tiles);
         }
         return s;
@@ -347,7 +334,7 @@ static sxfir::SynTileArgs syn_tile_args(const sxfir_plan *p, const CallIO &c, co
     a.hist = (const float *)p->hist_dev;
     a.hist_out = (float *)p->hist_alt;
     a.out = (float *)c.out;
-    a.taps = p->taps_scaled_dev;                    // the phase-major table (2x oversampled: the parity-major one)
+    a.taps = p->taps_scaled_dev;                    // the phase-major table (2x oversampled: its phases are the two parities)
     a.n_in = (long long)c.n_in;
     a.in_stride = (long long)c.in_stride;
     a.band_stride = (long long)c.band_stride;
@@ -414,13 +401,14 @@ static int launch_decim(sxfir_plan *p, const CallIO &c, bool *history_done)
     const long long first = first_offset(p);
     const LaunchGeom geom = decim_geom(p, c.n_out, first, stores_aligned(p, c));
     const dim3 grid((unsigned)geom.groups, (unsigned)p->nchan);
+    const int band = p->form ? p->form->geom : GEOM_GENERIC;         // channelizer plans: which of the two forms
     if (geom.kind == GEOM_GENERIC) {
         if (p->kernel == SXFIR_KERNEL_TILED)
             return fail(SXFIR_EUNSUPPORTED,
                         "tiled kernel needs a 16-byte aligned output, an even output stride and a call that starts on "
-                        "an output boundary%s", p->kind == KIND_CHANNELIZER && p->oversample == 2 ? " of even index (a stream position that is a multiple of 4)" : "");
-        if (p->kind == KIND_CHANNELIZER && p->oversample == 2) return launch(p->k.chan4x2_generic, grid, 256, c.st, chan_os_generic_args(p, c, first));
-        if (p->kind == KIND_CHANNELIZER) return launch(p->k.chan_generic, grid, 256, c.st, chan_generic_args(p, c, first));
+                        "an output boundary%s", p->form && p->form->start_multiple == 4 ? " of even index (a stream position that is a multiple of 4)" : "");
+        if (band == GEOM_CHAN4X2) return launch(p->k.chan4x2_generic, grid, 256, c.st, chan_os_generic_args(p, c, first));
+        if (band == GEOM_CHAN4) return launch(p->k.chan_generic, grid, 256, c.st, chan_generic_args(p, c, first));
         return launch(p->k.generic, grid, 256, c.st, generic_args(p, c, first));
     }
     if (geom.n_tiles > 0x7fffffffLL) return fail(SXFIR_EINVAL, "call too large");
@@ -495,17 +483,13 @@ static int launch_synth(sxfir_plan *p, const CallIO &c, bool *history_done)
     if (geom.kind == GEOM_GENERIC) {
         if (p->kernel == SXFIR_KERNEL_TILED)
             return fail(SXFIR_EUNSUPPORTED, "tiled synthesizer needs a 16-byte aligned output and an even output stride");
-        if (p->oversample == 2) return launch(p->k.syn4x2_generic, grid, 256, c.st, syn_os_generic_args(p, c));
+        if (p->form->geom == GEOM_SYN4X2) return launch(p->k.syn4x2_generic, grid, 256, c.st, syn_os_generic_args(p, c));
         return launch(p->k.syn_generic, grid, 256, c.st, syn_generic_args(p, c));
     }
     if (geom.n_tiles > 0x7fffffffLL) return fail(SXFIR_EINVAL, "call too large");
-    if (geom.kind == GEOM_SYN4X2) {
-        if (int rc = need_tap_table(p, TAPS_PARITY2, "synthesis4x2_kernel")) return rc;
-        *history_done = true;
-        return launch(p->k.syn4x2, grid, 64, c.st, syn_os_tile_args(p, c, geom));
-    }
-    if (int rc = need_tap_table(p, TAPS_PHASE4, "synthesis4_kernel")) return rc;
+    if (int rc = need_tap_table(p, TAPS_PHASED, p->form->tiled)) return rc;
     *history_done = true;
+    if (geom.kind == GEOM_SYN4X2) return launch(p->k.syn4x2, grid, 64, c.st, syn_os_tile_args(p, c, geom));
     return launch(p->k.syn4, grid, 64, c.st, syn_tile_args(p, c, geom));
 }
 

@@ -1,8 +1,8 @@
 // Plan bookkeeping of the C ABI (include/sxfir.h): what a plan holds and which of the four kinds it is, the kernel table (which
 // instance a shape launches: the one statement of it, for the occupancy queries and the launches), the creation frame every
 // sxfir_create* goes through (argument checks, the device, the plan's common fields, the real-tap contract, the plan's device
-// memory and the one list of what to free), how sxfir_create settles a real-tap plan's flags and lays out its tap tables, and
-// the small state entry points (reset, history, position, contract).
+// memory and the one list of what to free), how sxfir_create settles a real-tap plan's flags and lays out its tap tables, the
+// one creation path of the four band plans (create_band_plan), and the small state entry points (reset, history, position, contract).
 // Included by sxfir.hip after the kernel headers; not a stand-alone translation unit.
 #pragma once
 
@@ -12,7 +12,10 @@
 // (sxfir_synthesizer_os.hip.h: KIND_SYNTHESIZER with ratio = bands / oversample).  A complex-tap plan is a decimator whose taps_dev
 // holds a[0, ntaps) then b[0, ntaps); the band kinds are a /ratio decimator and a x ratio interpolator in everything about the stream.
 enum PlanKind { KIND_REAL = 0, KIND_COMPLEX = 1, KIND_CHANNELIZER = 2, KIND_SYNTHESIZER = 3 };
-enum TapTable { TAPS_SCALED = 0, TAPS_SUBSET8 = 1, TAPS_PASS8 = 2, TAPS_BLOCKS16 = 3, TAPS_PHASE4 = 4, TAPS_PARITY2 = 5 };
+enum TapTable { TAPS_SCALED = 0, TAPS_SUBSET8 = 1, TAPS_PASS8 = 2, TAPS_BLOCKS16 = 3, TAPS_PHASED = 4 };
+
+// Which kernel family a call launches (LaunchGeom::kind, sxfir_launch.hip.h)
+enum { GEOM_GENERIC = 0, GEOM_MULTI = 1, GEOM_WIDE = 2, GEOM_TILE = 3, GEOM_IPASS = 4, GEOM_ITILE = 5, GEOM_CX = 6, GEOM_CHAN4 = 7, GEOM_SYN4 = 8, GEOM_CHAN4X2 = 9, GEOM_SYN4X2 = 10 };
 
 // One typed kernel pointer per launch-argument family, and a plan's kernels: resolved once by the plan's creator
 // (resolve_kernels below), read by the occupancy queries there and by the launches (sxfir_launch.hip.h).
@@ -42,6 +45,14 @@ struct KernelTable {
     SynGenericFn syn_generic;    // ... and synthesis_generic_kernel, which every synthesizer plan has INSTEAD of `generic`
     SynOsTileFn syn4x2;          // 2x oversampled synthesizer plans (include/sxfir_synthesizer_os.h): synthesis4x2_kernel (4 bands x 128 taps, CF32) ...
     SynOsGenericFn syn4x2_generic;     // ... and synthesis_os_generic_kernel, which every such plan has INSTEAD of `generic` and `syn_generic`
+};
+
+// What the geometry and launch code needs to know of a band plan's pair of kernels (BAND_FORMS below; resolve_kernels picks one)
+struct BandForm {
+    const char *tiled, *generic;   // the kernels' names, as sxfir_launch_geometry reports them
+    int geom;                      // GEOM_* of the tiled kernel: also names the form where the typed pointers and argument structs differ
+    int tile;                      // the tiled kernel's tile PER BAND: outputs of a channelizer, inputs of a synthesizer
+    int start_multiple;            // the tiled kernel takes a call that starts at a stream position that is a multiple of this (1: any)
 };
 
 struct sxfir_plan {
@@ -105,8 +116,8 @@ struct sxfir_plan {
     int tap_table;            // TAPS_SCALED: taps * 2^-31 (exact) in tap order, for the /4 scalar-tap kernels on S32 wire words;
                               // TAPS_SUBSET8: the subset-major table of decim_dense_kernel<8, ..., SUBSET> (times 2^-31 for S32 plans);
                               // TAPS_PASS8: the pass-major table of interp8_pass_kernel (pass (c, p) at 64 (2c + p), (jj, rr) at 4 jj + rr).
-                              // TAPS_PHASE4: the phase-major table of synthesis4_kernel (h[4j + r] at (ntaps / 4) r + j).
-                              // TAPS_PARITY2: the parity-major table of synthesis4x2_kernel (h[2i + q] at (ntaps / 2) q + i).
+                              // TAPS_PHASED: the phase-major table of synthesis4_kernel and synthesis4x2_kernel (h[ratio j + r] at
+                              // (ntaps / ratio) r + j: four phases, or the two output parities of the oversampled plan).
                               // Every launch that hands taps_scaled_dev to a kernel checks this first (need_tap_table).
     bool ipass;               // x8, 256 taps, CF32: interp8_pass_kernel (scalar taps, four passes per tile)
     int occ_ipass;
@@ -120,6 +131,7 @@ struct sxfir_plan {
     void *hist_dev;        // current history: nchan * hist_len samples
     void *hist_alt;        // the tile kernel writes the next history here, then the two swap
     KernelTable k;         // the instances this plan launches (null: none in this build for that family)
+    const BandForm *form;  // the band kinds: what decim_geom / interp_geom and the launches read of the plan's two kernels; else null
     long long consumed, produced;
 };
 
@@ -276,29 +288,41 @@ static SynOsGenericFn synthesis_os_generic_kernel_for(int fmt)
     return synthesis_os_generic_kernel<CF32, S32>;
 }
 
+// The four band forms, [synthesizer][oversampled].  chan4_kernel: tiles of 512 outputs per band.  chan4x2_kernel (ratio 2): 1024
+// outputs per band = 2048 inputs; its lane map needs the call's first output to have an EVEN index, i.e. a stream position that is
+// a multiple of 4 (every position of the /2 raster starts on an output).  synthesis4_kernel: 256 inputs per band on the x4 pass
+// kernel's frame.  synthesis4x2_kernel: any per-band start index -- the start's parity is its argument.
+static const BandForm BAND_FORMS[2][2] = {
+    {{"chan4_kernel", "chan_generic_kernel", GEOM_CHAN4, 512, 1}, {"chan4x2_kernel", "chan4x2_generic_kernel", GEOM_CHAN4X2, 1024, 4}},
+    {{"synthesis4_kernel", "synthesis_generic_kernel", GEOM_SYN4, 256, 1},
+     {"synthesis4x2_kernel", "synthesis_os_generic_kernel", GEOM_SYN4X2, sxfir::Syn4x2::TILE_IN, 1}}};
+
 // The plan's kernels, from its kind and the capability flags its creator has settled (the profiling knobs included)
 static void resolve_kernels(sxfir_plan *p)
 {
     KernelTable &k = p->k;
     k = KernelTable{};
-    if (p->kind == KIND_CHANNELIZER && p->oversample == 2) {
-        k.chan4x2_generic = chan4x2_generic_kernel_for(p->fmt);
-        if (p->ext_tiled) k.chan4x2 = sxfir::chan4x2_kernel;
-        return;
-    }
-    if (p->kind == KIND_CHANNELIZER) {
-        k.chan_generic = chan_generic_kernel_for(p->fmt);
-        if (p->ext_tiled) k.chan4 = sxfir::chan4_kernel;
-        return;
-    }
-    if (p->kind == KIND_SYNTHESIZER && p->oversample == 2) {
-        k.syn4x2_generic = synthesis_os_generic_kernel_for(p->fmt);
-        if (p->ext_tiled) k.syn4x2 = sxfir::synthesis4x2_kernel;
-        return;
-    }
-    if (p->kind == KIND_SYNTHESIZER) {
-        k.syn_generic = synthesis_generic_kernel_for(p->fmt);
-        if (p->ext_tiled) k.syn4 = sxfir::synthesis4_kernel;
+    p->form = nullptr;
+    if (p->kind == KIND_CHANNELIZER || p->kind == KIND_SYNTHESIZER) {
+        p->form = &BAND_FORMS[p->kind == KIND_SYNTHESIZER][p->oversample == 2];
+        switch (p->form->geom) {            // every band plan has its form's generic kernel INSTEAD of `generic`
+        case GEOM_CHAN4:
+            k.chan_generic = chan_generic_kernel_for(p->fmt);
+            if (p->ext_tiled) k.chan4 = sxfir::chan4_kernel;
+            break;
+        case GEOM_CHAN4X2:
+            k.chan4x2_generic = chan4x2_generic_kernel_for(p->fmt);
+            if (p->ext_tiled) k.chan4x2 = sxfir::chan4x2_kernel;
+            break;
+        case GEOM_SYN4:
+            k.syn_generic = synthesis_generic_kernel_for(p->fmt);
+            if (p->ext_tiled) k.syn4 = sxfir::synthesis4_kernel;
+            break;
+        case GEOM_SYN4X2:
+            k.syn4x2_generic = synthesis_os_generic_kernel_for(p->fmt);
+            if (p->ext_tiled) k.syn4x2 = sxfir::synthesis4x2_kernel;
+            break;
+        }
         return;
     }
     k.generic = generic_kernel(p->mode, p->fmt, p->kind == KIND_COMPLEX);
@@ -456,6 +480,61 @@ static int plan_to_device(sxfir_plan **out, sxfir_plan *p, const float *taps, si
         return fail(SXFIR_EHIP, "plan allocation failed: %s", hipGetErrorString(e));
     }
     *out = p;
+    return SXFIR_OK;
+}
+
+// The one creation path of the four band plans (sxfir_create_channelizer, sxfir_create_synthesizer and their _os forms, in
+// their own headers): `kind` KIND_CHANNELIZER or KIND_SYNTHESIZER, `what` the creator's name for its plan in the refusals
+// ("channelizer", "oversampled channelizer", ...), `oversample` 1 or 2 once an _os creator's own checks are through.  The plan is a
+// /ratio decimator or a x ratio interpolator, ratio = nbands / oversample, in everything about the stream.
+static int create_band_plan(sxfir_plan **out, int kind, const char *what, const float *taps, int ntaps, int nbands, int oversample,
+                            int nchan, int fmt, int device)
+{
+    const bool syn = kind == KIND_SYNTHESIZER;
+    const char *word = syn ? "synthesizer" : "channelizer";
+    const int mode = syn ? SXFIR_INTERPOLATE : SXFIR_DECIMATE;
+    if (int rc = check_create_args(out, taps, mode, ntaps, "nbands", nbands, nchan, fmt)) return rc;
+    if (nbands != 4)
+        return fail(SXFIR_EUNSUPPORTED, "%s: 4 bands only (the twiddles of %d bands are not exact: no rounding rule for them)", what, nbands);
+    if (ntaps % nbands) return fail(SXFIR_EINVAL, "%s needs ntaps %% nbands == 0 (%d, %d)", word, ntaps, nbands);
+    const int ratio = nbands / oversample;
+    sxfir_plan *p = nullptr;
+    if (int rc = new_plan(&p, kind, mode, ntaps, ratio, nchan, fmt, device)) return rc;
+    p->bands = nbands;
+    p->oversample = oversample;
+    p->ext_tiled = fmt == SXFIR_CF32 && ntaps == 128;
+    const int jt = ntaps / ratio;                           // a synthesizer's taps per phase (oversampled: per output parity)
+    std::vector<float> phased(syn ? (size_t)ntaps : 0);     // a synthesizer's second tap table
+    if (syn) {
+        p->hist_len = nbands * ((jt + 1) & ~1);             // per channel: a x ratio interpolator's history for every band, band k's at k * hist_len / 4
+        real_tap_contract(p);                               // a phase's sum: the real-tap interpolator's
+        // the phase-major table of the tiled kernels: h[ratio j + r] at jt r + j
+        p->tap_table = TAPS_PHASED;
+        for (int r = 0; r < ratio; ++r)
+            for (int j = 0; j < jt; ++j) phased[(size_t)(jt * r + j)] = taps[ratio * j + r];
+    } else {
+        p->hist_len = ntaps;                                // (a multiple of 4)
+        // the numeric contract of a branch sum: one chain per phase, no tree, no rotation
+        p->jsplit = 1;
+        p->cw = 1;
+    }
+    resolve_kernels(p);
+    if (p->form->geom == GEOM_SYN4X2) p->occ_ext = 5;       // (where the runtime has no answer; its answer replaces it)
+    const KernelTable &k = p->k;                            // the form's tiled kernel: at most one of the four is set
+    query_occupancy(&p->occ_ext, k.chan4 ? (const void *)k.chan4 : k.chan4x2 ? (const void *)k.chan4x2 : k.syn4 ? (const void *)k.syn4 : (const void *)k.syn4x2, 64);
+    return plan_to_device(out, p, taps, (size_t)ntaps, syn ? phased.data() : nullptr);
+}
+
+// The _os creators' own argument, checked behind check_create_args and in front of create_band_plan: its range, and the two values
+// version 1 does not take (`word`: "channelizer" / "synthesizer").  A band count that create_band_plan refuses is left to it: that
+// refusal has always come in front of the two here.
+static int check_oversample(const char *word, int nbands, int oversample)
+{
+    if (oversample < 1 || oversample > 4096) return fail(SXFIR_EINVAL, "oversample %d out of range", oversample);
+    if (nbands != 4) return SXFIR_OK;
+    if (oversample == 1)
+        return fail(SXFIR_EUNSUPPORTED, "oversample 1 is the critically sampled %s: sxfir_create_%s (include/sxfir_%s.h)", word, word, word);
+    if (oversample != 2) return fail(SXFIR_EUNSUPPORTED, "oversampled %s: oversample 2 only (%d asked for)", word, oversample);
     return SXFIR_OK;
 }
 

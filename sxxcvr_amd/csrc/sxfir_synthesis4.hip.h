@@ -102,17 +102,39 @@ __device__ __forceinline__ void syn4_steps(std::integer_sequence<int, Ts...>, co
     (syn4_step<Ts>(win[Ts], hs, acc), ...);
 }
 
-// The butterflies of one chunk (two samples) of the four band images, in place.
-__device__ __forceinline__ void syn4_butterfly_chunk(f32x4 *img, int c)
+// The butterflies of one chunk (two samples) of the four band images of PITCH slots each, in place.
+template <int PITCH>
+__device__ __forceinline__ void syn_butterfly_chunk(f32x4 *img, int c)
 {
-    const f32x4 x0 = img[c], x1 = img[Syn4::IMG + c], x2 = img[2 * Syn4::IMG + c], x3 = img[3 * Syn4::IMG + c];
+    const f32x4 x0 = img[c], x1 = img[PITCH + c], x2 = img[2 * PITCH + c], x3 = img[3 * PITCH + c];
     f32x2 e[4], o[4];
     chan4_butterfly(__builtin_shufflevector(x0, x0, 0, 1), __builtin_shufflevector(x1, x1, 0, 1), __builtin_shufflevector(x2, x2, 0, 1),
                     __builtin_shufflevector(x3, x3, 0, 1), e);
     chan4_butterfly(__builtin_shufflevector(x0, x0, 2, 3), __builtin_shufflevector(x1, x1, 2, 3), __builtin_shufflevector(x2, x2, 2, 3),
                     __builtin_shufflevector(x3, x3, 2, 3), o);
 #pragma unroll
-    for (int r = 0; r < 4; ++r) img[Syn4::IMG * r + c] = (f32x4){e[r].x, e[r].y, o[r].x, o[r].y};
+    for (int r = 0; r < 4; ++r) img[PITCH * r + c] = (f32x4){e[r].x, e[r].y, o[r].x, o[r].y};
+}
+
+// The pass kernel's tile schedule: in pass i the G workgroups cover tiles [iG, (i+1)G), the workgroups of one XCD a contiguous block
+// of them (a tile's history is its neighbour's tail: found in that XCD's L2).  Workgroup `b`'s first tile.  (Unsigned % 8, / 8:
+// xcd_blocked's signed form is other code.)
+__device__ __forceinline__ int syn_first_tile(unsigned b, int G)
+{
+    return (G % 8 == 0) ? (int)(b % 8) * (G / 8) + (int)(b / 8) : (int)b;
+}
+
+// A tap set of N SGPR pairs, set `index` of the table at `tq0`, behind an opaque pointer (hoisted, a tile's sets would need 128 SGPRs
+// at once): the first set of a tile waits for nothing, a later one for `prev`, a result of the pass before.
+template <int N>
+__device__ __forceinline__ void syn_load_tap_set(f32x2 (&hs)[N], const __attribute__((address_space(4))) f32x2 *tq0, int index, bool first, const f32x2 &prev)
+{
+    unsigned long long tp = (unsigned long long)tq0;
+    if (first) asm volatile("" : "+s"(tp));
+    else asm volatile("" : "+s"(tp) : "v"(prev));
+    const __attribute__((address_space(4))) f32x2 *tq = (const __attribute__((address_space(4))) f32x2 *)tp;
+#pragma unroll
+    for (int m = 0; m < N; ++m) hs[m] = tq[N * index + m];
 }
 
 __global__ __launch_bounds__(64) void synthesis4_kernel(const SynTileArgs a)
@@ -130,10 +152,8 @@ __global__ __launch_bounds__(64) void synthesis4_kernel(const SynTileArgs a)
     const float *hist = a.hist + 2 * a.hist_stride * ch;
     float *out = a.out + 2 * a.out_stride * ch;
 
-    // the pass kernel's tile schedule: in pass i the G workgroups cover tiles [iG, (i+1)G), the workgroups of one XCD a contiguous
-    // block of them (a tile's 32-sample history is its neighbour's tail: found in that XCD's L2)
     const int G = a.n_groups;
-    const int first_tile = (G % 8 == 0) ? (int)(blockIdx.x % 8) * (G / 8) + (int)(blockIdx.x / 8) : (int)blockIdx.x;
+    const int first_tile = syn_first_tile(blockIdx.x, G);
     if (first_tile >= a.n_tiles) return;
     if (first_tile == (a.n_tiles - 1) % G && lane < C::HIST) {
         float *ho = a.hist_out + 2 * a.hist_stride * ch;
@@ -204,9 +224,9 @@ __global__ __launch_bounds__(64) void synthesis4_kernel(const SynTileArgs a)
         const long long q0 = (long long)tile * C::TILE_IN;
 
         // ---- x -> v in place, once per sample: chunks lane, 64 + lane and (lanes 0..15) 128 + lane of the four images
-        syn4_butterfly_chunk(lds, lane);
-        syn4_butterfly_chunk(lds, 64 + lane);
-        if (lane < C::CHUNKS - 128) syn4_butterfly_chunk(lds, 128 + lane);
+        syn_butterfly_chunk<C::IMG>(lds, lane);
+        syn_butterfly_chunk<C::IMG>(lds, 64 + lane);
+        if (lane < C::CHUNKS - 128) syn_butterfly_chunk<C::IMG>(lds, 128 + lane);
 
         const int next = tile + G;
         counted = false;
@@ -227,15 +247,7 @@ __global__ __launch_bounds__(64) void synthesis4_kernel(const SynTileArgs a)
                 if (next < a.n_tiles) counted = stage(next);
             }
             f32x2 hs[16];
-            {
-                // (an opaque pointer per pass: hoisted, the four tap sets would need 128 SGPRs at once)
-                unsigned long long tp = (unsigned long long)tq0;
-                if (r == 0) asm volatile("" : "+s"(tp));
-                else asm volatile("" : "+s"(tp) : "v"(prev));
-                const __attribute__((address_space(4))) f32x2 *tq = (const __attribute__((address_space(4))) f32x2 *)tp;
-#pragma unroll
-                for (int m = 0; m < 16; ++m) hs[m] = tq[16 * r + m];
-            }
+            syn_load_tap_set(hs, tq0, r, r == 0, prev);      // (a set per pass)
             f32x2 acc[2][4];                                    // every chain's first FMA (rows 31 and 15) writes it
             syn4_steps(std::make_integer_sequence<int, C::NW>{}, win, hs, acc);
             f32x2 y[4];

@@ -20,7 +20,7 @@
 //     (the fifth on 32 lanes), the middle three -- rows no other tile reads -- non-temporal; a band's five are issued as soon as
 //     no later pass reads its image, two to three passes ahead of their use;
 //   * the four passes are by output RESIDUE r = n mod 4 inside the tile, in the order 0, 2, 1, 3 (a tap set serves two passes): pass r holds the 64 taps h[2i + (r & 1)] in 32 SGPR pairs
-//     (parity-major table, behind a laundered pointer), reads the lane's window -- 36 chunks -- of the image v_(r ^ 2 par) and runs
+//     (the phase-major table at ratio 2: by output parity; behind a laundered pointer), reads the lane's window -- 36 chunks -- of the image v_(r ^ 2 par) and runs
 //     the two row-half chains of its four outputs 16l + r + 4q: 256 packed FMAs, every one with a scalar tap; P0 + P1; residues
 //     2c, 2c + 1 of q are one 16-byte chunk of the lane's line in the transposition buffer;
 //   * `par` is the parity of the call's absolute per-band start index, a uniform argument: it only selects which image a pass
@@ -94,19 +94,6 @@ __device__ __forceinline__ void syn4x2_steps(std::integer_sequence<int, Ts...>, 
     (syn4x2_step<Ts, RH>(win[Ts], hs, acc), ...);
 }
 
-// The butterflies of one chunk (two samples) of the four band images, in place (syn4_butterfly_chunk on this image's pitch).
-__device__ __forceinline__ void syn4x2_butterfly_chunk(f32x4 *img, int c)
-{
-    const f32x4 x0 = img[c], x1 = img[Syn4x2::IMG + c], x2 = img[2 * Syn4x2::IMG + c], x3 = img[3 * Syn4x2::IMG + c];
-    f32x2 e[4], o[4];
-    chan4_butterfly(__builtin_shufflevector(x0, x0, 0, 1), __builtin_shufflevector(x1, x1, 0, 1), __builtin_shufflevector(x2, x2, 0, 1),
-                    __builtin_shufflevector(x3, x3, 0, 1), e);
-    chan4_butterfly(__builtin_shufflevector(x0, x0, 2, 3), __builtin_shufflevector(x1, x1, 2, 3), __builtin_shufflevector(x2, x2, 2, 3),
-                    __builtin_shufflevector(x3, x3, 2, 3), o);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) img[Syn4x2::IMG * r + c] = (f32x4){e[r].x, e[r].y, o[r].x, o[r].y};
-}
-
 __global__ __launch_bounds__(64) void synthesis4x2_kernel(const SynOsTileArgs ao)
 {
     using C = Syn4x2;
@@ -126,10 +113,8 @@ __global__ __launch_bounds__(64) void synthesis4x2_kernel(const SynOsTileArgs ao
     const float *hist = a.hist + 2 * a.hist_stride * ch;
     float *out = a.out + 2 * a.out_stride * ch;
 
-    // synthesis4_kernel's tile schedule: in pass i the G workgroups cover tiles [iG, (i+1)G), the workgroups of one XCD a contiguous
-    // block of them (a tile's 64-sample history is its neighbour's tail: found in that XCD's L2)
     const int G = a.n_groups;
-    const int first_tile = (G % 8 == 0) ? (int)(blockIdx.x % 8) * (G / 8) + (int)(blockIdx.x / 8) : (int)blockIdx.x;
+    const int first_tile = syn_first_tile(blockIdx.x, G);
     if (first_tile >= a.n_tiles) return;
     if (first_tile == (a.n_tiles - 1) % G) {
         float *ho = a.hist_out + 2 * a.hist_stride * ch;
@@ -201,8 +186,8 @@ __global__ __launch_bounds__(64) void synthesis4x2_kernel(const SynOsTileArgs ao
 
         // ---- x -> v in place, once per sample: chunks lane, 64 + lane, .. and (lanes 0..31) 256 + lane of the four images
 #pragma unroll
-        for (int i = 0; i < C::NBFLY - 1; ++i) syn4x2_butterfly_chunk(lds, 64 * i + lane);
-        if (lane < C::CHUNKS - 64 * (C::NBFLY - 1)) syn4x2_butterfly_chunk(lds, 64 * (C::NBFLY - 1) + lane);
+        for (int i = 0; i < C::NBFLY - 1; ++i) syn_butterfly_chunk<C::IMG>(lds, 64 * i + lane);
+        if (lane < C::CHUNKS - 64 * (C::NBFLY - 1)) syn_butterfly_chunk<C::IMG>(lds, 64 * (C::NBFLY - 1) + lane);
 
         const int next = tile + G;
         counted = false;
@@ -213,15 +198,7 @@ __global__ __launch_bounds__(64) void synthesis4x2_kernel(const SynOsTileArgs ao
 #pragma unroll
         for (int pi = 0; pi < C::NBANDS; ++pi) {
             const int r = 2 * (pi & 1) + (pi >> 1);
-            if ((pi & 1) == 0) {
-                // (an opaque pointer per pair of passes: hoisted, the two tap sets would need 128 SGPRs at once)
-                unsigned long long tp = (unsigned long long)tq0;
-                if (pi == 0) asm volatile("" : "+s"(tp));
-                else asm volatile("" : "+s"(tp) : "v"(prev));
-                const __attribute__((address_space(4))) f32x2 *tq = (const __attribute__((address_space(4))) f32x2 *)tp;
-#pragma unroll
-                for (int m = 0; m < 32; ++m) hs[m] = tq[32 * (r & 1) + m];
-            }
+            if ((pi & 1) == 0) syn_load_tap_set(hs, tq0, r & 1, pi == 0, prev);      // (a set per pair of passes)
             // the lane's window of v_(r ^ flip): image samples 8l .. 8l + 71 -> chunks 4l .. 4l + 35
             f32x4 win[C::NW];
             {

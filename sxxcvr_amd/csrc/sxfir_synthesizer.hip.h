@@ -1,5 +1,5 @@
 // The 4-band synthesizer of the C ABI (include/sxfir_synthesizer.h): plan creation and the streaming entry point.  The plan is
-// of KIND_SYNTHESIZER: a x4 interpolator in everything about the stream, created through the frame of sxfir_plan.hip.h -- the kernel
+// of KIND_SYNTHESIZER: a x4 interpolator in everything about the stream, created by create_band_plan (sxfir_plan.hip.h) -- the kernel
 // table gives it synthesis4_kernel and synthesis_generic_kernel, interp_geom / launch_synth (sxfir_launch.hip.h) choose between the
 // two per call, the state entry points take it as it is; sxfir_interpolate and its kin refuse it (check_io).  sxfir_synthesize is
 // its own argument checks in front of stream_call.  Included by sxfir.hip last; not a stand-alone translation unit.
@@ -11,25 +11,7 @@ int sxfir_synthesizer_abi_version(void) { return SXFIR_SYNTHESIZER_ABI_VERSION; 
 
 int sxfir_create_synthesizer(sxfir_plan **out, const float *taps, int ntaps, int nbands, int nchan, int fmt, int device)
 {
-    if (int rc = check_create_args(out, taps, SXFIR_INTERPOLATE, ntaps, "nbands", nbands, nchan, fmt)) return rc;
-    if (nbands != 4)
-        return fail(SXFIR_EUNSUPPORTED, "synthesizer: 4 bands only (the twiddles of %d bands are not exact: no rounding rule for them)", nbands);
-    if (ntaps % nbands) return fail(SXFIR_EINVAL, "synthesizer needs ntaps %% nbands == 0 (%d, %d)", ntaps, nbands);
-    sxfir_plan *p = nullptr;      // critically sampled: everything about the stream is a x nbands interpolator's
-    if (int rc = new_plan(&p, KIND_SYNTHESIZER, SXFIR_INTERPOLATE, ntaps, nbands, nchan, fmt, device)) return rc;
-    const int jt = ntaps / nbands;                          // taps per phase
-    p->hist_len = nbands * ((jt + 1) & ~1);                 // per channel: an interpolator's history for every band, band k's at k * hist_len / 4
-    p->ext_tiled = fmt == SXFIR_CF32 && ntaps == 128;
-    p->tap_table = TAPS_PHASE4;
-    real_tap_contract(p);                                   // a phase's sum: the real-tap interpolator's
-    resolve_kernels(p);
-    query_occupancy(&p->occ_ext, p->k.syn4, 64);
-
-    // the phase-major table of synthesis4_kernel: h[4j + r] at jt r + j
-    std::vector<float> phased((size_t)ntaps);
-    for (int r = 0; r < nbands; ++r)
-        for (int j = 0; j < jt; ++j) phased[(size_t)(jt * r + j)] = taps[nbands * j + r];
-    return plan_to_device(out, p, taps, (size_t)ntaps, phased.data());
+    return create_band_plan(out, KIND_SYNTHESIZER, "synthesizer", taps, ntaps, nbands, 1, nchan, fmt, device);   // critically sampled
 }
 
 int sxfir_plan_synthesis_bands(const sxfir_plan *p, int *nbands)

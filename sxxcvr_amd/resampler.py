@@ -142,7 +142,7 @@ class Geometry(C.Structure):
 
 class _Plan:
     """What every sxfir_plan answers, whichever entry point created it: the stream state, the numeric contract, the launch
-    geometry and the kernel choice.  Resampler, Channelizer and Synthesizer create the plan (self._plan in self._lib) and add their passes."""
+    geometry and the kernel choice.  Resampler and the band plans (Channelizer, Synthesizer) create the plan (self._plan in self._lib) and add their passes."""
 
     _plan = None
 
@@ -349,7 +349,45 @@ class Resampler(_Plan):
         return y[0] if squeeze else y
 
 
-class Channelizer(_Plan):
+class _BandPlan(_Plan):
+    """What Channelizer and Synthesizer share: the constructor (a critically sampled plan through the first creator, an oversampled
+    one through the second) and the plan's own band count and oversampling factor."""
+
+    _mode = None
+    _create = (None, None)      # sxfir_create_<what>, sxfir_create_<what>_os
+    _query = (None, None)       # the queries behind `bands` and `oversampling`
+
+    def __init__(self, taps, nbands=4, nchan=1, fmt="CF32", device=-1, oversample=1):
+        self._lib = load_sxfir()
+        self._plan = C.c_void_p()
+        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        nbands, oversample = int(nbands), int(oversample)
+        self.mode, self.nbands, self.nchan, self.fmt, self.ntaps = self._mode, nbands, int(nchan), _FMT[fmt], taps.size
+        head = (C.byref(self._plan), taps.ctypes.data_as(C.c_void_p), taps.size, nbands)
+        if oversample == 1:
+            self.ratio = nbands
+            self._ck(getattr(self._lib, self._create[0])(*head, int(nchan), self.fmt, int(device)))
+        else:
+            self.ratio = nbands // oversample if oversample > 0 else 0
+            self._ck(getattr(self._lib, self._create[1])(*head, oversample, int(nchan), self.fmt, int(device)))
+
+    def _answer(self, query):
+        n = C.c_int()
+        self._ck(getattr(self._lib, query)(self._plan, C.byref(n)))
+        return n.value
+
+    @property
+    def bands(self):
+        """The plan's own band count (sxfir_plan_bands / sxfir_plan_synthesis_bands)."""
+        return self._answer(self._query[0])
+
+    @property
+    def oversampling(self):
+        """1 for the critically sampled plan, 2 for the oversampled one (sxfir_plan_oversampling / sxfir_plan_synthesis_oversampling)."""
+        return self._answer(self._query[1])
+
+
+class Channelizer(_BandPlan):
     """The 4-band channelizer (include/sxfir_channelizer.h): all `nbands` sub-bands of the /nbands raster out of one wideband
     stream in one pass.  `taps`: the REAL prototype low-pass (design_lowpass(ntaps, nbands)); band k is the band that
     design_bandpass(ntaps, nbands, k, nbands) centres, at 0 Hz of its output.  Stream state, contract, geometry and kernel
@@ -359,33 +397,9 @@ class Channelizer(_Plan):
     across its whole width.  Even-time outputs have the bits of the critically sampled plan's; the plan is a /(nbands // oversample)
     decimator in everything about the stream."""
 
-    def __init__(self, taps, nbands=4, nchan=1, fmt="CF32", device=-1, oversample=1):
-        self._lib = load_sxfir()
-        self._plan = C.c_void_p()
-        taps = np.ascontiguousarray(taps, dtype=np.float32)
-        self.mode, self.nbands, self.nchan, self.fmt, self.ntaps = DECIMATE, int(nbands), int(nchan), _FMT[fmt], taps.size
-        if int(oversample) == 1:
-            self.ratio = int(nbands)
-            self._ck(self._lib.sxfir_create_channelizer(C.byref(self._plan), taps.ctypes.data_as(C.c_void_p), taps.size, int(nbands),
-                                                        int(nchan), self.fmt, int(device)))
-        else:
-            self.ratio = int(nbands) // int(oversample) if int(oversample) > 0 else 0
-            self._ck(self._lib.sxfir_create_channelizer_os(C.byref(self._plan), taps.ctypes.data_as(C.c_void_p), taps.size, int(nbands),
-                                                           int(oversample), int(nchan), self.fmt, int(device)))
-
-    @property
-    def bands(self):
-        """sxfir_plan_bands: the plan's own count."""
-        n = C.c_int()
-        self._ck(self._lib.sxfir_plan_bands(self._plan, C.byref(n)))
-        return n.value
-
-    @property
-    def oversampling(self):
-        """sxfir_plan_oversampling: 1 for the critically sampled plan, 2 for the oversampled one."""
-        n = C.c_int()
-        self._ck(self._lib.sxfir_plan_oversampling(self._plan, C.byref(n)))
-        return n.value
+    _mode = DECIMATE
+    _create = ("sxfir_create_channelizer", "sxfir_create_channelizer_os")
+    _query = ("sxfir_plan_bands", "sxfir_plan_oversampling")
 
     def process_ptr(self, in_ptr, n_in, in_stride, out_ptr, out_stride, band_stride, stream=0):
         """sxfir_channelize: band k of channel c starts at out_ptr + c * out_stride + k * band_stride (samples of the output
@@ -427,7 +441,7 @@ class Channelizer(_Plan):
         return res[0] if squeeze else res
 
 
-class Synthesizer(_Plan):
+class Synthesizer(_BandPlan):
     """The 4-band synthesizer (include/sxfir_synthesizer.h): `nbands` sub-bands of the x nbands raster into one wideband stream in one
     pass -- what Channelizer takes apart, put together.  `taps`: the REAL prototype low-pass of a x nbands interpolator
     (design_lowpass(ntaps, nbands, gain=nbands)); band k lands at k / nbands cycles per output sample.  Stream state, contract,
@@ -437,33 +451,9 @@ class Synthesizer(_Plan):
     Channelizer(..., oversample=2) hands out -- and the prototype is a x2 interpolator's with the /4 band edge
     (design_lowpass(ntaps, nbands, gain=2)); the plan is a x(nbands // oversample) interpolator in everything about the stream."""
 
-    def __init__(self, taps, nbands=4, nchan=1, fmt="CF32", device=-1, oversample=1):
-        self._lib = load_sxfir()
-        self._plan = C.c_void_p()
-        taps = np.ascontiguousarray(taps, dtype=np.float32)
-        self.mode, self.nbands, self.nchan, self.fmt, self.ntaps = INTERPOLATE, int(nbands), int(nchan), _FMT[fmt], taps.size
-        if int(oversample) == 1:
-            self.ratio = int(nbands)
-            self._ck(self._lib.sxfir_create_synthesizer(C.byref(self._plan), taps.ctypes.data_as(C.c_void_p), taps.size, int(nbands),
-                                                        int(nchan), self.fmt, int(device)))
-        else:
-            self.ratio = int(nbands) // int(oversample) if int(oversample) > 0 else 0
-            self._ck(self._lib.sxfir_create_synthesizer_os(C.byref(self._plan), taps.ctypes.data_as(C.c_void_p), taps.size, int(nbands),
-                                                           int(oversample), int(nchan), self.fmt, int(device)))
-
-    @property
-    def bands(self):
-        """sxfir_plan_synthesis_bands: the plan's own count."""
-        n = C.c_int()
-        self._ck(self._lib.sxfir_plan_synthesis_bands(self._plan, C.byref(n)))
-        return n.value
-
-    @property
-    def oversampling(self):
-        """sxfir_plan_synthesis_oversampling: 1 for the critically sampled plan, 2 for the oversampled one."""
-        n = C.c_int()
-        self._ck(self._lib.sxfir_plan_synthesis_oversampling(self._plan, C.byref(n)))
-        return n.value
+    _mode = INTERPOLATE
+    _create = ("sxfir_create_synthesizer", "sxfir_create_synthesizer_os")
+    _query = ("sxfir_plan_synthesis_bands", "sxfir_plan_synthesis_oversampling")
 
     def set_tx_threshold(self, threshold2):
         self._ck(self._lib.sxfir_set_tx_threshold(self._plan, float(threshold2)))

@@ -34,6 +34,46 @@ def to_cpu(t):
     return t.cpu().numpy()
 
 
+# ---- the band plans' inputs (tests/test_gpu_channelizer.py, test_gpu_synthesizer.py and their _os files: each binds its own
+# SEED with functools.partial and names the result `source`) --------------------------------------------------------------------
+def random_taps(n, seed=5):
+    """Real taps with no symmetry to lean on."""
+    return (np.random.default_rng(seed).standard_normal(n) / 64.0).astype(np.float32)
+
+
+def wideband_source(oracle, channel, n, start=0, seed=0):
+    """The synthetic source on the GPU and its CPU twin: a channelizer's input."""
+    import torch
+    import sxxcvr_amd
+    x = torch.empty(n, dtype=torch.complex64, device="cuda")
+    sxxcvr_amd.synth_fill(x, seed, channel, start)
+    return x, oracle.synth_iq(seed, channel, start, n)
+
+
+def four_band_source(oracle, channel, n, start=0, seed=0):
+    """Four bands of the synthetic source on the GPU (channels channel .. channel + 3) and their CPU twin: a synthesizer's input."""
+    import torch
+    import sxxcvr_amd
+    x = torch.empty((4, n), dtype=torch.complex64, device="cuda")
+    sxxcvr_amd.synth_fill(x, seed, channel, start)
+    return x, np.stack([oracle.synth_iq(seed, channel + k, start, n) for k in range(4)])
+
+
+def run(plan, xg, **kw):
+    """One process() call, waited for, on the CPU."""
+    import torch
+    y = plan.process(xg, **kw)
+    torch.cuda.synchronize()
+    return to_cpu(y)
+
+
+def band_proto(gain=1.0):
+    """The 128-tap prototype of the 4-band plans, the /4 band edge: gain 1 for a channelizer (critically sampled or oversampled),
+    4 for the synthesizer (as for any x4 interpolator), 2 for the oversampled synthesizer (a x2 interpolator's)."""
+    import sxxcvr_amd
+    return sxxcvr_amd.design_lowpass(128, 4, 8.0, gain)
+
+
 # ---- the band plans' references (tests/test_gpu_channelizer.py, test_gpu_synthesizer.py, test_gpu_call_frame.py) -------------
 def chan_ref(oracle, h, x, threads=None):
     """[4, n_out] complex64: the four bands of one channelizer pass over x from zero history."""

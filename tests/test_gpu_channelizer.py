@@ -4,6 +4,7 @@ The reference value is always built the same way: u_r = oracle.dec
 every tap of phase != r set to +0.0 -- the oracle's (1, 1) tree then adds three +0.0 columns to the one chain, which is exact, and
 a chain from +0.0 never yields -0.0 -- then the radix-2 butterflies of the header in float32 numpy, one rounding per operation."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -11,38 +12,19 @@ import pytest
 import sxxcvr_amd
 from sxxcvr_amd import design_lowpass
 from sxxcvr_amd.resampler import DECIMATE, KERNEL_GENERIC, KERNEL_TILED
-from gpu_util import OUT_FILL, assert_bands, assert_bit_exact, chan_ref, to_cpu, to_gpu
+from gpu_util import OUT_FILL, assert_bands, assert_bit_exact, band_proto, chan_ref, random_taps, run, to_cpu, to_gpu, wideband_source
 
 pytestmark = pytest.mark.gpu
 
 SEED = 0xC4A77E1
 TILE_IN = 2048
 TILED, GENERIC = "chan4_kernel", "chan_generic_kernel"
-
-
-def random_taps(n, seed=5):
-    """Real taps with no symmetry to lean on."""
-    return (np.random.default_rng(seed).standard_normal(n) / 64.0).astype(np.float32)
-
-
-def source(oracle, channel, n, start=0):
-    """The synthetic source on the GPU and its CPU twin."""
-    import torch
-    x = torch.empty(n, dtype=torch.complex64, device="cuda")
-    sxxcvr_amd.synth_fill(x, SEED, channel, start)
-    return x, oracle.synth_iq(SEED, channel, start, n)
-
-
-def run(plan, xg, **kw):
-    import torch
-    y = plan.process(xg, **kw)
-    torch.cuda.synchronize()
-    return to_cpu(y)
+source = functools.partial(wideband_source, seed=SEED)
 
 
 @pytest.fixture(scope="module")
 def proto():
-    return design_lowpass(128, 4)
+    return band_proto()
 
 
 @pytest.mark.parametrize("which", ["lowpass", "random"])

@@ -5,6 +5,7 @@ The reference value is always built the same way: u_r = oracle.decim_f32(h_r, 2,
 started from +0.0 as it is -- then the radix-2 butterflies of the header in float32 numpy, one rounding per operation, on
 (u0, u1, u2, u3) in the even columns and on (u2, u3, u0, u1) in the odd ones."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -12,7 +13,7 @@ import pytest
 import sxxcvr_amd
 from sxxcvr_amd import design_lowpass
 from sxxcvr_amd.resampler import DECIMATE, KERNEL_AUTO, KERNEL_GENERIC, KERNEL_TILED
-from gpu_util import OUT_FILL, assert_bands, assert_bit_exact, to_cpu, to_gpu
+from gpu_util import OUT_FILL, assert_bands, assert_bit_exact, band_proto, random_taps, run, to_cpu, to_gpu, wideband_source
 from test_channelizer_os_host import (EDGE_TONE_BAND0_DB, EDGE_TONE_BAND1_DB, EDGE_TONE_BIN0, EDGE_TONE_BIN1, edge_tone,
                                       edge_tone_spectra)
 
@@ -21,11 +22,7 @@ pytestmark = pytest.mark.gpu
 SEED = 0xC4A77E2
 TILE_IN = 2048
 TILED, GENERIC = "chan4x2_kernel", "chan4x2_generic_kernel"
-
-
-def random_taps(n, seed=5):
-    """Real taps with no symmetry to lean on."""
-    return (np.random.default_rng(seed).standard_normal(n) / 64.0).astype(np.float32)
+source = functools.partial(wideband_source, seed=SEED)
 
 
 def chan_os_ref(oracle, h, x, threads=None):
@@ -51,28 +48,13 @@ def chan_os_ref(oracle, h, x, threads=None):
     return y
 
 
-def source(oracle, channel, n, start=0):
-    """The synthetic source on the GPU and its CPU twin."""
-    import torch
-    x = torch.empty(n, dtype=torch.complex64, device="cuda")
-    sxxcvr_amd.synth_fill(x, SEED, channel, start)
-    return x, oracle.synth_iq(SEED, channel, start, n)
-
-
-def run(plan, xg, **kw):
-    import torch
-    y = plan.process(xg, **kw)
-    torch.cuda.synchronize()
-    return to_cpu(y)
-
-
 def os_plan(h, **kw):
     return sxxcvr_amd.Channelizer(h, oversample=2, **kw)
 
 
 @pytest.fixture(scope="module")
 def proto():
-    return design_lowpass(128, 4)
+    return band_proto()
 
 
 @pytest.mark.parametrize("which", ["lowpass", "random"])

@@ -30,7 +30,8 @@ pytestmark = pytest.mark.gpu
 def shapes():
     """name -> (mode, ratio, taps): both modes at ratios 4 .. 96 with 32 taps per phase, /4 with 64 taps, /4 with 128 taps
     that are not bit-symmetric, one shape only the generic kernels take, the two complex-tap plans, and the band plans
-    ("chan...": created through Channelizer, "syn...": through Synthesizer) with the tiled kernels' 128 taps and with 64."""
+    ("chan...": created through Channelizer, "syn...": through Synthesizer; "...os...": with oversample=2, where `ratio` is the
+    stream's 2 and the bands are 4) with the tiled kernels' 128 taps and with 64."""
     import sxxcvr_amd
     from sxxcvr_amd.resampler import DECIMATE, INTERPOLATE
     out = {}
@@ -48,12 +49,16 @@ def shapes():
     for n in (128, 64):
         out["chan4x%d" % n] = (DECIMATE, 4, sxxcvr_amd.design_lowpass(n, 4))
         out["syn4x%d" % n] = (INTERPOLATE, 4, sxxcvr_amd.design_lowpass(n, 4, 8.0, 4.0))
+        # 2x oversampled: 4 bands on a /2, x2 stream
+        out["chanos4x%d" % n] = (DECIMATE, 2, sxxcvr_amd.design_lowpass(n, 4))
+        out["synos4x%d" % n] = (INTERPOLATE, 2, sxxcvr_amd.design_lowpass(n, 4, 8.0, 2.0))
     return out
 
 
 SHAPE_NAMES = ["decim%d" % r for r in (4, 8, 16, 32, 48, 96)] + ["interp%d" % r for r in (4, 8, 16, 32, 48, 96)] + \
               ["decim4x64", "decim4asym", "decim5x40", "interp5x40", "cx4x128", "cx8x256"] + \
-              ["chan4x128", "chan4x64", "syn4x128", "syn4x64"]
+              ["chan4x128", "chan4x64", "syn4x128", "syn4x64"] + \
+              ["chanos4x128", "chanos4x64", "synos4x128", "synos4x64"]
 
 
 def call_sizes(plan, mode, ratio, nchan):
@@ -78,9 +83,9 @@ def make_plan(name, fmt, nchan):
     import sxxcvr_amd
     mode, ratio, taps = shapes()[name]
     if name.startswith("chan"):
-        return sxxcvr_amd.Channelizer(taps, ratio, nchan=nchan, fmt=fmt)
+        return sxxcvr_amd.Channelizer(taps, 4, nchan=nchan, fmt=fmt, oversample=4 // ratio)
     if name.startswith("syn"):
-        return sxxcvr_amd.Synthesizer(taps, ratio, nchan=nchan, fmt=fmt)
+        return sxxcvr_amd.Synthesizer(taps, 4, nchan=nchan, fmt=fmt, oversample=4 // ratio)
     return sxxcvr_amd.Resampler(mode, taps, ratio, nchan=nchan, fmt=fmt)
 
 
@@ -108,6 +113,22 @@ def off_boundary_rows(sizes=None):
         return [[n] + [plan.geometry(n)[f] for f in FIELDS] for n in sizes]
     finally:
         plan.close()
+
+
+def chanos_position_rows(sizes=None):
+    """position -> rows of a 2x oversampled channelizer (4 bands x 128 taps, CF32) placed there: every position of the /2 stream's
+    raster starts on an output, but chan4x2_kernel also needs that output's index even -- a position that is a multiple of 4."""
+    import sxxcvr_amd
+    sizes = sizes if sizes is not None else [7, 8, 1024, 1 << 20]
+    out = {}
+    for pos in (2, 4):
+        plan = sxxcvr_amd.Channelizer(sxxcvr_amd.design_lowpass(128, 4), 4, oversample=2)
+        try:
+            plan.set_position(pos)
+            out[str(pos)] = [[n] + [plan.geometry(n)[f] for f in FIELDS] for n in sizes]
+        finally:
+            plan.close()
+    return out
 
 
 def compute_units():
@@ -152,6 +173,14 @@ def test_off_boundary_falls_to_generic(table):
     got = off_boundary_rows([row[0] for row in want])
     assert got == want
     assert all(row[1] == "decim_generic_kernel" and not row[2] for row in got)
+
+
+def test_chanos_position_picks_the_kernel(table):
+    want = table["chanos_position"]
+    got = chanos_position_rows([row[0] for row in want["2"]])
+    assert got == want
+    assert all(row[1] == "chan4x2_generic_kernel" and not row[2] for row in got["2"])
+    assert all(row[1] == "chan4x2_kernel" and row[2] for row in got["4"])
 
 
 # ---- kernel-table entries that no other test compares with the oracle bit for bit (which test reaches which entry:
@@ -318,10 +347,11 @@ def record(path):
             for nchan in NCHAN:
                 t["plans"]["%s/%s/%d" % (name, fmt, nchan)] = rows_for(name, fmt, nchan)
     t["off_boundary"] = off_boundary_rows()
+    t["chanos_position"] = chanos_position_rows()
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "w") as f:
-        f.write("{\n \"compute_units\": %d,\n \"fields\": %s,\n \"off_boundary\": %s,\n \"plans\": {\n" % (
-            t["compute_units"], json.dumps(t["fields"]), json.dumps(t["off_boundary"])))
+        f.write("{\n \"compute_units\": %d,\n \"fields\": %s,\n \"off_boundary\": %s,\n \"chanos_position\": %s,\n \"plans\": {\n" % (
+            t["compute_units"], json.dumps(t["fields"]), json.dumps(t["off_boundary"]), json.dumps(t["chanos_position"])))
         f.write(",\n".join("  %s: %s" % (json.dumps(k), json.dumps(v, separators=(",", ":"))) for k, v in t["plans"].items()))
         f.write("\n }\n}\n")
     print("recorded %d plans, %d rows, %d compute units -> %s" % (len(t["plans"]), sum(len(v) for v in t["plans"].values()), t["compute_units"], path))

@@ -4,6 +4,7 @@ The reference value is always built the same way: v_r by the heade
 per operation; then output phase r of oracle.interp_f32(h, 4, v_r, jsplit) -- the real-tap interpolator under the contract the plan
 reports, applied to the stream v_r -- for r = 0..3, interleaved."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -11,7 +12,7 @@ import pytest
 import sxxcvr_amd
 from sxxcvr_amd import design_lowpass
 from sxxcvr_amd.resampler import DECIMATE, INTERPOLATE, KERNEL_GENERIC, KERNEL_TILED
-from gpu_util import OUT_FILL, assert_bit_exact, syn_ref, to_cpu, to_gpu
+from gpu_util import OUT_FILL, assert_bit_exact, band_proto, four_band_source, random_taps, run, syn_ref, to_cpu, to_gpu
 from test_synthesizer_host import band_tone, tone_and_rest, wideband_tone
 
 pytestmark = pytest.mark.gpu
@@ -19,31 +20,12 @@ pytestmark = pytest.mark.gpu
 SEED = 0x5E7A11
 T = 256                                                     # inputs per band of a tile
 TILED, GENERIC = "synthesis4_kernel", "synthesis_generic_kernel"
-
-
-def random_taps(n, seed=5):
-    """Real taps with no symmetry to lean on."""
-    return (np.random.default_rng(seed).standard_normal(n) / 64.0).astype(np.float32)
-
-
-def source(oracle, channel, n, start=0):
-    """Four bands of the synthetic source on the GPU (channels channel .. channel + 3) and their CPU twin."""
-    import torch
-    x = torch.empty((4, n), dtype=torch.complex64, device="cuda")
-    sxxcvr_amd.synth_fill(x, SEED, channel, start)
-    return x, np.stack([oracle.synth_iq(SEED, channel + k, start, n) for k in range(4)])
-
-
-def run(plan, xg, **kw):
-    import torch
-    y = plan.process(xg, **kw)
-    torch.cuda.synchronize()
-    return to_cpu(y)
+source = functools.partial(four_band_source, seed=SEED)
 
 
 @pytest.fixture(scope="module")
 def proto():
-    return design_lowpass(128, 4, 8.0, 4.0)                 # gain 4, as for any x4 interpolator
+    return band_proto(gain=4.0)
 
 
 @pytest.mark.parametrize("which", ["lowpass", "random"])

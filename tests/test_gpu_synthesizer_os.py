@@ -5,6 +5,7 @@ The reference value is always built the same way: v_r by the heade
 under the contract the plan reports, applied to the stream v_r -- for r = 0..3, and output n taken from run n & 3, n the ABSOLUTE
 output index."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -12,7 +13,7 @@ import pytest
 import sxxcvr_amd
 from sxxcvr_amd import design_lowpass
 from sxxcvr_amd.resampler import INTERPOLATE, KERNEL_GENERIC, KERNEL_TILED
-from gpu_util import OUT_FILL, assert_bit_exact, butterflies_f32, to_cpu, to_gpu
+from gpu_util import OUT_FILL, assert_bit_exact, band_proto, butterflies_f32, four_band_source, random_taps, run, to_cpu, to_gpu
 from test_channelizer_os_host import edge_tone
 from test_synthesizer_host import band_tone, spectrum_db, tone_and_rest
 from test_synthesizer_os_host import (BAND_TONE_BIN, BAND_TONE_DB, BAND_TONE_DROP, BAND_TONE_KEEP, BAND_TONE_N, CRIT_IMAGE_BIN,
@@ -24,19 +25,7 @@ SEED = 0x5E7A12
 T = 512                                                     # inputs per band of a tile (outputs: 2 T)
 HIST = 64                                                   # a band's history: ntaps / 2
 TILED, GENERIC = "synthesis4x2_kernel", "synthesis_os_generic_kernel"
-
-
-def random_taps(n, seed=5):
-    """Real taps with no symmetry to lean on."""
-    return (np.random.default_rng(seed).standard_normal(n) / 64.0).astype(np.float32)
-
-
-def source(oracle, channel, n, start=0):
-    """Four bands of the synthetic source on the GPU (channels channel .. channel + 3) and their CPU twin."""
-    import torch
-    x = torch.empty((4, n), dtype=torch.complex64, device="cuda")
-    sxxcvr_amd.synth_fill(x, SEED, channel, start)
-    return x, np.stack([oracle.synth_iq(SEED, channel + k, start, n) for k in range(4)])
+source = functools.partial(four_band_source, seed=SEED)
 
 
 def syn_os_ref(oracle, h, x, jsplit, m0=0, threads=None):
@@ -57,16 +46,9 @@ def os_plan(h, **kw):
     return sxxcvr_amd.Synthesizer(h, oversample=2, **kw)
 
 
-def run(plan, xg, **kw):
-    import torch
-    y = plan.process(xg, **kw)
-    torch.cuda.synchronize()
-    return to_cpu(y)
-
-
 @pytest.fixture(scope="module")
 def proto():
-    return design_lowpass(128, 4, 8.0, 2.0)                 # the /4 band edge, gain 2: a x2 interpolator's
+    return band_proto(gain=2.0)
 
 
 @pytest.mark.parametrize("which", ["lowpass", "random"])
