@@ -16,18 +16,17 @@ int sxfir_create_complex(sxfir_plan **out, int mode, const float *taps_iq, int n
     sxfir_plan *p = nullptr;
     if (int rc = new_plan(&p, KIND_COMPLEX, mode, ntaps, ratio, nchan, fmt, device)) return rc;
     p->hist_len = (ntaps + 1) & ~1;
-    p->ext_tiled = fmt == SXFIR_CF32 && ratio == 4 && ntaps == 128;
     real_tap_contract(p);
-    resolve_kernels(p);
-    query_occupancy(&p->occ_ext, p->k.cx, 64);
+    set_form(p, fmt == SXFIR_CF32 && ratio == 4 && ntaps == 128 ? &FORM_CX : nullptr);
+    resolve_form(p);
 
-    // planar on the device: a[0, ntaps) then b[0, ntaps); no second tap table
+    // planar on the device: a[0, ntaps) then b[0, ntaps); no second tap table (TAPS_NONE, new_plan)
     std::vector<float> planar(2 * (size_t)ntaps);
     for (int k = 0; k < ntaps; ++k) {
         planar[(size_t)k] = taps_iq[2 * k];
         planar[(size_t)ntaps + (size_t)k] = taps_iq[2 * k + 1];
     }
-    return plan_to_device(out, p, planar.data(), planar.size(), nullptr);
+    return plan_to_device(out, p, planar.data(), planar.size());
 }
 
 int sxfir_taps_are_complex(const sxfir_plan *p, int *is_complex)

@@ -7,8 +7,8 @@
 // sxfir.hip after sxfir_plan.hip.h.
 #pragma once
 
-// A launch that hands taps_scaled_dev to a kernel states which layout that kernel reads; sxfir_create chose the layout
-// from the same plan flags, so a mismatch means the two sides were changed apart: refuse instead of filtering with
+// A launch that hands taps_scaled_dev to a kernel states which layout that kernel reads; the plan's creator took the layout
+// from the plan's form row, so a mismatch means the two sides were changed apart: refuse instead of filtering with
 // permuted taps.
 static int need_tap_table(const sxfir_plan *p, int layout, const char *kernel)
 {
@@ -28,15 +28,14 @@ struct CallIO {
                               // (sxfir_synthesize): inputs between them; else 0
 };
 
-// What the tiled kernels' 16-byte stores need: an aligned output and, between channels, an even stride -- whole 16-byte units of
-// halves (a stride of 4) for the multi-column and dense kernels on CF16 storage; a channelizer's bands are stored like channels:
-// an even band stride too (critically sampled or oversampled).  (LDS-DMA sources need no 16-byte alignment -- verified on MI355X, tools/probe_unaligned.hip -- and the
-// edge loads go sample by sample: the input's alignment and strides are the entry point's business alone.)  The stride of 4 holds
-// for every kernel of a multi_capable CF16 plan; that is right only while no CF16 plan is both multi_capable and tile_capable
-// (sxfir_create: half4_wide excludes multi, the `mu` knob is CF32 only) -- a shape with both would need 2 for its tile kernel.
+// What the tiled kernels' 16-byte stores need: an aligned output and, between channels, an even stride -- on CF16 storage the
+// form's own quantum (whole 16-byte units of halves, a stride of 4, for the dense and block kernels); a channelizer's bands are
+// stored like channels: an even band stride too (critically sampled or oversampled).  (LDS-DMA sources need no 16-byte alignment
+// -- verified on MI355X, tools/probe_unaligned.hip -- and the edge loads go sample by sample: the input's alignment and strides are
+// the entry point's business alone.)
 static bool stores_aligned(const sxfir_plan *p, const CallIO &c)
 {
-    const size_t q = p->multi_capable && p->fmt == SXFIR_CF16 ? 4 : 2;
+    const size_t q = p->form && p->fmt == SXFIR_CF16 ? p->form->cf16_stride : 2;
     return (uintptr_t)c.out % 16 == 0 && (p->nchan == 1 || c.out_stride % q == 0) && (p->kind != KIND_CHANNELIZER || c.band_stride % 2 == 0);
 }
 
@@ -82,7 +81,8 @@ static int launch(void (*kernel)(P...), dim3 grid, unsigned threads, hipStream_t
 struct LaunchGeom {
     int kind;                 // GEOM_* (sxfir_plan.hip.h)
     const char *kernel;
-    long long tile_out;       // decimator: outputs per tile; interpolator: inputs per tile
+    long long tile_out;       // decimator: outputs per tile; interpolator: inputs per tile (generic kernels: 256 threads' items)
+    long long tile_samples;   // ... in wideband samples: a decimator's inputs, an interpolator's outputs
     long long n_tiles;        // per channel
     long long groups;         // workgroups per channel (times phase_blocks)
     long long resident;       // workgroups the chip holds at once, all channels
@@ -115,9 +115,9 @@ static void set_schedule(sxfir::DecimTileArgs &a, long long n_tiles, long long g
 // the x16 .. x96 pass kernels' window and lane constants) run 2-3 % faster when a workgroup keeps at least four tiles
 // (tools/split_ab.sh: /32 at 2^25 66.7 us with 2 generations, 69.0 with 8; at 2^28 the other way round, 514 against 508): as many
 // generations as leave every workgroup four tiles, at least one, at most the plan's.
-static long long generations(const sxfir_plan *p, long long n_tiles, long long resident, bool heavy_prologue)
+static long long generations(const sxfir_plan *p, long long n_tiles, long long resident)
 {
-    if (!heavy_prologue || prof_oversub_forced()) return p->oversub;
+    if (!p->form->heavy_prologue || prof_oversub_forced()) return p->oversub;
     long long g = n_tiles * p->nchan / (4 * resident);
     if (g < 1) g = 1;
     return g > p->oversub ? p->oversub : g;
@@ -129,14 +129,29 @@ static long long clamp_groups(long long g, long long n_tiles)
     return g > n_tiles ? n_tiles : g;
 }
 
-// tiles of `tile` outputs (interpolator: inputs), `resident` workgroup slots on the chip
-static void set_tiles(LaunchGeom &g, int kind, const char *kernel, long long n, long long tile, long long resident)
+// The plan's generic kernel over n items, one per thread, each `samples_per_item` wideband samples: a decimator's outputs and a
+// synthesizer's input indexes (ratio samples each), an interpolator's outputs (one)
+static LaunchGeom generic_geom(const sxfir_plan *p, long long n, long long samples_per_item)
 {
-    g.kind = kind;
-    g.kernel = kernel;
+    return LaunchGeom{GEOM_GENERIC, p->k.generic_name, 256, 256 * samples_per_item, (n + 255) / 256, (n + 255) / 256, (long long)p->compute_units * 8, 1, 1};
+}
+
+// The plan's form over n outputs (interpolator: inputs) in tiles of `tile`, on the workgroup slots the chip has for it
+static void set_tiles(LaunchGeom &g, const sxfir_plan *p, long long n, long long tile)
+{
+    g.kind = p->form->geom;
+    g.kernel = p->form->tiled;
     g.tile_out = tile;
+    g.tile_samples = tile * p->ratio;
     g.n_tiles = (n + tile - 1) / tile;
-    g.resident = resident;
+    g.resident = (long long)p->compute_units * p->occ;
+}
+
+// Workgroups per channel: the form's generations of resident workgroups (generations(): fewer for a small call of a form with a
+// heavy prologue, whose tile is `work_per_tile` units of the rule), at most one per work item
+static void set_groups(LaunchGeom &g, const sxfir_plan *p, long long work_per_tile)
+{
+    g.groups = clamp_groups(g.resident * generations(p, g.n_tiles * work_per_tile, g.resident) / p->nchan, g.n_tiles * g.split) * g.phase_blocks;
 }
 
 // samples of this call in front of the first one that completes an output (0: the call starts on an output boundary)
@@ -146,78 +161,48 @@ static long long first_offset(const sxfir_plan *p)
     return ((p->consumed + D - 1) / D) * D - p->consumed;
 }
 
-// `aligned`: stores_aligned() of the call
+// `aligned`: stores_aligned() of the call.  The plan's generic kernel, unless the plan has a form, the call wants it, is aligned,
+// starts on an output boundary and at a position the form takes; then the form's tiles, its generations of workgroups, and for
+// the block form, while the call's tiles over all channels fit the plan's scratch, (tile, block) items, one workgroup each
+// (decim_blocks_kernel<..., SPLIT>).
 static LaunchGeom decim_geom(const sxfir_plan *p, long long n_out, long long first, bool aligned)
 {
-    const BandForm *f = p->form;          // channelizer plans
-    LaunchGeom g{GEOM_GENERIC, f ? f->generic : p->kind == KIND_COMPLEX ? "decim_cx_generic_kernel" : "decim_generic_kernel", 256,
-                 (n_out + 255) / 256, (n_out + 255) / 256, (long long)p->compute_units * 8, 1, 1};
-    const long long CU = p->compute_units;
-    const bool want = p->kernel != SXFIR_KERNEL_GENERIC && first == 0;
-    if (p->ext_tiled && want && aligned && (!f || p->consumed % f->start_multiple == 0)) {
-        // complex taps: decim4_cx_kernel for /4 x 128 on CF32; channelizer: the form's tiled kernel for 4 bands x 128 taps on CF32 (its
-        // tile PER BAND and the positions it starts at: BAND_FORMS); the generic kernel of the kind for everything else.  All on the wide
-        // kernel's frame: its sixteen generations of waves at the sizes they were measured at, fewer while that would leave a wave
-        // under four tiles (generations(): a small call is one strided pass of resident waves)
-        if (f) set_tiles(g, f->geom, f->tiled, n_out, f->tile, CU * p->occ_ext);
-        else set_tiles(g, GEOM_CX, "decim4_cx_kernel", n_out, 512, CU * p->occ_ext);
-        g.groups = clamp_groups(g.resident * generations(p, g.n_tiles, g.resident, true) / p->nchan, g.n_tiles);
-    } else if (p->multi_capable && want && aligned) {
-        set_tiles(g, GEOM_MULTI, p->blocks ? "decim_blocks_kernel" : p->dense32 ? "decim_dense_kernel" : "decim_multi_kernel", n_out,
-                  p->blocks ? 512 : p->multi_waves * 8 * (64 / (p->multi_ps * (p->ratio / 4))), CU * p->occ_multi);
-        g.groups = clamp_groups(g.resident * generations(p, g.n_tiles, g.resident, p->dense32 && !p->dense_subset) / p->nchan, g.n_tiles);
-        // /48, /96: while a call has at most eight times as many tiles as the chip has workgroup slots, (tile, block) items are dealt,
-        // one workgroup each (decim_blocks_kernel<..., SPLIT>); the plan's scratch holds that many block values
-        if (p->blocks && p->join_partials && p->blocks_split && g.n_tiles * p->nchan <= p->join_tiles) {
-            g.split = p->blocks;
-            g.groups = g.n_tiles * p->blocks;
-        }
-    } else if (p->tile_capable && want && aligned) {
-        // 128 symmetric taps: decim4_wide_kernel, tiles of 512 outputs, one wave (= one workgroup) per tile and pass; else the
-        // 4-outputs-per-lane kernels.  Short-lived waves in generations: CUs x resident waves x oversub waves per launch, each
-        // covering its share of the tiles in strided, XCD-blocked passes (sxfir_decim_tile.hip.h)
-        if (p->wide8 && p->sched != 1) set_tiles(g, GEOM_WIDE, "decim4_wide_kernel", n_out, 512, CU * p->occ_wide);
-        else set_tiles(g, GEOM_TILE, "decim4_tile_kernel", n_out, prof_tile_out(p, 256), CU * (p->tile_dbuf ? p->occ_db : p->occ_sb));
-        g.groups = clamp_groups(g.resident * p->oversub / p->nchan, g.n_tiles);
+    LaunchGeom g = generic_geom(p, n_out, p->ratio);
+    const PlanForm *f = p->form;
+    if (!(f && p->kernel != SXFIR_KERNEL_GENERIC && aligned && first == 0 && p->consumed % f->start_multiple == 0)) return g;
+    set_tiles(g, p, n_out, p->tile);
+    set_groups(g, p, 1);
+    if (p->blocks && p->join_partials && p->blocks_split && g.n_tiles * p->nchan <= p->join_tiles) {
+        g.split = p->blocks;
+        g.groups = g.n_tiles * p->blocks;
     }
     return g;
 }
 
+// Interpolators and synthesizers: as decim_geom (every position starts a tile).  interp_tile_kernel's tile is shared by one
+// workgroup per phase block (x48, x96: three; six blocks of the x16 kernel -- SXFIR_IBLOCK16=1 in the profiling build -- measured
+// 5 % slower, profiles/round5_rates.txt).  The pass form's tile at x16 .. x96 is ratio / 16 phase blocks' work -- generations()
+// counts blocks, dealt or walked -- and at x32, x48, x96, while a call has at most four times as many tiles as the chip holds
+// waves, (tile, phase block) items are dealt (interp8_pass_kernel<..., PBSPLIT>: an interpolator's phases never meet, so nothing
+// is joined).
 static LaunchGeom interp_geom(const sxfir_plan *p, long long n_in, bool aligned, bool keyed)
 {
-    if (p->kind == KIND_SYNTHESIZER) {
-        // synthesizer: the form's tiled kernel for 4 bands x 128 taps on CF32 (its tile of inputs PER BAND: BAND_FORMS; both forms start
-        // at any position); one thread per input index of the form's generic kernel for everything else.  Small calls dealt as fewer
-        // generations of waves, the channelizer's rule
-        const BandForm *f = p->form;
-        LaunchGeom s{GEOM_GENERIC, f->generic, 256, (n_in + 255) / 256, (n_in + 255) / 256, (long long)p->compute_units * 8, 1, 1};
-        if (p->ext_tiled && p->kernel != SXFIR_KERNEL_GENERIC && aligned) {
-            set_tiles(s, f->geom, f->tiled, n_in, f->tile, (long long)p->compute_units * p->occ_ext);
-            s.groups = clamp_groups(s.resident * generations(p, s.n_tiles, s.resident, true) / p->nchan, s.n_tiles);
-        }
-        return s;
+    const bool syn = p->kind == KIND_SYNTHESIZER;       // one thread per input index of its generic kernels
+    LaunchGeom g = generic_geom(p, syn ? n_in : n_in * p->ratio, syn ? p->ratio : 1);
+    const PlanForm *f = p->form;
+    if (!(f && p->kernel != SXFIR_KERNEL_GENERIC && aligned)) return g;
+    long long tile = p->tile, blocks_per_tile = 1;
+    if (f->geom == GEOM_ITILE) {
+        const int base_l = prof_iblock16(p, keyed, itile_base(p->ratio));
+        g.phase_blocks = p->ratio / base_l;
+        tile = 2048 / base_l;
     }
-    const long long n_out = n_in * p->ratio;
-    LaunchGeom g{GEOM_GENERIC, "interp_generic_kernel", 256, (n_out + 255) / 256, (n_out + 255) / 256,
-                 (long long)p->compute_units * 8, 1, 1};
-    if (!(p->itile_capable && p->kernel != SXFIR_KERNEL_GENERIC && aligned)) return g;
-    if (p->ipass) {
-        set_tiles(g, GEOM_IPASS, "interp8_pass_kernel", n_in, 64 * p->ipass_qi, (long long)p->compute_units * p->occ_ipass);
-        // x32, x48, x96: while a call has at most four times as many tiles as the chip holds waves, (tile, phase block) items are
-        // dealt (interp8_pass_kernel<..., PBSPLIT>: an interpolator's phases never meet, so nothing is joined)
+    set_tiles(g, p, n_in, tile);
+    if (f->geom == GEOM_IPASS && p->ratio >= 16) {
+        blocks_per_tile = p->ratio / 16;
         if (p->ratio > 16 && p->ipass_split && g.n_tiles * p->nchan <= 4 * g.resident) g.split = p->ratio / 16;
-        // (a x48 / x96 tile is three / six blocks' work: the rule counts blocks, dealt or walked)
-        g.groups = clamp_groups(g.resident * generations(p, g.n_tiles * (p->ratio >= 16 ? p->ratio / 16 : 1), g.resident, p->ratio >= 16) / p->nchan,
-                                g.n_tiles * g.split);
-        return g;
     }
-    // CF16 storage: interp_tile_kernel; x48: three phase blocks of the x16 kernel; x96: three of the x32 kernel (two whole lines per
-    // input and block; six blocks of the x16 kernel -- SXFIR_IBLOCK16=1 in the profiling build -- measured 5 % slower,
-    // profiles/round5_rates.txt)
-    const int base_l = prof_iblock16(p, keyed, p->ratio == 96 ? 32 : (p->ratio == 48 ? 16 : p->ratio));
-    g.phase_blocks = p->ratio / base_l;
-    set_tiles(g, GEOM_ITILE, "interp_tile_kernel", n_in, 4 * 4 * (32 / (base_l / 4)) /* InterpTile<L>::TILE_IN */, (long long)p->compute_units * 16);
-    g.groups = clamp_groups(g.resident * p->oversub / p->nchan, g.n_tiles) * g.phase_blocks;
+    set_groups(g, p, blocks_per_tile);
     return g;
 }
 
@@ -278,8 +263,8 @@ static sxfir::DecimTileArgs decim_tile_args(const sxfir_plan *p, const CallIO &c
     a.in_stride = (long long)c.in_stride;
     a.out_stride = (long long)c.out_stride;
     a.hist_stride = p->hist_len;
-    a.sched = p->sched;
-    set_schedule(a, geom.n_tiles, geom.groups, p->sched);
+    a.sched = prof_sched(p);                        // (0: XCD-blocked strided passes)
+    set_schedule(a, geom.n_tiles, geom.groups, a.sched);
     return a;
 }
 
@@ -401,24 +386,25 @@ static int launch_decim(sxfir_plan *p, const CallIO &c, bool *history_done)
     const long long first = first_offset(p);
     const LaunchGeom geom = decim_geom(p, c.n_out, first, stores_aligned(p, c));
     const dim3 grid((unsigned)geom.groups, (unsigned)p->nchan);
-    const int band = p->form ? p->form->geom : GEOM_GENERIC;         // channelizer plans: which of the two forms
     if (geom.kind == GEOM_GENERIC) {
         if (p->kernel == SXFIR_KERNEL_TILED)
             return fail(SXFIR_EUNSUPPORTED,
                         "tiled kernel needs a 16-byte aligned output, an even output stride and a call that starts on "
                         "an output boundary%s", p->form && p->form->start_multiple == 4 ? " of even index (a stream position that is a multiple of 4)" : "");
-        if (band == GEOM_CHAN4X2) return launch(p->k.chan4x2_generic, grid, 256, c.st, chan_os_generic_args(p, c, first));
-        if (band == GEOM_CHAN4) return launch(p->k.chan_generic, grid, 256, c.st, chan_generic_args(p, c, first));
+        // (a channelizer plan has its own generic kernel instead of `generic`)
+        if (p->k.chan4x2_generic) return launch(p->k.chan4x2_generic, grid, 256, c.st, chan_os_generic_args(p, c, first));
+        if (p->k.chan_generic) return launch(p->k.chan_generic, grid, 256, c.st, chan_generic_args(p, c, first));
         return launch(p->k.generic, grid, 256, c.st, generic_args(p, c, first));
     }
     if (geom.n_tiles > 0x7fffffffLL) return fail(SXFIR_EINVAL, "call too large");
     *history_done = true;
-    if (geom.kind == GEOM_CHAN4) return launch(p->k.chan4, grid, 64, c.st, chan_tile_args(p, c, geom));
-    if (geom.kind == GEOM_CHAN4X2) return launch(p->k.chan4x2, grid, 64, c.st, chan_tile_args(p, c, geom));
+    const unsigned threads = (unsigned)p->form->threads;
+    if (geom.kind == GEOM_CHAN4) return launch(p->k.chan4, grid, threads, c.st, chan_tile_args(p, c, geom));
+    if (geom.kind == GEOM_CHAN4X2) return launch(p->k.chan4x2, grid, threads, c.st, chan_tile_args(p, c, geom));
     if (geom.kind == GEOM_MULTI) {
         sxfir::DecimMultiArgs a = decim_multi_args(p, c, geom);
         if (p->blocks) {
-            // /48, /96: sixteen-column blocks, scalar taps from the block-major table of the rotated taps
+            // sixteen-column blocks, scalar taps from the block-major table of the rotated taps
             if (int rc = need_tap_table(p, TAPS_BLOCKS16, "decim_blocks_kernel")) return rc;
             a.taps = p->taps_scaled_dev;
             sxfir::DecimBlocksJoin jn{};
@@ -427,26 +413,26 @@ static int launch_decim(sxfir_plan *p, const CallIO &c, bool *history_done)
             const int pr = prof_launch_blocks(p, geom, a, jn, grid, c.st);
             if (pr < 0) return pr;
             if (!pr)
-                if (int rc = launch(p->k.blocks[geom.split > 1], grid, 256, c.st, a, jn)) return rc;
+                if (int rc = launch(p->k.blocks[geom.split > 1], grid, threads, c.st, a, jn)) return rc;
             return prof_join_drop_copy(p, geom, c.st);
         }
         // /8, /16, /32: decim_dense_kernel (profiling: its ablations, or the multi-column kernel it replaced)
-        if (const int pr = p->dense32 ? prof_launch_dense(p, a, grid, c.st) : prof_launch_multi(p, a, grid, c.st)) return pr < 0 ? pr : SXFIR_OK;
-        if (p->dense_subset) {
+        if (const int pr = prof_launch_dense(p, a, grid, c.st)) return pr < 0 ? pr : SXFIR_OK;
+        if (p->form->taps == TAPS_SUBSET8) {
             if (int rc = need_tap_table(p, TAPS_SUBSET8, p->fmt == SXFIR_CF16 ? "decim_dense_kernel<8, SUBSET, HALFIN>" : "decim_dense_kernel<8, SUBSET>")) return rc;
             a.taps = p->taps_scaled_dev;                      // the subset-major tap table
         }
-        return launch(p->k.dense, grid, 256, c.st, a);
+        return launch(p->k.dense, grid, threads, c.st, a);
     }
     // /4: one wave (= one workgroup) per tile and pass
     sxfir::DecimTileArgs a = decim_tile_args(p, c, geom);
-    if (geom.kind == GEOM_CX) return launch(p->k.cx, grid, 64, c.st, a);
+    if (geom.kind == GEOM_CX) return launch(p->k.cx, grid, threads, c.st, a);
     if (p->fmt == SXFIR_S32)                               // only wire-word plans read taps_scaled
         if (int rc = need_tap_table(p, TAPS_SCALED, "the /4 scalar-tap kernels on S32 words")) return rc;
     if (p->fmt == SXFIR_CF16 && geom.kind != GEOM_WIDE)
         return fail(SXFIR_EUNSUPPORTED, "CF16 storage at /4 runs the wide kernel only (a profiling knob asked for another /4 variant)");
     if (const int pr = prof_launch_tile(p, geom, a, c.n_out, c.st)) return pr < 0 ? pr : SXFIR_OK;
-    return launch(geom.kind == GEOM_WIDE ? p->k.wide : p->k.tile, grid, 64, c.st, a);
+    return launch(geom.kind == GEOM_WIDE ? p->k.wide : p->k.tile, grid, threads, c.st, a);
 }
 
 extern "C" {
@@ -471,7 +457,7 @@ static int launch_interp(sxfir_plan *p, const CallIO &c, bool *history_done, con
     const sxfir::InterpTileArgs t = interp_tile_args(p, c, geom, key);
     *history_done = true;
     if (const int pr = prof_launch_interp(p, geom, t, grid, key != nullptr, c.st)) return pr < 0 ? pr : SXFIR_OK;
-    return launch(p->k.interp[key != nullptr][geom.split > 1], grid, 64, c.st, t);
+    return launch(p->k.interp[key != nullptr][geom.split > 1], grid, (unsigned)p->form->threads, c.st, t);
 }
 
 // Synthesizer plans (sxfir_synthesize): the kernel alone, as launch_interp.
@@ -483,14 +469,14 @@ static int launch_synth(sxfir_plan *p, const CallIO &c, bool *history_done)
     if (geom.kind == GEOM_GENERIC) {
         if (p->kernel == SXFIR_KERNEL_TILED)
             return fail(SXFIR_EUNSUPPORTED, "tiled synthesizer needs a 16-byte aligned output and an even output stride");
-        if (p->form->geom == GEOM_SYN4X2) return launch(p->k.syn4x2_generic, grid, 256, c.st, syn_os_generic_args(p, c));
+        if (p->k.syn4x2_generic) return launch(p->k.syn4x2_generic, grid, 256, c.st, syn_os_generic_args(p, c));
         return launch(p->k.syn_generic, grid, 256, c.st, syn_generic_args(p, c));
     }
     if (geom.n_tiles > 0x7fffffffLL) return fail(SXFIR_EINVAL, "call too large");
     if (int rc = need_tap_table(p, TAPS_PHASED, p->form->tiled)) return rc;
     *history_done = true;
-    if (geom.kind == GEOM_SYN4X2) return launch(p->k.syn4x2, grid, 64, c.st, syn_os_tile_args(p, c, geom));
-    return launch(p->k.syn4, grid, 64, c.st, syn_tile_args(p, c, geom));
+    if (geom.kind == GEOM_SYN4X2) return launch(p->k.syn4x2, grid, (unsigned)p->form->threads, c.st, syn_os_tile_args(p, c, geom));
+    return launch(p->k.syn4, grid, (unsigned)p->form->threads, c.st, syn_tile_args(p, c, geom));
 }
 
 // Shapes the tiled kernels do not take: the keying count as a pass of its own (same rule, same counter).  Queued by
@@ -611,8 +597,7 @@ int sxfir_launch_geometry(const sxfir_plan *p, size_t n_in, sxfir_geometry *out)
     snprintf(out->kernel, sizeof(out->kernel), "%s", g.kernel);
     out->tiled = g.kind != GEOM_GENERIC;
     out->split = g.split;
-    out->tile_samples = g.tile_out * p->ratio;       // wideband samples: a decimator's inputs, an interpolator's outputs
-    if (g.kind == GEOM_GENERIC) out->tile_samples = p->mode == SXFIR_DECIMATE ? 256LL * p->ratio : (p->kind == KIND_SYNTHESIZER ? 256LL * p->ratio : 256);
+    out->tile_samples = g.tile_samples;
     out->n_tiles = g.n_tiles;
     out->workgroups = g.groups * p->nchan;
     out->resident = g.resident;

@@ -1,8 +1,11 @@
 // Plan bookkeeping of the C ABI (include/sxfir.h): what a plan holds and which of the four kinds it is, the kernel table (which
-// instance a shape launches: the one statement of it, for the occupancy queries and the launches), the creation frame every
-// sxfir_create* goes through (argument checks, the device, the plan's common fields, the real-tap contract, the plan's device
-// memory and the one list of what to free), how sxfir_create settles a real-tap plan's flags and lays out its tap tables, the
-// one creation path of the four band plans (create_band_plan), and the small state entry points (reset, history, position, contract).
+// instance a shape launches: the one statement of it, for the occupancy query and the launches), the form rows (what the geometry
+// and launch code needs to know of a tiled kernel family: one row per family, one pointer per plan), settle_form (which row a
+// real-tap shape gets: the one statement of the product's shape-to-family rules), the tap-table layouts, the creation frame every
+// sxfir_create* goes through (argument checks, the device, the plan's common fields, the real-tap contract, the form, its kernels
+// and occupancy, the plan's device memory and the one list of what to free), sxfir_create, the one creation path of the four band
+// plans (create_band_plan), and the small state entry points (reset, history, position, contract).  The product never looks at the
+// environment: what the profiling build's knobs change sits behind the prof_* hooks of sxfir_prof_create.inc.
 // Included by sxfir.hip after the kernel headers; not a stand-alone translation unit.
 #pragma once
 
@@ -12,13 +15,22 @@
 // (sxfir_synthesizer_os.hip.h: KIND_SYNTHESIZER with ratio = bands / oversample).  A complex-tap plan is a decimator whose taps_dev
 // holds a[0, ntaps) then b[0, ntaps); the band kinds are a /ratio decimator and a x ratio interpolator in everything about the stream.
 enum PlanKind { KIND_REAL = 0, KIND_COMPLEX = 1, KIND_CHANNELIZER = 2, KIND_SYNTHESIZER = 3 };
-enum TapTable { TAPS_SCALED = 0, TAPS_SUBSET8 = 1, TAPS_PASS8 = 2, TAPS_BLOCKS16 = 3, TAPS_PHASED = 4 };
+
+// The layout of a plan's second tap table (taps_scaled_dev); one function per layout below (second_tap_table).
+// TAPS_SCALED: taps * 2^-31 (exact) in tap order, for the /4 scalar-tap kernels on S32 wire words;
+// TAPS_SUBSET8: the subset-major table of decim_dense_kernel<8, ..., SUBSET> (times 2^-31 for S32 plans);
+// TAPS_PASS8: the pass-major table of interp8_pass_kernel (pass (c, p) at 64 (2c + p), (jj, rr) at 4 jj + rr);
+// TAPS_BLOCKS16: the block-major table of decim_blocks_kernel, of the ROTATED taps (times 2^-31 for S32 plans);
+// TAPS_PHASED: the phase-major table of synthesis4_kernel and synthesis4x2_kernel (h[ratio j + r] at (ntaps / ratio) r + j: four
+// phases, or the two output parities of the oversampled plan); TAPS_NONE: the plan's kernels read taps_dev alone.
+// Every launch that hands taps_scaled_dev to a kernel checks the plan's layout first (need_tap_table).
+enum TapTable { TAPS_SCALED = 0, TAPS_SUBSET8 = 1, TAPS_PASS8 = 2, TAPS_BLOCKS16 = 3, TAPS_PHASED = 4, TAPS_NONE = 5 };
 
 // Which kernel family a call launches (LaunchGeom::kind, sxfir_launch.hip.h)
 enum { GEOM_GENERIC = 0, GEOM_MULTI = 1, GEOM_WIDE = 2, GEOM_TILE = 3, GEOM_IPASS = 4, GEOM_ITILE = 5, GEOM_CX = 6, GEOM_CHAN4 = 7, GEOM_SYN4 = 8, GEOM_CHAN4X2 = 9, GEOM_SYN4X2 = 10 };
 
 // One typed kernel pointer per launch-argument family, and a plan's kernels: resolved once by the plan's creator
-// (resolve_kernels below), read by the occupancy queries there and by the launches (sxfir_launch.hip.h).
+// (resolve_kernels below), read by the occupancy query there and by the launches (sxfir_launch.hip.h).
 typedef void (*GenericFn)(sxfir::GenericArgs);
 typedef void (*DecimMultiFn)(sxfir::DecimMultiArgs);
 typedef void (*DecimBlocksFn)(sxfir::DecimMultiArgs, sxfir::DecimBlocksJoin);
@@ -32,7 +44,8 @@ typedef void (*SynGenericFn)(sxfir::SynGenericArgs);
 typedef void (*SynOsTileFn)(sxfir::SynOsTileArgs);
 typedef void (*SynOsGenericFn)(sxfir::SynOsGenericArgs);
 struct KernelTable {
-    GenericFn generic;           // decim_generic_kernel / decim_cx_generic_kernel / interp_generic_kernel: every plan has one
+    const char *generic_name;    // the plan's generic kernel, as sxfir_launch_geometry reports it: every plan has exactly one of the five
+    GenericFn generic;           // decim_generic_kernel / decim_cx_generic_kernel / interp_generic_kernel: real and complex taps
     DecimMultiFn dense;          // decim_dense_kernel (/8, /16, /32)
     DecimBlocksFn blocks[2];     // decim_blocks_kernel (/48, /96): [0] the walking form, [1] SPLIT, (tile, block) items
     DecimTileFn tile, wide, cx;  // /4: decim4_tile_kernel, decim4_wide_kernel, decim4_cx_kernel (complex taps)
@@ -47,13 +60,24 @@ struct KernelTable {
     SynOsGenericFn syn4x2_generic;     // ... and synthesis_os_generic_kernel, which every such plan has INSTEAD of `generic` and `syn_generic`
 };
 
-// What the geometry and launch code needs to know of a band plan's pair of kernels (BAND_FORMS below; resolve_kernels picks one)
-struct BandForm {
-    const char *tiled, *generic;   // the kernels' names, as sxfir_launch_geometry reports them
-    int geom;                      // GEOM_* of the tiled kernel: also names the form where the typed pointers and argument structs differ
-    int tile;                      // the tiled kernel's tile PER BAND: outputs of a channelizer, inputs of a synthesizer
-    int start_multiple;            // the tiled kernel takes a call that starts at a stream position that is a multiple of this (1: any)
+// What the geometry and launch code needs to know of a tiled kernel family (FORM_* below).  A plan has at most one, settled at
+// creation (settle_form; the band and complex-tap creators' one line each); a call only chooses between it and the plan's generic
+// kernel.  A plan without a row runs its generic kernel alone.
+enum { TILE_DENSE = -1, TILE_IPASS = -2, TILE_ITILE = -3 };    // PlanForm::tile where one family serves several ratios (form_tile)
+struct PlanForm {
+    const char *tiled;             // the kernel's name, as sxfir_launch_geometry reports it
+    int geom;                      // GEOM_*: also names the family where the typed pointers and argument structs differ
+    int tile;                      // outputs per tile of a decimator, inputs of an interpolator (band plans: PER BAND), or a TILE_* rule
+    int threads;                   // per workgroup
+    int start_multiple;            // the kernel takes a call that starts at a stream position that is a multiple of this (1: any)
+    int cf16_stride;               // on CF16 storage its 16-byte stores need a channel stride that is a multiple of this (else: of 2)
+    bool heavy_prologue;           // generations(): a workgroup of a small call keeps at least four tiles
+    int generations;               // generations of resident workgroups per launch, measured (the comments at the rows)
+    int occ;                       // resident workgroups per CU where the runtime has no answer
+    int taps;                      // the TapTable layout its kernel reads
 };
+
+#include "sxfir_prof_knobs.inc"    // struct ProfKnobs: what the profiling build's knobs set; empty in the production library
 
 struct sxfir_plan {
     int kind;              // PlanKind
@@ -65,73 +89,30 @@ struct sxfir_plan {
                            // (sxfir_create_synthesizer), 2 each band at fs/2 (sxfir_create_synthesizer_os: ratio 2, bands 4); else 0
     int kernel;            // SXFIR_KERNEL_*
     int hist_len;          // samples of history kept per channel
-    int blocks;            // /48, /96: sixteen-column blocks of decim_blocks_kernel (3, 6), else 0
     int jsplit, cw;        // numeric contract
     int rot;               // ... and its rotation (0; 1 for /48, /96: sxfir_contract_rotation)
-    void *join_partials;   // /48, /96: scratch of decim_blocks_kernel<..., SPLIT>: join_tiles x blocks block values of 4 KiB
+    bool symmetric;        // real taps: taps[k] == taps[ntaps-1-k] bit for bit (every linear-phase design)
+    const PlanForm *form;  // the plan's tiled kernel family; null: generic only
+    int tile;              // ... its tile for this ratio (form_tile),
+    int oversub;           // ... its generations per launch: workgroups launched = CUs * occ * oversub,
+    int occ;               // ... and its resident workgroups per CU, asked of the runtime for the form's base instance (occupancy_instance)
+    int blocks;            // the block form: sixteen-column blocks per row (/48: 3, /96: 6), else 0
+    void *join_partials;   // ... scratch of decim_blocks_kernel<..., SPLIT>: join_tiles x blocks block values of 4 KiB
     unsigned *join_arrived;   // ... and one arrival counter per (channel, tile); zero between launches: each tile's last item
                               // zeroes its own, sxfir_reset and a failed launch zero them all
     long long join_tiles;  // tiles (over all channels) the scratch holds = the largest call the SPLIT form takes
-    bool blocks_split;     // (profiling: SXFIR_BLOCKS_SPLIT=0 switches the (tile, block) dealing off)
-#ifdef SXFIR_PROFILING
-    int join_drop;         // SXFIR_BLOCKS_JOIN_DROP=<b> (test hook): the items of block b store their block value to join_shadow instead
-    void *join_shadow;     // of the scratch, where it is copied behind the launch (join_tiles x 4 KiB, allocated with the knob); -1 = off
-#endif
-    bool ipass_split;      // x32, x48, x96: (tile, phase block) items for small calls (profiling: SXFIR_IPASS_SPLIT=0 switches it off)
-    bool tile_capable;     // decim4_tile_kernel (ratio 4, 128 or 64 taps, CF32)
-    bool multi_capable;    // decim_multi_kernel (ratio 8/16/32, 32 taps per phase, CF32)
-    bool itile_capable;    // interp_tile_kernel (ratio 4/8/16/32, 32 taps per phase, CF32)
-    int dense_nt;          // profiling build, SXFIR_DENSE_NT = 1 / 0: decim_dense_kernel with nt / plain staging loads at every ratio
-    int dense_nt_set;      // ... and whether the knob was given at all
-    bool dense_hc;         // (profiling) SXFIR_DENSE_HC=1: decim_dense_kernel with halo carry (/32, /16)
-    bool dense_subset;     // /8, CF32 or S32 words: the scalar-tap form of decim_dense_kernel (tap subsets on the four waves)
-    bool dense32;          // decim_dense_kernel (ratio 8 / 16 / 32, 32 taps per phase, CF32 / S32): the linear-image form
-    int multi_waves;       // waves per workgroup of the multi kernel
-    int multi_ps;          // lanes that share the 32 tap rows of one output (2 or 4) in the multi kernel
-    int occ_multi;         // resident workgroups per CU of the multi kernel
-    bool tile_dbuf;        // double-buffered LDS-DMA variant of the tile kernel
-    int occ_sb, occ_db;    // resident waves per CU of the two tile-kernel variants
-    int oversub;           // waves launched = CUs * occupancy * oversub
-    void *stamps_dev;      // diagnostic clock stamps (ABLATE 11/12 only)
-    size_t stamps_n;
+    bool blocks_split;     // (tile, block) items for calls the scratch holds (profiling: SXFIR_BLOCKS_SPLIT=0 switches the dealing off)
+    bool ipass_split;      // the pass form at x32, x48, x96: (tile, phase block) items for small calls (profiling: SXFIR_IPASS_SPLIT=0 switches it off)
     float thr2;            // S32 interpolator: transmitter-keying threshold (squared magnitude)
-    int sgpr_r;            // experiment: SGPR-tap variant with R outputs per lane (0 = off)
-    int sched;             // tile schedule of the tile kernel (0 strided passes, 1 contiguous runs)
-    int ablate;            // profiling only: 1 = memory side alone, 2 = compute side alone
-    int lds_pad;           // profiling only: extra dynamic LDS bytes per workgroup of a tile2 variant (caps the waves per CU)
-    int t2_wpg, t2_opt;    // profiling only: decim4_tile2_kernel variant (waves per workgroup, T2_* bits); wpg 0 = off
-    bool pair;             // decim4_pair_kernel: the two tap halves on the two waves of a workgroup
-    bool pair_xsep;        // ... with a separate exchange buffer (two barriers per tile instead of four)
-    int occ_pair;          // its resident workgroups per CU
-    bool wide8;            // product: /4 with 128 symmetric taps runs decim4_wide_kernel (8 outputs per lane, 512-output tiles)
-    bool wide;             // (profiling) a non-default build of decim4_wide_kernel was asked for ("wide<nb>", "wident<nb>")
-    int wide_nb;           // (profiling) its LDS read-ahead depth: 0 = default
-    bool wide_nt;          // (profiling) "wident...": with non-temporal staging loads
-    bool wide_pin;         // (profiling) "widentp...": and the FMA issue order pinned (volatile asm)
-    int wide_pol;          // (profiling) SXFIR_WIDE_POL: cache policy of its nt loads (low byte) and stores (next byte)
-    int occ_wide;
     int compute_units;
     float *taps_dev;
-    float *taps_scaled_dev;   // the second tap table; its layout is one of TapTable, chosen from dense_subset / ipass in sxfir_create
-    int tap_table;            // TAPS_SCALED: taps * 2^-31 (exact) in tap order, for the /4 scalar-tap kernels on S32 wire words;
-                              // TAPS_SUBSET8: the subset-major table of decim_dense_kernel<8, ..., SUBSET> (times 2^-31 for S32 plans);
-                              // TAPS_PASS8: the pass-major table of interp8_pass_kernel (pass (c, p) at 64 (2c + p), (jj, rr) at 4 jj + rr).
-                              // TAPS_PHASED: the phase-major table of synthesis4_kernel and synthesis4x2_kernel (h[ratio j + r] at
-                              // (ntaps / ratio) r + j: four phases, or the two output parities of the oversampled plan).
-                              // Every launch that hands taps_scaled_dev to a kernel checks this first (need_tap_table).
-    bool ipass;               // x8, 256 taps, CF32: interp8_pass_kernel (scalar taps, four passes per tile)
-    int occ_ipass;
-    int ipass_qi;             // inputs per lane of that kernel (2; profiling: 4)
-    bool ipass_wait0;         // (profiling) SXFIR_IPASS_WAIT0=1: its vmcnt(0) form (A/B partner of the counted wait)
+    float *taps_scaled_dev;   // the second tap table, in the layout tap_table names (the form's; TAPS_SCALED for a real-tap plan without a form)
+    int tap_table;
     float taps_k[64];         // the first 64 taps (times 2^-31 for S32 plans) for kernels that take them by value
-    bool symmetric;           // taps[k] == taps[ntaps-1-k] bit for bit (every linear-phase design)
-    bool ext_tiled;           // the other kinds: the shape their tiled kernel takes (decim4_cx_kernel: /4, 128 taps, CF32; chan4_kernel,
-                              // chan4x2_kernel, synthesis4_kernel and synthesis4x2_kernel: 4 bands x 128 taps, CF32)
-    int occ_ext;              // its resident waves per CU
     void *hist_dev;        // current history: nchan * hist_len samples
-    void *hist_alt;        // the tile kernel writes the next history here, then the two swap
+    void *hist_alt;        // the tiled kernels write the next history here, then the two swap
     KernelTable k;         // the instances this plan launches (null: none in this build for that family)
-    const BandForm *form;  // the band kinds: what decim_geom / interp_geom and the launches read of the plan's two kernels; else null
+    ProfKnobs prof;        // written and read by the profiling build's hooks alone
     long long consumed, produced;
 };
 
@@ -140,7 +121,7 @@ struct sxfir_plan {
 // the product's template argument lists are written.  nullptr: no instance for that shape in the production library (its A/B
 // partners are launched by the profiling build's hooks, sxfir_prof_dispatch.inc); launch() refuses a null entry.
 //
-// Occupancy (sxfir_create) is queried on the entry of a plan's BASE form, which is not always the instance a call launches:
+// Occupancy (occupancy_instance, resolve_form) is queried on the entry of a plan's BASE form, which is not always the instance a call launches:
 // the walking, non-SPLIT form for /48 and /96; interp_kernel(16, CF32, unkeyed, walking) for every x16 .. x96 plan whatever its
 // ratio, format or keying, (8, CF32, ...) for x8 and (4, CF32, ...) for x4; decim4_tile_kernel's CF32 instance for S32 words too.
 // The launch geometry of every plan was measured with these figures.
@@ -292,48 +273,153 @@ static SynOsGenericFn synthesis_os_generic_kernel_for(int fmt)
 // outputs per band = 2048 inputs; its lane map needs the call's first output to have an EVEN index, i.e. a stream position that is
 // a multiple of 4 (every position of the /2 raster starts on an output).  synthesis4_kernel: 256 inputs per band on the x4 pass
 // kernel's frame.  synthesis4x2_kernel: any per-band start index -- the start's parity is its argument.
-static const BandForm BAND_FORMS[2][2] = {
-    {{"chan4_kernel", "chan_generic_kernel", GEOM_CHAN4, 512, 1}, {"chan4x2_kernel", "chan4x2_generic_kernel", GEOM_CHAN4X2, 1024, 4}},
-    {{"synthesis4_kernel", "synthesis_generic_kernel", GEOM_SYN4, 256, 1},
-     {"synthesis4x2_kernel", "synthesis_os_generic_kernel", GEOM_SYN4X2, sxfir::Syn4x2::TILE_IN, 1}}};
+static const PlanForm BAND_FORMS[2][2] = {
+    {{"chan4_kernel", GEOM_CHAN4, 512, 64, 1, 2, true, 16, 8, TAPS_NONE}, {"chan4x2_kernel", GEOM_CHAN4X2, 1024, 64, 4, 2, true, 16, 8, TAPS_NONE}},
+    {{"synthesis4_kernel", GEOM_SYN4, 256, 64, 1, 2, true, 16, 8, TAPS_PHASED},
+     {"synthesis4x2_kernel", GEOM_SYN4X2, sxfir::Syn4x2::TILE_IN, 64, 1, 2, true, 16, 5, TAPS_PHASED}}};
 
-// The plan's kernels, from its kind and the capability flags its creator has settled (the profiling knobs included)
+// ---- The form rows of the real-tap and complex-tap plans: {name, GEOM_*, tile, threads, start multiple, CF16 stride, heavy
+// prologue, generations, occupancy where the runtime has no answer, tap layout}.
+// Generations of workgroups per launch, measured on MI355X at 2^28 samples (tools/kbench.py): the /4 kernels, single-buffered LDS-DMA
+// at their resident waves per CU, run 16 generations of short-lived waves (4 tiles each) in strided XCD-blocked passes (the
+// double-buffered variant and long contiguous runs are slower); decim4_cx_kernel and the band kernels stand on the wide kernel's
+// frame: its sixteen generations at the sizes they were measured at, fewer while that would leave a wave under four tiles.  The
+// dense and block kernels' prologue (the taps and the DMA offset table per lane) is heavier than the /4 kernels': 8 beats 16, and
+// where it is 64 taps into VGPRs (/16, /32) a small call keeps four tiles per workgroup.  The pass kernel: 4 / 8 / 16 measured within
+// 0.3 % (tools/ibench2.py), 8; its x16 .. x96 form pays a window and lane constants per workgroup.  interp_tile_kernel is flat between
+// 2 and 16 (tools/ibench.py): 4, and 2 for its three-phase-block form (x48, x96: 1-2 % ahead of 4 .. 32, profiles/round5_rates.txt).
+// decim4_wide_kernel: /4, 128 taps, tiles of 512 outputs, one wave (= one workgroup) per tile and pass
+static const PlanForm FORM_WIDE = {"decim4_wide_kernel", GEOM_WIDE, 512, 64, 1, 2, false, 16, 8, TAPS_SCALED};
+// decim4_tile_kernel: /4, four outputs per lane, tiles of 256 outputs
+static const PlanForm FORM_TILE4 = {"decim4_tile_kernel", GEOM_TILE, 256, 64, 1, 2, false, 16, 8, TAPS_SCALED};
+// decim_dense_kernel: /16, /32, the linear-image form, 4096 / ratio outputs per tile of four waves (a 10 KiB LDS image per wave
+// while the 31-row halo stays a small part of the staging); LDS is what limits the residents: 2
+static const PlanForm FORM_DENSE = {"decim_dense_kernel", GEOM_MULTI, TILE_DENSE, 256, 1, 4, true, 8, 2, TAPS_SCALED};
+// ... and /8: its scalar-tap form, the tap subsets on the four waves (round 4: 4.4-5 % less time)
+static const PlanForm FORM_DENSE_SUBSET = {"decim_dense_kernel", GEOM_MULTI, TILE_DENSE, 256, 1, 4, false, 8, 2, TAPS_SUBSET8};
+// decim_blocks_kernel: /48, /96, sixteen-column blocks of whole input lines under the rotated contract, tiles of 512 outputs
+static const PlanForm FORM_BLOCKS = {"decim_blocks_kernel", GEOM_MULTI, 512, 256, 1, 4, false, 8, 2, TAPS_BLOCKS16};
+// interp8_pass_kernel on CF32 / S32 words: 64 x inputs per lane -- x4 four inputs per lane and two passes, x8 two and four ...
+static const PlanForm FORM_IPASS = {"interp8_pass_kernel", GEOM_IPASS, TILE_IPASS, 64, 1, 2, false, 8, 16, TAPS_PASS8};
+// ... x16 .. x96 over ratio / 16 phase blocks of sixteen per tile, walked or (x32, x48, x96: ipass_split) dealt
+static const PlanForm FORM_IPASS_BLOCKS = {"interp8_pass_kernel", GEOM_IPASS, TILE_IPASS, 64, 1, 2, true, 8, 16, TAPS_PASS8};
+// interp_tile_kernel on CF16 storage: InterpTile<L>::TILE_IN inputs per tile; its 16 waves per CU are the measured figure, not asked
+// of the runtime ...
+static const PlanForm FORM_ITILE = {"interp_tile_kernel", GEOM_ITILE, TILE_ITILE, 64, 1, 2, false, 4, 16, TAPS_SCALED};
+// ... x48 as three phase blocks of its x16 form, x96 of its x32 form (two whole lines per input and block)
+static const PlanForm FORM_ITILE_BLOCKS = {"interp_tile_kernel", GEOM_ITILE, TILE_ITILE, 64, 1, 2, false, 2, 16, TAPS_SCALED};
+// decim4_cx_kernel: complex taps, /4 x 128 on CF32, on the wide kernel's frame
+static const PlanForm FORM_CX = {"decim4_cx_kernel", GEOM_CX, 512, 64, 1, 2, true, 16, 8, TAPS_NONE};
+
+// The ratio whose kernel a tile of interp_tile_kernel runs: x48 is three phase blocks of the x16 kernel, x96 three of the x32 kernel
+static int itile_base(int ratio) { return ratio > 32 ? ratio / 3 : ratio; }
+
+static int form_tile(const PlanForm *f, int ratio)
+{
+    switch (f->tile) {
+    case TILE_DENSE: return 4096 / ratio;
+    case TILE_IPASS: return 64 * (ratio == 4 ? 4 : 2);
+    case TILE_ITILE: return 2048 / itile_base(ratio);          // InterpTile<L>::TILE_IN = 4 * 4 * (32 / (L / 4))
+    }
+    return f->tile;
+}
+
+// Which form a real-tap shape gets: DESIGN.md 5's table, row by row.  Everything it does not name -- any other ratio, any
+// taps_per_phase but 32 -- runs the generic kernels (null).
+static const PlanForm *settle_form(int mode, int ratio, int ntaps, int fmt, bool symmetric)
+{
+    const bool cf16 = fmt == SXFIR_CF16;
+    if (mode == SXFIR_DECIMATE && ratio == 4 && ntaps == 64) return fmt == SXFIR_CF32 ? &FORM_TILE4 : nullptr;
+    if (ntaps != 32 * ratio) return nullptr;
+    if (mode == SXFIR_INTERPOLATE) {
+        // CF32 / S32 words: the scalar-tap pass kernel at every ratio (x16 .. x96, round 5: 8-9 % less time than interp_tile_kernel,
+        // which keeps CF16 storage: typed LDS-DMA in, half pairs out)
+        switch (ratio) {
+        case 4: case 8: return cf16 ? &FORM_ITILE : &FORM_IPASS;
+        case 16: case 32: return cf16 ? &FORM_ITILE : &FORM_IPASS_BLOCKS;
+        case 48: case 96: return cf16 ? &FORM_ITILE_BLOCKS : &FORM_IPASS_BLOCKS;
+        }
+        return nullptr;
+    }
+    switch (ratio) {
+    // /4 x 128: the wide kernel for bit-symmetric taps and, its ASYM form, for CF16 storage whatever the taps (wide_kernel); else
+    // the four-outputs-per-lane kernel
+    case 4: return symmetric || cf16 ? &FORM_WIDE : &FORM_TILE4;
+    case 8: return &FORM_DENSE_SUBSET;
+    case 16: case 32: return &FORM_DENSE;
+    case 48: case 96: return &FORM_BLOCKS;             // (the reference's rates master clock / 768 and / 1536)
+    }
+    return nullptr;
+}
+
+// The plan's form: its tile at the plan's ratio, its generations per launch and its default occupancy
+static void set_form(sxfir_plan *p, const PlanForm *f)
+{
+    p->form = f;
+    if (!f) return;
+    p->tile = form_tile(f, p->ratio);
+    p->oversub = f->generations;
+    p->occ = f->occ;
+}
+
+// The plan's kernels, from its kind and its form
 static void resolve_kernels(sxfir_plan *p)
 {
     KernelTable &k = p->k;
     k = KernelTable{};
-    p->form = nullptr;
-    if (p->kind == KIND_CHANNELIZER || p->kind == KIND_SYNTHESIZER) {
-        p->form = &BAND_FORMS[p->kind == KIND_SYNTHESIZER][p->oversample == 2];
-        switch (p->form->geom) {            // every band plan has its form's generic kernel INSTEAD of `generic`
-        case GEOM_CHAN4:
-            k.chan_generic = chan_generic_kernel_for(p->fmt);
-            if (p->ext_tiled) k.chan4 = sxfir::chan4_kernel;
-            break;
-        case GEOM_CHAN4X2:
-            k.chan4x2_generic = chan4x2_generic_kernel_for(p->fmt);
-            if (p->ext_tiled) k.chan4x2 = sxfir::chan4x2_kernel;
-            break;
-        case GEOM_SYN4:
-            k.syn_generic = synthesis_generic_kernel_for(p->fmt);
-            if (p->ext_tiled) k.syn4 = sxfir::synthesis4_kernel;
-            break;
-        case GEOM_SYN4X2:
-            k.syn4x2_generic = synthesis_os_generic_kernel_for(p->fmt);
-            if (p->ext_tiled) k.syn4x2 = sxfir::synthesis4x2_kernel;
-            break;
-        }
+    const bool os = p->oversample == 2;
+    const int geom = p->form ? p->form->geom : GEOM_GENERIC;
+    if (p->kind == KIND_CHANNELIZER) {      // every band plan has its own generic kernel INSTEAD of `generic`
+        k.generic_name = os ? "chan4x2_generic_kernel" : "chan_generic_kernel";
+        if (os) k.chan4x2_generic = chan4x2_generic_kernel_for(p->fmt);
+        else k.chan_generic = chan_generic_kernel_for(p->fmt);
+        if (geom == GEOM_CHAN4) k.chan4 = sxfir::chan4_kernel;
+        if (geom == GEOM_CHAN4X2) k.chan4x2 = sxfir::chan4x2_kernel;
         return;
     }
+    if (p->kind == KIND_SYNTHESIZER) {
+        k.generic_name = os ? "synthesis_os_generic_kernel" : "synthesis_generic_kernel";
+        if (os) k.syn4x2_generic = synthesis_os_generic_kernel_for(p->fmt);
+        else k.syn_generic = synthesis_generic_kernel_for(p->fmt);
+        if (geom == GEOM_SYN4) k.syn4 = sxfir::synthesis4_kernel;
+        if (geom == GEOM_SYN4X2) k.syn4x2 = sxfir::synthesis4x2_kernel;
+        return;
+    }
+    k.generic_name = p->kind == KIND_COMPLEX ? "decim_cx_generic_kernel" : p->mode == SXFIR_DECIMATE ? "decim_generic_kernel" : "interp_generic_kernel";
     k.generic = generic_kernel(p->mode, p->fmt, p->kind == KIND_COMPLEX);
-    if (p->ext_tiled) k.cx = sxfir::decim4_cx_kernel;
-    if (p->dense32) k.dense = dense_kernel(p->ratio, p->fmt);
-    for (int split = 0; split < 2; ++split) k.blocks[split] = blocks_kernel(p->blocks, p->fmt, split != 0);
-    if (p->tile_capable) k.tile = tile_kernel(p->ntaps, p->fmt);
-    if (p->tile_capable && p->ntaps == 128) k.wide = wide_kernel(p->fmt, p->symmetric);
-    if (p->itile_capable)
+    switch (geom) {
+    case GEOM_CX: k.cx = sxfir::decim4_cx_kernel; break;
+    case GEOM_MULTI:
+        if (!p->blocks) k.dense = dense_kernel(p->ratio, p->fmt);
+        for (int split = 0; split < 2; ++split) k.blocks[split] = blocks_kernel(p->blocks, p->fmt, split != 0);
+        break;
+    case GEOM_WIDE: k.wide = wide_kernel(p->fmt, p->symmetric); break;
+    case GEOM_TILE: k.tile = tile_kernel(p->ntaps, p->fmt); break;
+    case GEOM_IPASS:
+    case GEOM_ITILE:
         for (int keyed = 0; keyed < 2; ++keyed)
             for (int split = 0; split < 2; ++split) k.interp[keyed][split] = interp_kernel(p->ratio, p->fmt, keyed != 0, split != 0);
+        break;
+    }
+}
+
+// The instance a form's occupancy is asked of: the plan's BASE form (the comment at the head of the kernel table), which is not
+// always the instance a call launches.  Null: the form's own figure stands (interp_tile_kernel's 16 was never the runtime's).
+static const void *occupancy_instance(const sxfir_plan *p)
+{
+    const KernelTable &k = p->k;
+    switch (p->form ? p->form->geom : GEOM_GENERIC) {
+    case GEOM_MULTI: return p->blocks ? (const void *)k.blocks[0] : (const void *)k.dense;
+    case GEOM_WIDE: return (const void *)k.wide;
+    case GEOM_TILE: return (const void *)tile_kernel(p->ntaps, SXFIR_CF32);
+    case GEOM_IPASS: return (const void *)interp_kernel(p->ratio < 16 ? p->ratio : 16, SXFIR_CF32, false, false);
+    case GEOM_CX: return (const void *)k.cx;
+    case GEOM_CHAN4: return (const void *)k.chan4;
+    case GEOM_CHAN4X2: return (const void *)k.chan4x2;
+    case GEOM_SYN4: return (const void *)k.syn4;
+    case GEOM_SYN4X2: return (const void *)k.syn4x2;
+    }
+    return nullptr;
 }
 
 // resident workgroups per CU of a kernel; *occ keeps its default where the runtime has no answer
@@ -344,8 +430,17 @@ static void query_occupancy(int *occ, Fn kernel, int threads, size_t dynamic_lds
     if (kernel && hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kernel, threads, dynamic_lds) == hipSuccess && nb > 0) *occ = nb;
 }
 
-// ---- The creation frame.  A creator is: check_create_args, its own refusals, new_plan, its own fields and tap layout,
-// resolve_kernels and the occupancy of its tiled kernel, plan_to_device.  Every argument error comes before the device is looked at.
+// What every creator does once its form is settled: the plan's kernels, then the form's occupancy on this device
+static void resolve_form(sxfir_plan *p)
+{
+    resolve_kernels(p);
+    if (p->form) query_occupancy(&p->occ, occupancy_instance(p), p->form->threads);
+}
+
+#include "sxfir_prof_create.inc"   // the creators' prof_* hooks and the sxfir_debug_* entry points; empty in the production library
+
+// ---- The creation frame.  A creator is: check_create_args, its own refusals, new_plan, its own fields, set_form with the row of
+// its shape (or null), resolve_form, plan_to_device.  Every argument error comes before the device is looked at.
 
 // `ratio_name`: what the caller calls it ("ratio", "nbands")
 static int check_create_args(sxfir_plan **out, const float *taps, int mode, int ntaps, const char *ratio_name, int ratio, int nchan, int fmt)
@@ -395,11 +490,7 @@ static int new_plan(sxfir_plan **pp, int kind, int mode, int ntaps, int ratio, i
     p->kernel = SXFIR_KERNEL_AUTO;
     p->compute_units = prop.multiProcessorCount;
     p->thr2 = 1.0e-3f * 1.0e-3f;
-    p->oversub = 16;
-    p->occ_ext = 8;
-#ifdef SXFIR_PROFILING
-    p->join_drop = -1;
-#endif
+    p->tap_table = TAPS_NONE;
     *pp = p;
     return SXFIR_OK;
 }
@@ -443,10 +534,7 @@ static void free_plan(sxfir_plan *p)
     (void)hipFree(p->hist_alt);
     (void)hipFree(p->join_partials);
     (void)hipFree(p->join_arrived);
-#ifdef SXFIR_PROFILING
-    (void)hipFree(p->join_shadow);
-#endif
-    (void)hipFree(p->stamps_dev);          // the profiling build's clock stamps; null in the product
+    prof_free(p);
     delete p;
 }
 
@@ -456,24 +544,94 @@ static hipError_t upload(float **dev, const float *host, size_t n)
     return e != hipSuccess ? e : hipMemcpy(*dev, host, sizeof(float) * n, hipMemcpyHostToDevice);
 }
 
-// The plan's device memory: the tap table (`taps`: ntaps floats; `second`: p->ntaps floats for taps_scaled_dev too, in the layout
-// p->tap_table names), the two history buffers, the current one zeroed, and for /48 and /96 the join scratch.  The last step of
-// every creator: *out is the plan, or the plan is freed.
-static int plan_to_device(sxfir_plan **out, sxfir_plan *p, const float *taps, size_t ntaps, const float *second)
+// ---- The second tap table: one function per layout.  S32-word plans fold the wire words' 2^-31 into the taps a scalar-tap kernel reads.
+static const float TAPS_2_M31 = 4.656612873077393e-10f;       // 2^-31: exact
+static float word_scale(int fmt) { return fmt == SXFIR_S32 ? TAPS_2_M31 : 1.0f; }
+
+// the /4 scalar-tap kernels on S32 words (no other plan's kernel reads it): every tap times 2^-31, in tap order
+static void taps_scaled(std::vector<float> &t, const float *taps)
+{
+    for (size_t k = 0; k < t.size(); ++k) t[k] = taps[k] * TAPS_2_M31;
+}
+
+// decim_dense_kernel<8, ..., SUBSET>: subset s = 2c + p at 64 s, (jj, rr) at 4 jj + rr
+static void taps_subset8(std::vector<float> &t, const float *taps, int fmt)
+{
+    for (int c = 0; c < 2; ++c)
+        for (int ph = 0; ph < 2; ++ph)
+            for (int jj = 0; jj < 16; ++jj)
+                for (int rr = 0; rr < 4; ++rr) t[(size_t)(64 * (2 * c + ph) + 4 * jj + rr)] = taps[8 * (16 * ph + jj) + 4 * c + rr] * word_scale(fmt);
+}
+
+// decim_blocks_kernel: the taps rotated by `rot` (slot k' holds tap (k' + rot) mod ntaps); block b (columns 16 b .. 16 b + 15) at
+// 512 b, subset s = 2c + p at 64 s inside it, (jj, rr) at 4 jj + rr
+static void taps_blocks16(std::vector<float> &t, const float *taps, int ratio, int rot, int fmt)
+{
+    const int ntaps = (int)t.size();
+    for (int b = 0; b < ratio / 16; ++b)
+        for (int c = 0; c < 4; ++c)
+            for (int ph = 0; ph < 2; ++ph)
+                for (int jj = 0; jj < 16; ++jj)
+                    for (int rr = 0; rr < 4; ++rr) {
+                        const int slot = ratio * (16 * ph + jj) + 16 * b + 4 * c + rr;
+                        t[(size_t)(512 * b + 64 * (2 * c + ph) + 4 * jj + rr)] = taps[(slot + rot) % ntaps] * word_scale(fmt);
+                    }
+}
+
+// interp8_pass_kernel: phase block b at 32 ll b, pass (c, p) at 64 (2c + p) inside it, (jj, rr) at 4 jj + rr
+static void taps_pass8(std::vector<float> &t, const float *taps, int ratio)
+{
+    const int ll = ratio >= 16 ? 16 : ratio;            // phases per (block of the) pass kernel
+    for (int b = 0; b < ratio / ll; ++b)
+        for (int c = 0; c < ll / 4; ++c)                // x8: two phase groups; x4: one; x16 blocks: four
+            for (int ph = 0; ph < 2; ++ph)
+                for (int jj = 0; jj < 16; ++jj)
+                    for (int rr = 0; rr < 4; ++rr) t[(size_t)(32 * ll * b + 64 * (2 * c + ph) + 4 * jj + rr)] = taps[(16 * ph + jj) * ratio + ll * b + 4 * c + rr];
+}
+
+// synthesis4_kernel, synthesis4x2_kernel: h[ratio j + r] at jt r + j, jt the taps per phase (oversampled: per output parity)
+static void taps_phased(std::vector<float> &t, const float *taps, int ratio)
+{
+    const int jt = (int)t.size() / ratio;
+    for (int r = 0; r < ratio; ++r)
+        for (int j = 0; j < jt; ++j) t[(size_t)(jt * r + j)] = taps[ratio * j + r];
+}
+
+// p->ntaps floats in the layout p->tap_table names
+static std::vector<float> second_tap_table(const sxfir_plan *p, const float *taps)
+{
+    std::vector<float> t(taps, taps + p->ntaps);
+    switch (p->tap_table) {
+    case TAPS_SCALED: taps_scaled(t, taps); break;
+    case TAPS_SUBSET8: taps_subset8(t, taps, p->fmt); break;
+    case TAPS_BLOCKS16: taps_blocks16(t, taps, p->ratio, p->rot, p->fmt); break;
+    case TAPS_PASS8: taps_pass8(t, taps, p->ratio); break;
+    case TAPS_PHASED: taps_phased(t, taps, p->ratio); break;
+    }
+    return t;
+}
+
+// The plan's device memory: the tap table (`taps`: n_taps floats) and, unless p->tap_table is TAPS_NONE, the second one in that
+// layout (from the same `taps`: p->ntaps real taps), the two history buffers, the current one zeroed, and for the block form the
+// join scratch -- for calls of at most eight times as many tiles as the chip has workgroup slots unless the creator set another
+// figure.  Measured (tools/split_ab.sh, profiles/round6_split_ab.txt): against the walking form the dealt form takes 2.9 x less
+// time at 2^22 samples (/96), -39 % at 2^24, -15 % at 2^26 (2731 / 1366 tiles), -6 % at 5.3 x slots and +2 .. +5 % at 10.7 x slots
+// (2^28 samples at /96: the walking form keeps a tile's halo in one XCD's L2 and pays one prologue per eight tiles).  Scratch:
+// 4096 tiles x blocks x 4 KiB = 48 / 96 MiB per plan.  The last step of every creator: *out is the plan, or the plan is freed.
+static int plan_to_device(sxfir_plan **out, sxfir_plan *p, const float *taps, size_t n_taps)
 {
     const size_t hist_bytes = sample_bytes(p->fmt) * (size_t)p->hist_len * (size_t)p->nchan;
-    hipError_t e = upload(&p->taps_dev, taps, ntaps);
-    if (e == hipSuccess && second) e = upload(&p->taps_scaled_dev, second, (size_t)p->ntaps);
+    hipError_t e = upload(&p->taps_dev, taps, n_taps);
+    if (e == hipSuccess && p->tap_table != TAPS_NONE) e = upload(&p->taps_scaled_dev, second_tap_table(p, taps).data(), (size_t)p->ntaps);
     if (e == hipSuccess) e = hipMalloc(&p->hist_dev, hist_bytes);
     if (e == hipSuccess) e = hipMalloc(&p->hist_alt, hist_bytes);
     if (e == hipSuccess) e = hipMemset(p->hist_dev, 0, hist_bytes);
     if (e == hipSuccess && p->blocks) {
+        if (!p->join_tiles) p->join_tiles = 8LL * p->compute_units * p->occ;
         e = hipMalloc(&p->join_partials, (size_t)p->join_tiles * (size_t)p->blocks * 4096);
         if (e == hipSuccess) e = hipMalloc((void **)&p->join_arrived, sizeof(unsigned) * (size_t)p->join_tiles);
         if (e == hipSuccess) e = hipMemset(p->join_arrived, 0, sizeof(unsigned) * (size_t)p->join_tiles);
-#ifdef SXFIR_PROFILING
-        if (e == hipSuccess && p->join_drop >= 0) e = hipMalloc(&p->join_shadow, (size_t)p->join_tiles * 4096);
-#endif
+        if (e == hipSuccess) e = prof_alloc(p);
     }
     if (e != hipSuccess) {
         free_plan(p);
@@ -502,27 +660,21 @@ static int create_band_plan(sxfir_plan **out, int kind, const char *what, const 
     if (int rc = new_plan(&p, kind, mode, ntaps, ratio, nchan, fmt, device)) return rc;
     p->bands = nbands;
     p->oversample = oversample;
-    p->ext_tiled = fmt == SXFIR_CF32 && ntaps == 128;
-    const int jt = ntaps / ratio;                           // a synthesizer's taps per phase (oversampled: per output parity)
-    std::vector<float> phased(syn ? (size_t)ntaps : 0);     // a synthesizer's second tap table
+    const PlanForm *form = &BAND_FORMS[syn][oversample == 2];
+    p->tap_table = form->taps;                              // (a synthesizer's phase-major table, whether or not its tiled kernel takes the plan)
     if (syn) {
+        const int jt = ntaps / ratio;                       // taps per phase (oversampled: per output parity)
         p->hist_len = nbands * ((jt + 1) & ~1);             // per channel: a x ratio interpolator's history for every band, band k's at k * hist_len / 4
         real_tap_contract(p);                               // a phase's sum: the real-tap interpolator's
-        // the phase-major table of the tiled kernels: h[ratio j + r] at jt r + j
-        p->tap_table = TAPS_PHASED;
-        for (int r = 0; r < ratio; ++r)
-            for (int j = 0; j < jt; ++j) phased[(size_t)(jt * r + j)] = taps[ratio * j + r];
     } else {
         p->hist_len = ntaps;                                // (a multiple of 4)
         // the numeric contract of a branch sum: one chain per phase, no tree, no rotation
         p->jsplit = 1;
         p->cw = 1;
     }
-    resolve_kernels(p);
-    if (p->form->geom == GEOM_SYN4X2) p->occ_ext = 5;       // (where the runtime has no answer; its answer replaces it)
-    const KernelTable &k = p->k;                            // the form's tiled kernel: at most one of the four is set
-    query_occupancy(&p->occ_ext, k.chan4 ? (const void *)k.chan4 : k.chan4x2 ? (const void *)k.chan4x2 : k.syn4 ? (const void *)k.syn4 : (const void *)k.syn4x2, 64);
-    return plan_to_device(out, p, taps, (size_t)ntaps, syn ? phased.data() : nullptr);
+    set_form(p, fmt == SXFIR_CF32 && ntaps == 128 ? form : nullptr);       // the shape the tiled kernels take
+    resolve_form(p);
+    return plan_to_device(out, p, taps, (size_t)ntaps);
 }
 
 // The _os creators' own argument, checked behind check_create_args and in front of create_band_plan: its range, and the two values
@@ -591,294 +743,25 @@ int sxfir_create(sxfir_plan **out, int mode, const float *taps, int ntaps, int r
         return fail(SXFIR_EINVAL, "interpolator needs ntaps %% ratio == 0 (%d, %d)", ntaps, ratio);
     sxfir_plan *p = nullptr;
     if (int rc = new_plan(&p, KIND_REAL, mode, ntaps, ratio, nchan, fmt, device)) return rc;
-    p->occ_ipass = 16;
-    p->ipass_qi = 2;
     p->symmetric = true;
     for (int k = 0; k < ntaps / 2; ++k)
         if (memcmp(&taps[k], &taps[ntaps - 1 - k], sizeof(float)) != 0) p->symmetric = false;
-    p->blocks_split = true;
-    p->ipass_split = true;
     real_tap_contract(p);
-
-    if (mode == SXFIR_DECIMATE) {
-        p->hist_len = (ntaps + 1) & ~1;
-        // CF16 storage at /4 with 128 taps: the wide kernel with the typed-DMA front end (round 5)
-        const bool half4_wide = fmt == SXFIR_CF16 && ratio == 4 && ntaps == 128;
-        p->tile_capable = ((fmt == SXFIR_CF32 && ratio == 4 && (ntaps == 128 || ntaps == 64)) ||
-                           (fmt == SXFIR_S32 && ratio == 4 && ntaps == 128) || half4_wide);
-        // multi-column kernel: 32 taps per phase; CF32 at ratio 8/16/32, CF16 at ratio 4/8/16/32
-        p->multi_capable = (ntaps == 32 * ratio) && !half4_wide &&
-                           (((fmt == SXFIR_CF32 || fmt == SXFIR_S32) && (ratio == 8 || ratio == 16 || ratio == 32)) ||
-                            (fmt == SXFIR_CF16 && (ratio == 4 || ratio == 8 || ratio == 16 || ratio == 32)));
-        // /48 and /96 with 32 taps per phase (the rotated contract): decim_blocks_kernel on CF32, S32 words and CF16 storage
-        p->blocks = p->rot ? ratio / 16 : 0;
-#ifdef SXFIR_PROFILING
-        // experiment (round 6): /16 and /32 CF32 through the sixteen-column-block form too (one / two blocks per row, scalar taps,
-        // the ROTATED contract, or with SXFIR_BLOCKS_SMALL=2 the unrotated one): would config 5's shape gain what /48 and /96
-        // gained over the VGPR-tap dense kernel?
-        if (getenv("SXFIR_BLOCKS_SMALL") && atoi(getenv("SXFIR_BLOCKS_SMALL")) && fmt == SXFIR_CF32 && ntaps == 32 * ratio &&
-            (ratio == 16 || ratio == 32)) {
-            p->blocks = ratio / 16;
-            p->blocks_split = false;
-            p->rot = atoi(getenv("SXFIR_BLOCKS_SMALL")) == 2 ? 0 : 1;
-        }
-#endif
-        if (p->blocks) p->multi_capable = true;
-    } else {
-        p->hist_len = (ntaps / ratio + 1) & ~1;
-        // (x48, x96 -- the reference's rates master clock / 768 and / 1536 -- as three / six phase blocks of the x16 kernel)
-        // (CF16 storage, round 5: interp_tile_kernel<.., HALF> at every one of these ratios)
-        p->itile_capable = ((fmt == SXFIR_CF32 || fmt == SXFIR_S32 || fmt == SXFIR_CF16) && ntaps == 32 * ratio &&
-                            (ratio == 4 || ratio == 8 || ratio == 16 || ratio == 32 || ratio == 48 || ratio == 96));
+    p->hist_len = mode == SXFIR_DECIMATE ? (ntaps + 1) & ~1 : (ntaps / ratio + 1) & ~1;
+    set_form(p, settle_form(mode, ratio, ntaps, fmt, p->symmetric));
+    p->blocks_split = p->ipass_split = true;
+    prof_settle(p);                     // (profiling: the knobs that ask for another form or contract)
+    // the layout follows the form the plan will launch, not the shape: a plan whose /8 scalar-tap form was switched off
+    // (profiling knobs) keeps the plain table
+    p->tap_table = p->form ? p->form->taps : TAPS_SCALED;
+    p->blocks = p->tap_table == TAPS_BLOCKS16 ? ratio / 16 : 0;
+    resolve_form(p);
+    if (int rc = prof_resolved(p)) {    // (profiling: the variants' instances, occupancies and schedules)
+        free_plan(p);
+        return rc;
     }
-
-    // measured on MI355X (tools/kbench.py): single-buffered LDS-DMA at 16 waves/CU, 16 generations
-    // of short-lived waves (4 tiles each at 2^28 samples), strided XCD-blocked passes; the
-    // double-buffered variant at 8 waves/CU and long contiguous runs are slower
-    p->occ_sb = p->occ_db = 8;
-    // waves per workgroup of the multi-column kernel, measured (tools/kbench.py, KB_D, specs "w1".."w8"):
-    // the choice that brings the LDS image down to 10 KiB per wave (16 waves per CU) while the 31-row
-    // halo stays a small part of the staging
-    p->multi_waves = ratio <= 4 ? 1 : 4;
-    p->multi_ps = 2;
-    // CF32 / S32 words at ratio 8, 16, 32: the linear-image form (sxfir_decim_dense.hip.h); CF16 and ratio 4 keep
-    // the multi-column kernel
-    // ... and, since round 5, CF16 storage at /32 (BASELINE config 5's fp16 leg): the dense kernel with the typed LDS-DMA front end
-    // (HALFIN: the texture path converts half -> float on the way into the same CF32 image; no conversions in the FIR)
-    p->dense32 = p->multi_capable && !p->blocks && (ratio == 8 || ratio == 16 || ratio == 32);
-    // /8 CF32: the scalar-tap form of the dense kernel (tap subsets on the four waves, round 4: 4.4-5 % less time)
-    p->dense_subset = p->dense32 && ratio == 8;      // (CF16 storage too, round 5: the typed-DMA front end under the same scalar-tap FIR)
-    p->occ_pair = 8;
-    p->occ_wide = 8;
-    p->occ_multi = 2;
-    // generations of workgroups per launch, measured (tools/kbench.py): the multi-column kernel's prologue
-    // (64 taps and the DMA offset table per lane) is heavier than the tile kernel's, 8 beats 16; the
-    // interpolator is flat between 2 and 16 (tools/ibench.py)
-    if (p->multi_capable) p->oversub = 8;
-    if (p->itile_capable) p->oversub = ratio > 32 ? 2 : 4;     // (x48, x96: 2 measured 1-2 % ahead of 4 .. 32, profiles/round5_rates.txt)
-    // CF32 / S32 words: the scalar-tap pass kernel (interp8_pass_kernel) at every ratio -- x8 (two inputs per lane, four passes per
-    // tile; 4 / 8 / 16 generations measured within 0.3 %, tools/ibench2.py), x4 (round 5: four inputs per lane, two passes) and
-    // x16 .. x96 (round 5: ratio / 16 phase blocks of sixteen per tile, a lane's sixteen outputs per input and block are one line:
-    // 8-9 % less time than interp_tile_kernel, which keeps CF16 storage, profiles/round5_rates.txt)
-    if (p->itile_capable && fmt != SXFIR_CF16) {
-        p->ipass = true;
-        p->ipass_qi = ratio == 4 ? 4 : 2;
-        p->oversub = 8;
-        query_occupancy(&p->occ_ipass, interp_kernel(ratio < 16 ? ratio : 16, SXFIR_CF32, false, false), 64);
-    }
-#ifdef SXFIR_PROFILING
-    // A/B knobs of the profiling build.  The production library never looks at the environment.
-    if (const char *v = getenv("SXFIR_TILE_VARIANT")) {
-        if (strcmp(v, "mu") == 0 && mode == SXFIR_DECIMATE && fmt == SXFIR_CF32 && ratio == 4 && ntaps == 128) {
-            p->multi_capable = true;        // the multi-column kernel at D = 4 instead of decim4_tile_kernel
-            p->tile_capable = false;
-            p->oversub = 8;
-        }
-    }
-    if (const char *v = getenv("SXFIR_DENSE")) p->dense32 = p->dense32 && atoi(v) != 0;
-    if (const char *v = getenv("SXFIR_IPASS")) {     // 0: interp_tile_kernel at x8 too (A/B); 4: four inputs per lane
-        p->ipass = p->ipass && atoi(v) != 0;
-        if (p->ipass && atoi(v) == 4 && ratio == 8) {
-            p->ipass_qi = 4;
-            query_occupancy(&p->occ_ipass, sxfir::interp8_pass_kernel<4>, 64);
-        }
-    }
-    if (const char *v = getenv("SXFIR_IPASS_WAIT0")) p->ipass_wait0 = atoi(v) != 0;
-    if (const char *v = getenv("SXFIR_IPASS_SPLIT")) p->ipass_split = atoi(v) != 0;
-    if (const char *v = getenv("SXFIR_DENSE_NT")) { p->dense_nt = atoi(v); p->dense_nt_set = 1; }
-    if (const char *v = getenv("SXFIR_DENSE_HC")) p->dense_hc = atoi(v) != 0;
-    if (const char *v = getenv("SXFIR_DENSE_SUBSET")) p->dense_subset = p->dense_subset && atoi(v) != 0;     // 0: the VGPR-tap form (A/B)
-    if (!p->dense32) p->dense_subset = false;
-    if (getenv("SXFIR_MULTI_PS") || getenv("SXFIR_MULTI_W")) p->dense32 = false;   // those knobs belong to the multi-column kernel
-    if (p->multi_capable && fmt != SXFIR_S32 && !p->dense32) {
-        if (const char *v = getenv("SXFIR_MULTI_PS")) p->multi_ps = atoi(v) == 4 ? 4 : 2;
-        if (p->multi_ps == 4) p->multi_waves = ratio <= 4 ? 2 : (ratio == 8 ? 4 : 8);
-        if (const char *v = getenv("SXFIR_MULTI_W")) p->multi_waves = atoi(v);
-        p->jsplit = p->multi_ps;
-    }
-    if (p->multi_capable || p->itile_capable || p->tile_capable) {
-        if (const char *v = getenv("SXFIR_OVERSUB")) p->oversub = atoi(v) > 0 ? atoi(v) : 1;
-    }
-    if (p->multi_capable || p->tile_capable) {
-        if (const char *v = getenv("SXFIR_ABLATE")) p->ablate = atoi(v);
-    }
-#endif
-    resolve_kernels(p);
-    if (p->multi_capable) {
-        // resident workgroups per CU: LDS is the limiter (checked against the occupancy API below)
-        const int W = p->multi_waves;
-        const void *k = p->blocks ? (const void *)p->k.blocks[0] : (const void *)p->k.dense;
-#ifdef SXFIR_PROFILING
-        if (p->blocks && p->blocks < 3) {       // (the unrotated instances have the same resources)
-            k = p->blocks == 1 ? (const void *)sxfir::decim_blocks_kernel<1, false, true, false, false, true> : (const void *)sxfir::decim_blocks_kernel<2, false, true, false, false, true>;
-        } else if (!p->blocks && !p->dense32 && fmt == SXFIR_S32) {   // wire-word input: one instantiation per ratio (4 waves, 2-way row split)
-            k = ratio == 8    ? (const void *)sxfir::decim_multi_kernel<8, 4, false, 0, 2, true>
-                : ratio == 16 ? (const void *)sxfir::decim_multi_kernel<16, 4, false, 0, 2, true>
-                              : (const void *)sxfir::decim_multi_kernel<32, 4, false, 0, 2, true>;
-        } else if (!p->blocks && !p->dense32) {
-            switch (SXFIR_MULTI_KEY(ratio, W, fmt == SXFIR_CF16, p->multi_ps)) {
-#define SXFIR_X(DD, WW, HH, PP) \
-            case SXFIR_MULTI_KEY(DD, WW, HH, PP): k = (const void *)sxfir::decim_multi_kernel<DD, WW, HH, 0, PP>; break;
-                SXFIR_MULTI_VARIANTS(SXFIR_X)
-#undef SXFIR_X
-            }
-        }
-#endif
-        if (!k) {
-            free_plan(p);
-            return fail(SXFIR_EUNSUPPORTED, "no multi-column kernel for ratio %d with %d waves per workgroup", ratio, W);
-        }
-        query_occupancy(&p->occ_multi, k, 64 * W);
-    }
-    if (p->blocks) {
-        // calls of at most eight times as many tiles as the chip has workgroup slots are dealt as (tile, block) items (SPLIT).
-        // Measured (tools/split_ab.sh, profiles/round6_split_ab.txt): against the walking form the dealt form takes 2.9 x less time at
-        // 2^22 samples (/96), -39 % at 2^24, -15 % at 2^26 (2731 / 1366 tiles), -6 % at 5.3 x slots and +2 .. +5 % at 10.7 x slots
-        // (2^28 samples at /96: the walking form keeps a tile's halo in one XCD's L2 and pays one prologue per eight tiles).
-        // Scratch: 4096 tiles x blocks x 4 KiB = 48 / 96 MiB per plan.
-        p->join_tiles = 8LL * p->compute_units * p->occ_multi;
-#ifdef SXFIR_PROFILING
-        if (const char *v = getenv("SXFIR_BLOCKS_SPLIT")) {     // 0: off; n >= 1: dealt while a call has at most n x slots tiles
-            p->blocks_split = atoi(v) != 0;
-            if (atoi(v) > 1) p->join_tiles = (long long)atoi(v) * p->compute_units * p->occ_multi;
-        }
-        // test hook: a hand-off that never arrives (tests/test_gpu_join.py proves with it that its checker sees one)
-        if (const char *v = getenv("SXFIR_BLOCKS_JOIN_DROP")) p->join_drop = (atoi(v) >= 0 && atoi(v) < p->blocks) ? atoi(v) : -1;
-#endif
-    }
-    if (p->tile_capable) {
-        // the 4-outputs-per-lane kernels (the CF32 instance's figure: see the kernel table) -- and, in the profiling build, round 3's
-        // scalar-tap form for 128 symmetric taps ("t2s"), the A/B partner of the wide kernel that replaced it
-        const void *ksb = (const void *)tile_kernel(ntaps, SXFIR_CF32);
-#ifdef SXFIR_PROFILING
-        if (ntaps == 128 && p->symmetric)
-            ksb = fmt == SXFIR_S32 ? (const void *)sxfir::decim4_tile2_kernel<128, 1, sxfir::T2_SHIPPED, 0, true>
-                                   : (const void *)sxfir::decim4_tile2_kernel<128, 1, sxfir::T2_SHIPPED>;
-#endif
-        query_occupancy(&p->occ_sb, ksb, 64);
-        // 128 taps: the wide kernel, for bit-symmetric taps and (its ASYM form) for CF16 storage
-        p->wide8 = p->k.wide != nullptr;
-        query_occupancy(&p->occ_wide, p->k.wide, 64);
-#ifdef SXFIR_PROFILING
-        if (!p->k.wide && ntaps == 128 && getenv("SXFIR_WIDE_ASYM") && atoi(getenv("SXFIR_WIDE_ASYM"))) {
-            p->wide8 = true;                                   // A/B: the wide kernel's ASYM form on CF32 / S32 words
-            p->k.wide = fmt == SXFIR_S32 ? sxfir::decim4_wide_kernel<0, true, 24, true, false, 0, false, true>
-                                         : sxfir::decim4_wide_kernel<0, false, 24, true, false, 0, false, true>;
-            query_occupancy(&p->occ_wide, p->k.wide, 64);
-        }
-        if (ntaps == 128) {
-            const void *kp = fmt == SXFIR_S32 ? (const void *)sxfir::decim4_pair_kernel<0, true> : (const void *)sxfir::decim4_pair_kernel<0, false>;
-            query_occupancy(&p->occ_pair, kp, 128);
-        }
-        const void *kdb = ntaps == 128 ? (const void *)sxfir::decim4_tile_kernel<128, true>
-                                       : (const void *)sxfir::decim4_tile_kernel<64, true>;
-        query_occupancy(&p->occ_db, kdb, 64);
-        if (const char *v = getenv("SXFIR_TILE_VARIANT")) {
-            p->tile_dbuf = (strcmp(v, "db") == 0);
-            // "sb", "db", "sg": the first-generation tile kernel (taps in VGPR pairs) also for symmetric taps
-            if (strcmp(v, "sb") == 0 || strcmp(v, "db") == 0 || strncmp(v, "sg", 2) == 0) { p->symmetric = false; p->wide8 = false; }
-            // "t2s": round 3's shipped form (decim4_tile2_kernel, T2_SHIPPED) as the A/B partner of the wide kernel
-            if (strcmp(v, "t2s") == 0) p->wide8 = false;
-            p->sgpr_r = strcmp(v, "sg") == 0 ? 8 : (strcmp(v, "sg4") == 0 ? 4 : 0);
-            if (p->sgpr_r && ntaps == 128) {
-                const void *k = p->sgpr_r == 8 ? (const void *)sxfir::decim4_sgpr_kernel<8>
-                                               : (const void *)sxfir::decim4_sgpr_kernel<4>;
-                query_occupancy(&p->occ_sb, k, 64);
-            }
-            // "wide": decim4_wide_kernel (sxfir_decim_wide.hip.h), symmetric taps only
-            if (strncmp(v, "wide", 4) == 0 && ntaps == 128 && p->symmetric) {
-                p->wide = true;
-                p->wide_nt = strncmp(v, "wident", 6) == 0;
-                p->wide_pin = strncmp(v, "widentp", 7) == 0;
-                p->wide_nb = atoi(v + (p->wide_pin ? 7 : (p->wide_nt ? 6 : 4)));
-                // "widepol<hex>": the shipped build (wident24) with another cache policy (sxfir_decim_wide.hip.h, POL)
-                if (strncmp(v, "widepol", 7) == 0) {
-                    p->wide_nt = true;
-                    p->wide_nb = 24;
-                    p->wide_pol = (int)strtol(v + 7, nullptr, 16);
-                }
-                // SXFIR_LDS_PAD: dynamic LDS bytes on top of the kernel's own image: fewer waves fit a CU (a probe: what would a
-                // form with a larger tile per wave -- 16 outputs per lane, 34 KB -- have left of the latency hiding?)
-                if (const char *lp = getenv("SXFIR_LDS_PAD")) {
-                    p->lds_pad = atoi(lp) > 0 ? atoi(lp) : 0;
-                    if (p->lds_pad) query_occupancy(&p->occ_wide, sxfir::decim4_wide_kernel<0, false, 24, true>, 64, (size_t)p->lds_pad);
-                }
-            }
-            // "pair": decim4_pair_kernel (sxfir_decim_pair.hip.h)
-            if (strncmp(v, "pair", 4) == 0 && ntaps == 128) {
-                p->pair = true;
-                p->pair_xsep = strcmp(v, "pairx") == 0;
-                if (p->pair_xsep) p->occ_pair = 7;
-            }
-            // "t2:<waves per workgroup>:<option bits>": decim4_tile2_kernel (sxfir_decim_tile2.hip.h)
-            if (strncmp(v, "t2:", 3) == 0 && ntaps == 128 && fmt == SXFIR_CF32) {
-                int wpg = 0, opt = 0;
-                if (sscanf(v + 3, "%d:%d", &wpg, &opt) == 2) {
-                    const void *k = nullptr;
-                    switch (wpg * 100 + opt) {
-#define SXFIR_X(WW, OO) case WW * 100 + OO: k = (const void *)sxfir::decim4_tile2_kernel<128, WW, OO>; break;
-                        SXFIR_TILE2_VARIANTS(SXFIR_X)
-#undef SXFIR_X
-                    }
-                    if (!k || ((opt & sxfir::T2_SCALAR) && !p->symmetric)) {
-                        free_plan(p);
-                        return fail(SXFIR_EUNSUPPORTED, "no tile2 variant %d:%d for these taps", wpg, opt);
-                    }
-                    p->t2_wpg = wpg;
-                    p->t2_opt = opt;
-                    // SXFIR_LDS_PAD: dynamic LDS bytes on top of the kernel's own image: fewer waves fit a CU
-                    if (const char *lp = getenv("SXFIR_LDS_PAD")) p->lds_pad = atoi(lp) > 0 ? atoi(lp) : 0;
-                    // occ_sb = resident WAVES per CU of this variant
-                    int nb = 0;
-                    query_occupancy(&nb, k, 64 * wpg, (size_t)p->lds_pad);
-                    if (nb > 0) p->occ_sb = nb * wpg;
-                }
-            }
-        }
-        if (const char *v = getenv("SXFIR_SCHED")) p->sched = atoi(v);
-        if (const char *v = getenv("SXFIR_OCC")) {
-            if (atoi(v) > 0) p->occ_sb = p->occ_db = atoi(v);
-        }
-#endif
-    }
-
-    std::vector<float> scaled(taps, taps + ntaps);
-    for (int k = 0; k < 64; ++k) p->taps_k[k] = k < ntaps ? (fmt == SXFIR_S32 ? taps[k] * 4.656612873077393e-10f : taps[k]) : 0.0f;
-    // the layout follows the kernel the plan will launch (the same flags launch_decim / launch_interp branch on),
-    // not the shape: a plan whose /8 scalar-tap form was switched off (profiling knobs) keeps the plain table
-    p->tap_table = p->blocks ? TAPS_BLOCKS16 : p->dense_subset ? TAPS_SUBSET8 : (mode == SXFIR_INTERPOLATE && p->ipass) ? TAPS_PASS8 : TAPS_SCALED;
-    if (p->tap_table == TAPS_SUBSET8) {
-        // /8 scalar-tap form (decim_dense_kernel<8, ..., SUBSET>): subset s = 2c + p at 64 s, (jj, rr) at 4 jj + rr
-        for (int c = 0; c < 2; ++c)
-            for (int ph = 0; ph < 2; ++ph)
-                for (int jj = 0; jj < 16; ++jj)
-                    for (int rr = 0; rr < 4; ++rr)
-                        scaled[(size_t)(64 * (2 * c + ph) + 4 * jj + rr)] =
-                            taps[8 * (16 * ph + jj) + 4 * c + rr] * (fmt == SXFIR_S32 ? 4.656612873077393e-10f : 1.0f);   // 2^-31: exact
-    } else if (p->tap_table == TAPS_BLOCKS16) {
-        // decim_blocks_kernel: the ROTATED taps (slot k' holds tap (k' + 1) mod ntaps); block b (columns 16 b .. 16 b + 15)
-        // at 512 b, subset s = 2c + p at 64 s inside it, (jj, rr) at 4 jj + rr
-        for (int b = 0; b < p->blocks; ++b)
-            for (int c = 0; c < 4; ++c)
-                for (int ph = 0; ph < 2; ++ph)
-                    for (int jj = 0; jj < 16; ++jj)
-                        for (int rr = 0; rr < 4; ++rr) {
-                            const int slot = ratio * (16 * ph + jj) + 16 * b + 4 * c + rr;
-                            scaled[(size_t)(512 * b + 64 * (2 * c + ph) + 4 * jj + rr)] =
-                                taps[(slot + p->rot) % ntaps] * (fmt == SXFIR_S32 ? 4.656612873077393e-10f : 1.0f);
-                        }
-    } else if (p->tap_table == TAPS_PASS8) {
-        const int ll = ratio >= 16 ? 16 : ratio;            // phases per (block of the) pass kernel
-        for (int b = 0; b < ratio / ll; ++b)
-        for (int c = 0; c < ll / 4; ++c)                    // x8: two phase groups; x4: one; x16 blocks: four
-            for (int ph = 0; ph < 2; ++ph)
-                for (int jj = 0; jj < 16; ++jj)
-                    for (int rr = 0; rr < 4; ++rr)
-                        scaled[(size_t)(32 * ll * b + 64 * (2 * c + ph) + 4 * jj + rr)] = taps[(16 * ph + jj) * ratio + ll * b + 4 * c + rr];
-    } else {
-        for (float &t : scaled) t *= 4.656612873077393e-10f;      // 2^-31: exact
-    }
-    return plan_to_device(out, p, taps, (size_t)ntaps, scaled.data());
+    for (int k = 0; k < 64; ++k) p->taps_k[k] = k < ntaps ? taps[k] * word_scale(fmt) : 0.0f;
+    return plan_to_device(out, p, taps, (size_t)ntaps);
 }
 
 int sxfir_destroy(sxfir_plan *p)
@@ -928,7 +811,7 @@ int sxfir_set_kernel(sxfir_plan *p, int kernel)
 {
     if (!p) return fail(SXFIR_EINVAL, "plan is NULL");
     if (kernel < SXFIR_KERNEL_AUTO || kernel > SXFIR_KERNEL_GENERIC) return fail(SXFIR_EINVAL, "bad kernel id");
-    if (kernel == SXFIR_KERNEL_TILED && !p->tile_capable && !p->multi_capable && !p->itile_capable && !p->ext_tiled)
+    if (kernel == SXFIR_KERNEL_TILED && !p->form)
         return fail(SXFIR_EUNSUPPORTED, "no tiled kernel for ntaps=%d ratio=%d fmt=%d mode=%d", p->ntaps,
                     p->ratio, p->fmt, p->mode);
     p->kernel = kernel;
@@ -941,65 +824,6 @@ int sxfir_set_tx_threshold(sxfir_plan *p, float tx_threshold2)
     p->thr2 = tx_threshold2;
     return SXFIR_OK;
 }
-
-#ifdef SXFIR_PROFILING
-// Diagnostic (SXFIR_ABLATE=11/12 builds): median in-kernel shader clock in MHz of the last launch.
-int sxfir_debug_clock(sxfir_plan *p, double *mhz)
-{
-    if (!p || !mhz || !p->stamps_dev) return fail(SXFIR_EINVAL, "no stamps recorded");
-    std::vector<unsigned long long> h(2 * p->stamps_n);
-    HIPCHECK(hipMemcpy(h.data(), p->stamps_dev, 16 * p->stamps_n, hipMemcpyDeviceToHost));
-    std::vector<double> f;
-    for (size_t i = 0; i < p->stamps_n; ++i)
-        if (h[2 * i + 1] > 0) f.push_back(100.0 * (double)h[2 * i] / (double)h[2 * i + 1]);
-    if (f.empty()) return fail(SXFIR_EINVAL, "no stamps recorded");
-    std::sort(f.begin(), f.end());
-    *mhz = f[f.size() / 2];
-    return SXFIR_OK;
-}
-
-int sxfir_debug_stamps(sxfir_plan *p, unsigned long long *host, size_t capacity_records, size_t *n_records)
-{
-    if (!p || !host || !n_records || !p->stamps_dev || (p->ablate != 3 && p->ablate != 5)) return fail(SXFIR_EINVAL, "no stamps recorded");
-    const size_t n = p->stamps_n < capacity_records ? p->stamps_n : capacity_records;
-    // records: 5 x uint64 (multi-column kernel, ablate 3) or 8 x uint64 (tile2 kernel, ablate 5)
-    HIPCHECK(hipMemcpy(host, p->stamps_dev, (p->ablate == 5 ? 64 : 40) * n, hipMemcpyDeviceToHost));
-    *n_records = n;
-    return SXFIR_OK;
-}
-
-// Test hooks of the (tile, block) join of decim_blocks_kernel<..., SPLIT> (tests/gpu_util.py, tools/soak_split.py).
-int sxfir_debug_join_poison(sxfir_plan *p, uint32_t word, void *stream)
-{
-    if (!p) return fail(SXFIR_EINVAL, "plan is NULL");
-    if (!p->join_partials) return fail(SXFIR_EUNSUPPORTED, "this plan has no join scratch");
-    HIPCHECK(hipMemsetD32Async((hipDeviceptr_t)p->join_partials, (int)word, (size_t)p->join_tiles * (size_t)p->blocks * 1024, S(stream)));
-    return SXFIR_OK;
-}
-
-int sxfir_debug_join_counters(sxfir_plan *p, long long *nonzero, void *stream)
-{
-    if (!p || !nonzero) return fail(SXFIR_EINVAL, "NULL argument");
-    if (!p->join_arrived) return fail(SXFIR_EUNSUPPORTED, "this plan has no join scratch");
-    std::vector<unsigned> h((size_t)p->join_tiles);
-    HIPCHECK(hipMemcpyAsync(h.data(), p->join_arrived, sizeof(unsigned) * h.size(), hipMemcpyDeviceToHost, S(stream)));
-    HIPCHECK(hipStreamSynchronize(S(stream)));
-    long long n = 0;
-    for (unsigned v : h) n += v != 0;
-    *nonzero = n;
-    return SXFIR_OK;
-}
-
-int sxfir_debug_join_set_counter(sxfir_plan *p, long long tile_index, unsigned value, void *stream)
-{
-    if (!p) return fail(SXFIR_EINVAL, "plan is NULL");
-    if (!p->join_arrived) return fail(SXFIR_EUNSUPPORTED, "this plan has no join scratch");
-    if (tile_index < 0 || tile_index >= p->join_tiles) return fail(SXFIR_EINVAL, "tile %lld of %lld", tile_index, p->join_tiles);
-    HIPCHECK(hipMemsetD32Async((hipDeviceptr_t)(p->join_arrived + tile_index), (int)value, 1, S(stream)));
-    return SXFIR_OK;
-}
-
-#endif  // SXFIR_PROFILING
 
 int sxfir_contract(const sxfir_plan *p, int *jsplit, int *cw)
 {

@@ -1,7 +1,7 @@
 // Launch tables of the profiling build (libsxfir_prof.so, -DSXFIR_PROFILING): kernel A/B variants, ablation modes and
-// phase stamps, selected by the SXFIR_* environment knobs (most of them read in sxfir_create).  Included by
-// sxfir_launch.hip.h in front of its geometry and launch functions, which call these hooks and otherwise read straight
-// through; in libsxfir.so every hook is the empty inline function at the end of this file.
+// phase stamps, selected by the SXFIR_* environment knobs (read at plan creation into the plan's ProfKnobs member:
+// sxfir_prof_create.inc).  Included by sxfir_launch.hip.h in front of its geometry and launch functions, which call these
+// hooks and otherwise read straight through; in libsxfir.so every hook is the empty inline function at the end of this file.
 //
 // Every prof_launch_* returns 0 when the plan asks for nothing of its kind (the product launch goes on), 1 when it
 // has launched the kernel, and a negative SXFIR_E* code on an error.
@@ -9,8 +9,7 @@
 
 static int prof_oversub_forced() { return getenv("SXFIR_OVERSUB") != nullptr; }              // the knob means what it says
 
-// decim4_sgpr_kernel<R>: tiles of 64 R outputs
-static long long prof_tile_out(const sxfir_plan *p, long long tile_out) { return (p->sgpr_r && p->ntaps == 128) ? 64 * p->sgpr_r : tile_out; }
+static int prof_sched(const sxfir_plan *p) { return p->prof.sched; }                          // SXFIR_SCHED
 
 // SXFIR_IBLOCK16=1: x96 on CF32 as six phase blocks of the x16 tile kernel instead of three of the x32 one
 static int prof_iblock16(const sxfir_plan *p, bool keyed, int base_l)
@@ -21,10 +20,10 @@ static int prof_iblock16(const sxfir_plan *p, bool keyed, int base_l)
 // stamp records for `need` waves of `bytes_per_record` bytes each (kept with the plan, regrown on demand)
 static int prof_stamps(sxfir_plan *p, size_t need, size_t bytes_per_record, unsigned long long **out)
 {
-    if (p->stamps_dev && p->stamps_n < need) { (void)hipFree(p->stamps_dev); p->stamps_dev = nullptr; }
-    if (!p->stamps_dev) HIPCHECK(hipMalloc(&p->stamps_dev, bytes_per_record * need));
-    p->stamps_n = need;
-    *out = (unsigned long long *)p->stamps_dev;
+    if (p->prof.stamps_dev && p->prof.stamps_n < need) { (void)hipFree(p->prof.stamps_dev); p->prof.stamps_dev = nullptr; }
+    if (!p->prof.stamps_dev) HIPCHECK(hipMalloc(&p->prof.stamps_dev, bytes_per_record * need));
+    p->prof.stamps_n = need;
+    *out = (unsigned long long *)p->prof.stamps_dev;
     return SXFIR_OK;
 }
 
@@ -33,7 +32,7 @@ static int prof_stamps(sxfir_plan *p, size_t need, size_t bytes_per_record, unsi
 static int prof_launch_dense_ablations(sxfir_plan *p, sxfir::DecimMultiArgs &a, dim3 grid, hipStream_t st)
 {
     if (p->fmt == SXFIR_CF16) return 0;                                                  // CF16 storage: the product dispatch (no ablations of it)
-    if (p->dense_subset && p->ablate == 1 && p->fmt != SXFIR_S32) {                      // (ablate 0: the product dispatch launches it)
+    if ((p->form->taps == TAPS_SUBSET8) && p->prof.ablate == 1 && p->fmt != SXFIR_S32) {                      // (ablate 0: the product dispatch launches it)
         sxfir::DecimMultiArgs b = a;
         if (int rc = need_tap_table(p, TAPS_SUBSET8, "decim_dense_kernel<8, SUBSET> (ablation 1)")) return rc;
         b.taps = p->taps_scaled_dev;                              // the subset-major tap table
@@ -41,43 +40,47 @@ static int prof_launch_dense_ablations(sxfir_plan *p, sxfir::DecimMultiArgs &a, 
         HIPCHECK(hipGetLastError());
         return 1;
     }
-    if (p->dense_hc && p->fmt != SXFIR_S32 && (p->ratio == 32 || p->ratio == 16) && (p->ablate == 0 || p->ablate == 1)) {
+    if (p->prof.dense_hc && p->fmt != SXFIR_S32 && (p->ratio == 32 || p->ratio == 16) && (p->prof.ablate == 0 || p->prof.ablate == 1)) {
         // SXFIR_DENSE_HC=1: halo carry (runs of consecutive tiles per workgroup, the next halo copied inside LDS)
-        if (p->ratio == 32 && p->ablate == 0) hipLaunchKernelGGL((sxfir::decim_dense_kernel<32, 0, false, 2, false, true>), grid, dim3(256), 0, st, a);
+        if (p->ratio == 32 && p->prof.ablate == 0) hipLaunchKernelGGL((sxfir::decim_dense_kernel<32, 0, false, 2, false, true>), grid, dim3(256), 0, st, a);
         else if (p->ratio == 32) hipLaunchKernelGGL((sxfir::decim_dense_kernel<32, 1, false, 2, false, true>), grid, dim3(256), 0, st, a);
-        else if (p->ablate == 0) hipLaunchKernelGGL((sxfir::decim_dense_kernel<16, 0, false, 2, false, true>), grid, dim3(256), 0, st, a);
+        else if (p->prof.ablate == 0) hipLaunchKernelGGL((sxfir::decim_dense_kernel<16, 0, false, 2, false, true>), grid, dim3(256), 0, st, a);
         else hipLaunchKernelGGL((sxfir::decim_dense_kernel<16, 1, false, 2, false, true>), grid, dim3(256), 0, st, a);
         HIPCHECK(hipGetLastError());
         return 1;
     }
-    if (p->dense_subset && p->ablate == 0 && p->dense_nt_set == 0) return 0;
-    if (p->fmt == SXFIR_S32 || (p->ablate == 0 && p->dense_nt_set == 0) || p->ablate > 3) return 0;
-    if (p->ablate == 3)
-        if (int rc = prof_stamps(p, (size_t)grid.x * p->nchan * p->multi_waves, 40, &a.stamps)) return rc;
+    if ((p->form->taps == TAPS_SUBSET8) && p->prof.ablate == 0 && p->prof.dense_nt_set == 0) return 0;
+    if (p->fmt == SXFIR_S32 || (p->prof.ablate == 0 && p->prof.dense_nt_set == 0) || p->prof.ablate > 3) return 0;
+    if (p->prof.ablate == 3)
+        if (int rc = prof_stamps(p, (size_t)grid.x * p->nchan * p->prof.multi_waves, 40, &a.stamps)) return rc;
 #define SXFIR_PD(AA, NN) \
     do { \
         if (p->ratio == 8) hipLaunchKernelGGL((sxfir::decim_dense_kernel<8, AA, false, NN>), grid, dim3(256), 0, st, a); \
         else if (p->ratio == 16) hipLaunchKernelGGL((sxfir::decim_dense_kernel<16, AA, false, NN>), grid, dim3(256), 0, st, a); \
         else hipLaunchKernelGGL((sxfir::decim_dense_kernel<32, AA, false, NN>), grid, dim3(256), 0, st, a); \
     } while (0)
-    if (p->ablate == 0 && p->dense_nt == 2) SXFIR_PD(0, 2);
-    else if (p->ablate == 0 && p->dense_nt) SXFIR_PD(0, 1);
-    else if (p->ablate == 0) SXFIR_PD(0, 0);
-    else if (p->ablate == 1 && p->dense_nt == 2) SXFIR_PD(1, 2);
-    else if (p->ablate == 1 && p->dense_nt) SXFIR_PD(1, 1);
-    else if (p->ablate == 1) SXFIR_PD(1, 0);
-    else if (p->ablate == 2) SXFIR_PD(2, 0);
+    if (p->prof.ablate == 0 && p->prof.dense_nt == 2) SXFIR_PD(0, 2);
+    else if (p->prof.ablate == 0 && p->prof.dense_nt) SXFIR_PD(0, 1);
+    else if (p->prof.ablate == 0) SXFIR_PD(0, 0);
+    else if (p->prof.ablate == 1 && p->prof.dense_nt == 2) SXFIR_PD(1, 2);
+    else if (p->prof.ablate == 1 && p->prof.dense_nt) SXFIR_PD(1, 1);
+    else if (p->prof.ablate == 1) SXFIR_PD(1, 0);
+    else if (p->prof.ablate == 2) SXFIR_PD(2, 0);
     else SXFIR_PD(3, 0);
 #undef SXFIR_PD
     HIPCHECK(hipGetLastError());
     return 1;
 }
 
-// ... and SXFIR_DENSE_SUBSET=0: the VGPR-tap forms at /8, A/B partners of the scalar-tap form that ships
+static int prof_launch_multi(sxfir_plan *p, sxfir::DecimMultiArgs &a, dim3 grid, hipStream_t st);
+
+// ... and SXFIR_DENSE_SUBSET=0: the VGPR-tap forms at /8, A/B partners of the scalar-tap form that ships; a plan of the
+// multi-column form (FORM_MULTI) launches that kernel
 static int prof_launch_dense(sxfir_plan *p, sxfir::DecimMultiArgs &a, dim3 grid, hipStream_t st)
 {
+    if (p->form == &FORM_MULTI) return prof_launch_multi(p, a, grid, st);
     if (const int pr = prof_launch_dense_ablations(p, a, grid, st)) return pr;
-    if (p->ratio != 8 || p->dense_subset) return 0;
+    if (p->ratio != 8 || (p->form->taps == TAPS_SUBSET8)) return 0;
     if (p->fmt == SXFIR_CF16) hipLaunchKernelGGL((sxfir::decim_dense_kernel<8, 0, false, 0, false, false, true>), grid, dim3(256), 0, st, a);
     else if (p->fmt == SXFIR_S32) hipLaunchKernelGGL((sxfir::decim_dense_kernel<8, 0, true, 2>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((sxfir::decim_dense_kernel<8, 0, false, 2>), grid, dim3(256), 0, st, a);
@@ -89,7 +92,7 @@ static int prof_launch_dense(sxfir_plan *p, sxfir::DecimMultiArgs &a, dim3 grid,
 // words (one instantiation per ratio), the (ratio, waves, CF16, row split) variants and their ablation / stamp builds
 static int prof_launch_multi(sxfir_plan *p, sxfir::DecimMultiArgs &a, dim3 grid, hipStream_t st)
 {
-    const int W = p->multi_waves;
+    const int W = p->prof.multi_waves;
     if (p->fmt == SXFIR_S32) {
         switch (p->ratio) {
         case 8: hipLaunchKernelGGL((sxfir::decim_multi_kernel<8, 4, false, 0, 2, true>), grid, dim3(256), 0, st, a); break;
@@ -99,9 +102,9 @@ static int prof_launch_multi(sxfir_plan *p, sxfir::DecimMultiArgs &a, dim3 grid,
         HIPCHECK(hipGetLastError());
         return 1;
     }
-    if (p->ablate == 3)
+    if (p->prof.ablate == 3)
         if (int rc = prof_stamps(p, (size_t)grid.x * p->nchan * W, 40, &a.stamps)) return rc;
-    const int key = SXFIR_MULTI_KEY(p->ratio, W, p->fmt == SXFIR_CF16, p->multi_ps) + 100000 * p->ablate;
+    const int key = SXFIR_MULTI_KEY(p->ratio, W, p->fmt == SXFIR_CF16, p->prof.multi_ps) + 100000 * p->prof.ablate;
     switch (key) {
 #define SXFIR_X(DD, WW, HH, PP) \
     case SXFIR_MULTI_KEY(DD, WW, HH, PP): hipLaunchKernelGGL((sxfir::decim_multi_kernel<DD, WW, HH, 0, PP>), grid, dim3(64 * WW), 0, st, a); break;
@@ -132,8 +135,8 @@ static int prof_launch_multi(sxfir_plan *p, sxfir::DecimMultiArgs &a, dim3 grid,
 // form (SXFIR_BLOCKS_SMALL=1, =2 unrotated), round 5's waves by row half (SXFIR_BLOCKS_RP=0), plain staging loads (SXFIR_BLOCKS_NT=0)
 static int prof_launch_blocks(sxfir_plan *p, const LaunchGeom &geom, const sxfir::DecimMultiArgs &a, sxfir::DecimBlocksJoin &jn, dim3 grid, hipStream_t st)
 {
-    jn.shadow = (sxfir::f32x4 *)p->join_shadow;
-    jn.drop_blk = p->join_drop;
+    jn.shadow = (sxfir::f32x4 *)p->prof.join_shadow;
+    jn.drop_blk = p->prof.join_drop;
 #define SXFIR_B(...) hipLaunchKernelGGL((sxfir::decim_blocks_kernel<__VA_ARGS__>), grid, dim3(256), 0, st, a, jn)
     const bool cf32 = p->fmt == SXFIR_CF32, split = geom.split > 1;
     if (p->blocks < 3 && !p->rot) {
@@ -164,8 +167,8 @@ static int prof_launch_blocks(sxfir_plan *p, const LaunchGeom &geom, const sxfir
 // NEXT launch's joiners find them there unless theirs arrive (what a stale hand-off looks like, deterministically)
 static int prof_join_drop_copy(sxfir_plan *p, const LaunchGeom &geom, hipStream_t st)
 {
-    if (p->join_drop >= 0 && geom.split > 1)
-        HIPCHECK(hipMemcpy2DAsync((char *)p->join_partials + 4096 * (size_t)p->join_drop, 4096 * (size_t)p->blocks, p->join_shadow, 4096,
+    if (p->prof.join_drop >= 0 && geom.split > 1)
+        HIPCHECK(hipMemcpy2DAsync((char *)p->join_partials + 4096 * (size_t)p->prof.join_drop, 4096 * (size_t)p->blocks, p->prof.join_shadow, 4096,
                                   4096, (size_t)(geom.n_tiles * p->nchan), hipMemcpyDeviceToDevice, st));
     return SXFIR_OK;
 }
@@ -174,75 +177,75 @@ static int prof_join_drop_copy(sxfir_plan *p, const LaunchGeom &geom, hipStream_
 // of decim4_tile2_kernel, each with its own grid
 static int prof_launch_tile_variant(sxfir_plan *p, sxfir::DecimTileArgs &a, long long n_out, long long n_tiles, hipStream_t st)
 {
-    if ((p->pair || p->wide) && p->ntaps == 128) {
+    if ((p->prof.pair || p->prof.wide) && p->ntaps == 128) {
         // one workgroup (2 waves / 1 wave) per tile, strided XCD-blocked passes
         const long long n_tiles2 = (n_out + 511) / 512;
-        long long G = ((long long)p->compute_units * (p->wide ? p->occ_wide : p->occ_pair) * p->oversub) / p->nchan;
+        long long G = ((long long)p->compute_units * (p->prof.wide ? p->prof.occ_wide : p->prof.occ_pair) * p->oversub) / p->nchan;
         if (G < 1) G = 1;
         if (G > n_tiles2) G = n_tiles2;
-        set_schedule(a, n_tiles2, G, p->sched == 1 ? 2 : p->sched);          // (these kernels make strided passes only)
+        set_schedule(a, n_tiles2, G, p->prof.sched == 1 ? 2 : p->prof.sched);          // (these kernels make strided passes only)
         dim3 grid((unsigned)G, (unsigned)p->nchan);
-        const int abl = p->ablate;
+        const int abl = p->prof.ablate;
         if (abl == 5)
-            if (int rc = prof_stamps(p, (size_t)G * p->nchan * (p->wide ? 1 : 2), 64, &a.stamps)) return rc;
-        if (p->wide) {
+            if (int rc = prof_stamps(p, (size_t)G * p->nchan * (p->prof.wide ? 1 : 2), 64, &a.stamps)) return rc;
+        if (p->prof.wide) {
             // <ABL, S32IN, NB (LDS read-ahead, chunks), NTL (nt staging loads)>; the product launches <0, *, 24, true>
-#define SXFIR_W(AA, NB_, NT_) hipLaunchKernelGGL((sxfir::decim4_wide_kernel<AA, false, NB_, NT_>), grid, dim3(64), (size_t)p->lds_pad, st, a)
-            const int nbk = p->wide_nb ? p->wide_nb : 8;
+#define SXFIR_W(AA, NB_, NT_) hipLaunchKernelGGL((sxfir::decim4_wide_kernel<AA, false, NB_, NT_>), grid, dim3(64), (size_t)p->prof.lds_pad, st, a)
+            const int nbk = p->prof.wide_nb ? p->prof.wide_nb : 8;
             if (p->fmt == SXFIR_S32) hipLaunchKernelGGL((sxfir::decim4_wide_kernel<0, true, 8, false>), grid, dim3(64), 0, st, a);
-            else if (abl == 1 && p->wide_nt) SXFIR_W(1, 8, true);
+            else if (abl == 1 && p->prof.wide_nt) SXFIR_W(1, 8, true);
             else if (abl == 1) SXFIR_W(1, 8, false);
-            else if (abl == 5 && p->wide_nt) SXFIR_W(5, 24, true);
+            else if (abl == 5 && p->prof.wide_nt) SXFIR_W(5, 24, true);
             else if (abl == 5) SXFIR_W(5, 8, false);
 #define SXFIR_WP(POL_) hipLaunchKernelGGL((sxfir::decim4_wide_kernel<0, false, 24, true, false, POL_>), grid, dim3(64), 0, st, a)
-            else if (p->wide_pol == 0x100 && nbk == 24 && p->wide_nt) SXFIR_WP(0x100);   // plain stores
-            else if (p->wide_pol == 0x200 && nbk == 24 && p->wide_nt) SXFIR_WP(0x200);   // sc0 sc1 stores
-            else if (p->wide_pol == 0x300 && nbk == 24 && p->wide_nt) SXFIR_WP(0x300);   // sc0 sc1 nt stores
-            else if (p->wide_pol == 0x400 && nbk == 24 && p->wide_nt) SXFIR_WP(0x400);   // sc1 stores
-            else if (p->wide_pol == 0x010 && nbk == 24 && p->wide_nt) SXFIR_WP(0x010);   // nt sc1 loads
-            else if (p->wide_pol == 0x011 && nbk == 24 && p->wide_nt) SXFIR_WP(0x011);   // nt sc0 sc1 loads
-            else if (p->wide_pol == 0x001 && nbk == 24 && p->wide_nt) SXFIR_WP(0x001);   // nt sc0 loads
-            else if (p->wide_pol == 0x310 && nbk == 24 && p->wide_nt) SXFIR_WP(0x310);
-            else if (p->wide_pol == 0x210 && nbk == 24 && p->wide_nt) SXFIR_WP(0x210);
-            else if (p->wide_pol) return fail(SXFIR_EUNSUPPORTED, "no wide variant with cache policy 0x%x (wident24 only)", p->wide_pol);
+            else if (p->prof.wide_pol == 0x100 && nbk == 24 && p->prof.wide_nt) SXFIR_WP(0x100);   // plain stores
+            else if (p->prof.wide_pol == 0x200 && nbk == 24 && p->prof.wide_nt) SXFIR_WP(0x200);   // sc0 sc1 stores
+            else if (p->prof.wide_pol == 0x300 && nbk == 24 && p->prof.wide_nt) SXFIR_WP(0x300);   // sc0 sc1 nt stores
+            else if (p->prof.wide_pol == 0x400 && nbk == 24 && p->prof.wide_nt) SXFIR_WP(0x400);   // sc1 stores
+            else if (p->prof.wide_pol == 0x010 && nbk == 24 && p->prof.wide_nt) SXFIR_WP(0x010);   // nt sc1 loads
+            else if (p->prof.wide_pol == 0x011 && nbk == 24 && p->prof.wide_nt) SXFIR_WP(0x011);   // nt sc0 sc1 loads
+            else if (p->prof.wide_pol == 0x001 && nbk == 24 && p->prof.wide_nt) SXFIR_WP(0x001);   // nt sc0 loads
+            else if (p->prof.wide_pol == 0x310 && nbk == 24 && p->prof.wide_nt) SXFIR_WP(0x310);
+            else if (p->prof.wide_pol == 0x210 && nbk == 24 && p->prof.wide_nt) SXFIR_WP(0x210);
+            else if (p->prof.wide_pol) return fail(SXFIR_EUNSUPPORTED, "no wide variant with cache policy 0x%x (wident24 only)", p->prof.wide_pol);
 #undef SXFIR_WP
-            else if (p->wide_pin && nbk == 24) hipLaunchKernelGGL((sxfir::decim4_wide_kernel<0, false, 24, true, true>), grid, dim3(64), 0, st, a);
-            else if (p->wide_pin && nbk == 16) hipLaunchKernelGGL((sxfir::decim4_wide_kernel<0, false, 16, true, true>), grid, dim3(64), 0, st, a);
-            else if (p->wide_nt && nbk == 8) SXFIR_W(0, 8, true);
-            else if (p->wide_nt && nbk == 12) SXFIR_W(0, 12, true);
-            else if (p->wide_nt && nbk == 16) SXFIR_W(0, 16, true);
-            else if (p->wide_nt && nbk == 24) SXFIR_W(0, 24, true);
-            else if (p->wide_nt && nbk == 32) SXFIR_W(0, 32, true);
+            else if (p->prof.wide_pin && nbk == 24) hipLaunchKernelGGL((sxfir::decim4_wide_kernel<0, false, 24, true, true>), grid, dim3(64), 0, st, a);
+            else if (p->prof.wide_pin && nbk == 16) hipLaunchKernelGGL((sxfir::decim4_wide_kernel<0, false, 16, true, true>), grid, dim3(64), 0, st, a);
+            else if (p->prof.wide_nt && nbk == 8) SXFIR_W(0, 8, true);
+            else if (p->prof.wide_nt && nbk == 12) SXFIR_W(0, 12, true);
+            else if (p->prof.wide_nt && nbk == 16) SXFIR_W(0, 16, true);
+            else if (p->prof.wide_nt && nbk == 24) SXFIR_W(0, 24, true);
+            else if (p->prof.wide_nt && nbk == 32) SXFIR_W(0, 32, true);
             else if (nbk == 2) SXFIR_W(0, 2, false);
             else if (nbk == 4) SXFIR_W(0, 4, false);
             else if (nbk == 12) SXFIR_W(0, 12, false);
             else if (nbk == 16) SXFIR_W(0, 16, false);
             else if (nbk == 24) SXFIR_W(0, 24, false);
-            else if (nbk == 8 && !p->wide_nt) SXFIR_W(0, 8, false);
-            else return fail(SXFIR_EUNSUPPORTED, "no wide variant nb %d nt %d ablate %d", nbk, (int)p->wide_nt, abl);
+            else if (nbk == 8 && !p->prof.wide_nt) SXFIR_W(0, 8, false);
+            else return fail(SXFIR_EUNSUPPORTED, "no wide variant nb %d nt %d ablate %d", nbk, (int)p->prof.wide_nt, abl);
 #undef SXFIR_W
         }
         else if (p->fmt == SXFIR_S32) hipLaunchKernelGGL((sxfir::decim4_pair_kernel<0, true>), grid, dim3(128), 0, st, a);
-        else if (p->pair_xsep && abl == 5) hipLaunchKernelGGL((sxfir::decim4_pair_kernel<5, false, true>), grid, dim3(128), 0, st, a);
-        else if (p->pair_xsep) hipLaunchKernelGGL((sxfir::decim4_pair_kernel<0, false, true>), grid, dim3(128), 0, st, a);
+        else if (p->prof.pair_xsep && abl == 5) hipLaunchKernelGGL((sxfir::decim4_pair_kernel<5, false, true>), grid, dim3(128), 0, st, a);
+        else if (p->prof.pair_xsep) hipLaunchKernelGGL((sxfir::decim4_pair_kernel<0, false, true>), grid, dim3(128), 0, st, a);
         else if (abl == 1) hipLaunchKernelGGL((sxfir::decim4_pair_kernel<1, false>), grid, dim3(128), 0, st, a);
         else if (abl == 5) hipLaunchKernelGGL((sxfir::decim4_pair_kernel<5, false>), grid, dim3(128), 0, st, a);
         else hipLaunchKernelGGL((sxfir::decim4_pair_kernel<0, false>), grid, dim3(128), 0, st, a);
         HIPCHECK(hipGetLastError());
         return 1;
     }
-    if (!p->t2_wpg) return 0;
+    if (!p->prof.t2_wpg) return 0;
     // decim4_tile2_kernel: G workgroups of t2_wpg waves per channel, wave ww of workgroup b takes tiles
     // (S(b) + i*G)*wpg + ww
-    const int wpg = p->t2_wpg;
+    const int wpg = p->prof.t2_wpg;
     const long long n_super = (n_tiles + wpg - 1) / wpg;
-    long long G = ((long long)p->compute_units * p->occ_sb * p->oversub / wpg) / p->nchan;
+    long long G = ((long long)p->compute_units * p->prof.occ_sb * p->oversub / wpg) / p->nchan;
     if (G < 1) G = 1;
     if (G > n_super) G = n_super;
     a.n_tiles = (int)n_tiles;
     a.w8 = (G % 8 == 0) ? (int)(G / 8) : 0;
     a.run_base = a.run_extra = 0;
-    if (p->t2_opt & sxfir::T2_HCARRY) {
+    if (p->prof.t2_opt & sxfir::T2_HCARRY) {
         // contiguous runs of K tiles per wave, waves numbered in dispatch order
         const long long K = (n_tiles + G * wpg - 1) / (G * wpg);
         G = ((n_tiles + K - 1) / K + wpg - 1) / wpg;          // workgroups that have a tile
@@ -251,25 +254,25 @@ static int prof_launch_tile_variant(sxfir_plan *p, sxfir::DecimTileArgs &a, long
     } else {
         const long long last = n_tiles - 1, sup = last / wpg;
         const int t = (int)(sup % G);
-        const int bb = (p->sched == 0 && a.w8) ? (t % a.w8) * 8 + t / a.w8 : t;
+        const int bb = (p->prof.sched == 0 && a.w8) ? (t % a.w8) * 8 + t / a.w8 : t;
         a.hist_wave = bb * wpg + (int)(last % wpg);
     }
     const unsigned grid_y = (unsigned)p->nchan;
     a.n_waves = (int)G;
     dim3 grid((unsigned)G, grid_y);
-    if (p->ablate == 5)
+    if (p->prof.ablate == 5)
         if (int rc = prof_stamps(p, (size_t)G * grid_y * wpg, 64, &a.stamps)) return rc;
-    switch ((wpg * 100 + p->t2_opt) * 10 + (p->ablate == 1 || p->ablate == 2 || p->ablate == 5 ? p->ablate : 0)) {
+    switch ((wpg * 100 + p->prof.t2_opt) * 10 + (p->prof.ablate == 1 || p->prof.ablate == 2 || p->prof.ablate == 5 ? p->prof.ablate : 0)) {
 #define SXFIR_X(WW, OO) \
-    case (WW * 100 + OO) * 10: hipLaunchKernelGGL((sxfir::decim4_tile2_kernel<128, WW, OO>), grid, dim3(64 * WW), p->lds_pad, st, a); break; \
-    case (WW * 100 + OO) * 10 + 1: hipLaunchKernelGGL((sxfir::decim4_tile2_kernel<128, WW, OO, 1>), grid, dim3(64 * WW), p->lds_pad, st, a); break;
+    case (WW * 100 + OO) * 10: hipLaunchKernelGGL((sxfir::decim4_tile2_kernel<128, WW, OO>), grid, dim3(64 * WW), p->prof.lds_pad, st, a); break; \
+    case (WW * 100 + OO) * 10 + 1: hipLaunchKernelGGL((sxfir::decim4_tile2_kernel<128, WW, OO, 1>), grid, dim3(64 * WW), p->prof.lds_pad, st, a); break;
         SXFIR_TILE2_VARIANTS(SXFIR_X)
 #undef SXFIR_X
 #define SXFIR_X(WW, OO) \
-    case (WW * 100 + OO) * 10 + 5: hipLaunchKernelGGL((sxfir::decim4_tile2_kernel<128, WW, OO, 5>), grid, dim3(64 * WW), p->lds_pad, st, a); break;
+    case (WW * 100 + OO) * 10 + 5: hipLaunchKernelGGL((sxfir::decim4_tile2_kernel<128, WW, OO, 5>), grid, dim3(64 * WW), p->prof.lds_pad, st, a); break;
         SXFIR_TILE2_STAMPED(SXFIR_X)
 #undef SXFIR_X
-    default: return fail(SXFIR_EUNSUPPORTED, "no tile2 variant %d:%d ablate %d", wpg, p->t2_opt, p->ablate);
+    default: return fail(SXFIR_EUNSUPPORTED, "no tile2 variant %d:%d ablate %d", wpg, p->prof.t2_opt, p->prof.ablate);
     }
     HIPCHECK(hipGetLastError());
     return 1;
@@ -279,9 +282,9 @@ static int prof_launch_tile_variant(sxfir_plan *p, sxfir::DecimTileArgs &a, long
 // waves as it had tiles
 static void prof_short_tail(sxfir_plan *p, sxfir::DecimTileArgs &a, long long n_tiles, long long *per_chan)
 {
-    if (!(p->sched == 3 && p->ntaps == 128 && p->symmetric)) return;
+    if (!(p->prof.sched == 3 && p->ntaps == 128 && p->symmetric)) return;
     const long long W = *per_chan, passes = n_tiles / W;
-    const long long resident = (long long)p->compute_units * p->occ_sb / p->nchan;
+    const long long resident = (long long)p->compute_units * p->prof.occ_sb / p->nchan;
     if (passes >= 2 && n_tiles % W == 0 && W > resident && resident % 8 == 0) {
         const long long glong = W - resident, gshort = resident * passes;
         a.long_waves = (int)glong;
@@ -299,24 +302,24 @@ static void prof_short_tail(sxfir_plan *p, sxfir::DecimTileArgs &a, long long n_
 // diagnostic (11, 12), the double-buffered form and the decim4_sgpr_kernel experiments
 static int prof_launch_tile_first_gen(sxfir_plan *p, sxfir::DecimTileArgs &a, dim3 grid, long long per_chan, bool dbuf, hipStream_t st)
 {
-    if (p->ablate == 11 || p->ablate == 12) {
+    if (p->prof.ablate == 11 || p->prof.ablate == 12) {
         // one {cycles, ticks} pair per wave, printed by sxfir_debug_clock()
-        if (!p->stamps_dev) HIPCHECK(hipMalloc(&p->stamps_dev, 16 * (size_t)per_chan * p->nchan));
-        p->stamps_n = (size_t)per_chan * p->nchan;
-        a.stamps = (unsigned long long *)p->stamps_dev;
+        if (!p->prof.stamps_dev) HIPCHECK(hipMalloc(&p->prof.stamps_dev, 16 * (size_t)per_chan * p->nchan));
+        p->prof.stamps_n = (size_t)per_chan * p->nchan;
+        a.stamps = (unsigned long long *)p->prof.stamps_dev;
     }
-    if (p->fmt == SXFIR_CF32 && p->ntaps == 128 && (p->sgpr_r || p->ablate != 0 || dbuf)) {
-        if (p->sgpr_r == 8) {
+    if (p->fmt == SXFIR_CF32 && p->ntaps == 128 && (p->prof.sgpr_r || p->prof.ablate != 0 || dbuf)) {
+        if (p->prof.sgpr_r == 8) {
             hipLaunchKernelGGL((sxfir::decim4_sgpr_kernel<8>), grid, dim3(64), 0, st, a);
-        } else if (p->sgpr_r == 4) {
+        } else if (p->prof.sgpr_r == 4) {
             hipLaunchKernelGGL((sxfir::decim4_sgpr_kernel<4>), grid, dim3(64), 0, st, a);
-        } else if (p->ablate != 0) {
-            switch (p->ablate) {
+        } else if (p->prof.ablate != 0) {
+            switch (p->prof.ablate) {
 #define SXFIR_X(N) \
             case N: hipLaunchKernelGGL((sxfir::decim4_tile_kernel<128, false, N>), grid, dim3(64), 0, st, a); break;
                 SXFIR_TILE_ABLATIONS(SXFIR_X)
 #undef SXFIR_X
-            default: return fail(SXFIR_EINVAL, "SXFIR_ABLATE=%d is not a profiling mode of the tile kernel", p->ablate);
+            default: return fail(SXFIR_EINVAL, "SXFIR_ABLATE=%d is not a profiling mode of the tile kernel", p->prof.ablate);
             }
         } else {
             hipLaunchKernelGGL((sxfir::decim4_tile_kernel<128, true>), grid, dim3(64), 0, st, a);
@@ -343,8 +346,8 @@ static int prof_launch_tile(sxfir_plan *p, const LaunchGeom &geom, sxfir::DecimT
     long long per_chan = geom.groups;
     prof_short_tail(p, a, geom.n_tiles, &per_chan);                                    // SXFIR_SCHED=3
     const dim3 grid((unsigned)per_chan, (unsigned)p->nchan);
-    if (const int pr = prof_launch_tile_first_gen(p, a, grid, per_chan, p->tile_dbuf, st)) return pr;
-    if (!(p->ntaps == 128 && p->symmetric && p->sched != 1)) return 0;
+    if (const int pr = prof_launch_tile_first_gen(p, a, grid, per_chan, p->prof.tile_dbuf, st)) return pr;
+    if (!(p->ntaps == 128 && p->symmetric && p->prof.sched != 1)) return 0;
     if (p->fmt == SXFIR_S32) hipLaunchKernelGGL((sxfir::decim4_tile2_kernel<128, 1, sxfir::T2_SHIPPED, 0, true>), grid, dim3(64), 0, st, a);
     else hipLaunchKernelGGL((sxfir::decim4_tile2_kernel<128, 1, sxfir::T2_SHIPPED>), grid, dim3(64), 0, st, a);
     HIPCHECK(hipGetLastError());
@@ -359,10 +362,10 @@ static int prof_launch_interp(sxfir_plan *p, const LaunchGeom &geom, const sxfir
 #define SXFIR_I(K_, ...) hipLaunchKernelGGL((sxfir::K_<__VA_ARGS__>), grid, dim3(64), 0, st, t)
     if (geom.kind == GEOM_IPASS) {
         if (p->ratio != 8) return 0;
-        if (p->ipass_qi == 4 && s32) return fail(SXFIR_EUNSUPPORTED, "four inputs per lane: CF32 only");
-        else if (p->ipass_qi == 4 && key) SXFIR_I(interp8_pass_kernel, 4, true);
-        else if (p->ipass_qi == 4) SXFIR_I(interp8_pass_kernel, 4);
-        else if (!p->ipass_wait0) return 0;
+        if (p->prof.ipass_qi == 4 && s32) return fail(SXFIR_EUNSUPPORTED, "four inputs per lane: CF32 only");
+        else if (p->prof.ipass_qi == 4 && key) SXFIR_I(interp8_pass_kernel, 4, true);
+        else if (p->prof.ipass_qi == 4) SXFIR_I(interp8_pass_kernel, 4);
+        else if (!p->prof.ipass_wait0) return 0;
         else if (s32 && key) SXFIR_I(interp8_pass_kernel, 2, true, true, false);
         else if (s32) SXFIR_I(interp8_pass_kernel, 2, false, true, false);
         else if (key) SXFIR_I(interp8_pass_kernel, 2, true, false, false);
@@ -394,14 +397,13 @@ static int prof_launch_interp(sxfir_plan *p, const LaunchGeom &geom, const sxfir
 
 #else  // the production library: no hook does anything
 
-static inline long long prof_tile_out(const sxfir_plan *, long long tile_out) { return tile_out; }
 static inline int prof_iblock16(const sxfir_plan *, bool, int base_l) { return base_l; }
 #define SXFIR_NO_HOOK(NAME) template <typename... A> static inline int NAME(const A &...) { return 0; }
 SXFIR_NO_HOOK(prof_oversub_forced)
+SXFIR_NO_HOOK(prof_sched)
 SXFIR_NO_HOOK(prof_launch_blocks)
 SXFIR_NO_HOOK(prof_join_drop_copy)
 SXFIR_NO_HOOK(prof_launch_dense)
-SXFIR_NO_HOOK(prof_launch_multi)
 SXFIR_NO_HOOK(prof_launch_tile)
 SXFIR_NO_HOOK(prof_launch_interp)
 #undef SXFIR_NO_HOOK
