@@ -41,6 +41,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 namespace sx {
@@ -151,65 +152,59 @@ private:
     size_t parallel_copies_ = 0;
 };
 
-class DeviceBuffer {
+// The device is selected before anything is created on it: a chain holds this in front of its streams, and the
+// member order does the rest.
+struct DeviceSelect {
+    explicit DeviceSelect(int gpu) { gpu_check(sxfir_set_device(gpu), "sxfir_set_device"); }
+};
+
+struct DeviceMemory {
+    static constexpr const char *what = "sxfir_malloc";
+    static int allocate(void **ptr, size_t bytes) { return sxfir_malloc(ptr, bytes); }
+    static int release(void *ptr) { return sxfir_free(ptr); }
+};
+// page-locked host memory: the only kind hipMemcpyAsync overlaps with kernels
+struct PinnedMemory {
+    static constexpr const char *what = "sxfir_host_alloc";
+    static int allocate(void **ptr, size_t bytes) { return sxfir_host_alloc(ptr, bytes); }
+    static int release(void *ptr) { return sxfir_host_free(ptr); }
+};
+
+template <class Memory>
+class Buffer {
 public:
-    DeviceBuffer() : ptr_(nullptr), bytes_(0) {}
-    ~DeviceBuffer() { release(); }
-    DeviceBuffer(const DeviceBuffer &) = delete;
-    DeviceBuffer &operator=(const DeviceBuffer &) = delete;
+    Buffer() = default;
+    ~Buffer() { release(); }
+    Buffer(const Buffer &) = delete;
+    Buffer &operator=(const Buffer &) = delete;
     void reserve(size_t bytes)
     {
         if (bytes <= bytes_) return;
         release();
-        gpu_check(sxfir_malloc(&ptr_, bytes), "sxfir_malloc");
+        gpu_check(Memory::allocate(&ptr_, bytes), Memory::what);
         bytes_ = bytes;
     }
     void release()
     {
-        if (ptr_) sxfir_free(ptr_);
+        if (ptr_) Memory::release(ptr_);
         ptr_ = nullptr;
         bytes_ = 0;
     }
     bool fits(size_t bytes) const { return bytes <= bytes_; }
     void *get() const { return ptr_; }
     char *at(size_t byte_offset) const { return static_cast<char *>(ptr_) + byte_offset; }
-
-private:
-    void *ptr_;
-    size_t bytes_;
-};
-
-// page-locked host memory: the only kind hipMemcpyAsync overlaps with kernels
-class PinnedBuffer {
-public:
-    PinnedBuffer() : ptr_(nullptr), bytes_(0) {}
-    ~PinnedBuffer() { release(); }
-    PinnedBuffer(const PinnedBuffer &) = delete;
-    PinnedBuffer &operator=(const PinnedBuffer &) = delete;
-    void reserve(size_t bytes)
-    {
-        if (bytes <= bytes_) return;
-        release();
-        gpu_check(sxfir_host_alloc(&ptr_, bytes), "sxfir_host_alloc");
-        bytes_ = bytes;
-    }
-    void release()
-    {
-        if (ptr_) sxfir_host_free(ptr_);
-        ptr_ = nullptr;
-        bytes_ = 0;
-    }
-    bool fits(size_t bytes) const { return bytes <= bytes_; }
     float *floats() const { return static_cast<float *>(ptr_); }
 
 private:
-    void *ptr_;
-    size_t bytes_;
+    void *ptr_ = nullptr;
+    size_t bytes_ = 0;
 };
+using DeviceBuffer = Buffer<DeviceMemory>;
+using PinnedBuffer = Buffer<PinnedMemory>;
 
 class GpuStream {
 public:
-    GpuStream() : st_(nullptr) { gpu_check(sxfir_stream_create(&st_), "sxfir_stream_create"); }
+    GpuStream() { gpu_check(sxfir_stream_create(&st_), "sxfir_stream_create"); }
     ~GpuStream() { sxfir_stream_destroy(st_); }
     GpuStream(const GpuStream &) = delete;
     GpuStream &operator=(const GpuStream &) = delete;
@@ -217,8 +212,59 @@ public:
     void sync() const { gpu_check(sxfir_stream_sync(st_), "sxfir_stream_sync"); }
 
 private:
-    void *st_;
+    void *st_ = nullptr;
 };
+
+class GpuEvent {
+public:
+    GpuEvent() { gpu_check(sxfir_event_create(&ev_), "sxfir_event_create"); }
+    ~GpuEvent() { sxfir_event_destroy(ev_); }
+    GpuEvent(const GpuEvent &) = delete;
+    GpuEvent &operator=(const GpuEvent &) = delete;
+    void record(const GpuStream &st) const { gpu_check(sxfir_event_record(ev_, st.get()), "sxfir_event_record"); }
+    void sync() const { gpu_check(sxfir_event_sync(ev_), "sxfir_event_sync"); }            // the HOST waits
+    void hold(const GpuStream &st) const { gpu_check(sxfir_stream_wait_event(st.get(), ev_), "sxfir_stream_wait_event"); }   // `st` waits
+
+private:
+    void *ev_ = nullptr;
+};
+
+using PlanHandle = std::unique_ptr<sxfir_plan, decltype(&sxfir_destroy)>;
+
+// The clock "the host really had to wait" is judged by.  tests/host/chains_probe.cpp names one it can stop: its call trace
+// runs every wait inline and must not depend on how long an inline wait happened to take.
+#ifndef SX_WAIT_CLOCK
+#define SX_WAIT_CLOCK std::chrono::steady_clock
+#endif
+
+// wait for the event; true when the host really had to wait for it (more than a few microseconds)
+inline bool really_waited(const GpuEvent &e)
+{
+    const auto t0 = SX_WAIT_CLOCK::now();
+    e.sync();
+    return SX_WAIT_CLOCK::now() - t0 > std::chrono::microseconds(3);
+}
+
+// Are the caller's blocks page-locked (pinned / registered with sxfir_host_register), every channel's whole range?
+// Then the DMA engines can read and write them as they are (any alignment, any layout: one copy per channel).
+inline bool page_locked(const float *const *ptrs, int nchan, size_t n)
+{
+    for (int c = 0; c < nchan; ++c) {
+        void *d = nullptr;
+        if (sxfir_host_device_pointer(ptrs[c], 8 * n, &d) != SXFIR_OK) return false;
+    }
+    return true;
+}
+
+// a buffer is replaced by a larger one only when nothing queued on the chain's streams can still use it
+template <class Memory>
+void grow(Buffer<Memory> &b, size_t bytes, const GpuStream &first, const GpuStream &second)
+{
+    if (b.fits(bytes)) return;
+    first.sync();
+    second.sync();
+    b.reserve(bytes);
+}
 
 class RxChain {
 public:
@@ -241,35 +287,21 @@ public:
     // load (the reference's wire format, SoapySX.cpp:103-112); otherwise CF32 end to end.
     RxChain(int gpu, int decim, int taps_per_phase, uint64_t seed, uint32_t first_channel, int nchan, bool wire_s32)
         : gpu_(gpu), decim_(decim), ntaps_(decim * taps_per_phase), nchan_(nchan), seed_(seed),
-          first_channel_(first_channel), fmt_(wire_s32 ? SXFIR_S32 : SXFIR_CF32), plan_(nullptr), next_(-1), cur_(0),
-          batch_(kMinBatch)
+          first_channel_(first_channel), fmt_(wire_s32 ? SXFIR_S32 : SXFIR_CF32), device_(gpu), plan_(nullptr, sxfir_destroy),
+          next_(-1), cur_(0), batch_(kMinBatch)
     {
-        gpu_check(sxfir_set_device(gpu_), "sxfir_set_device");
-        stream_.reset(new GpuStream());
-        copy_.reset(new GpuStream());
         std::vector<float> taps((size_t)ntaps_);
         gpu_check(sxfir_design_lowpass(ntaps_, decim_, 8.0, 1.0, taps.data()), "sxfir_design_lowpass");
-        gpu_check(sxfir_create(&plan_, SXFIR_DECIMATE, taps.data(), ntaps_, decim_, nchan_, fmt_, gpu_), "sxfir_create(rx)");
+        sxfir_plan *plan = nullptr;
+        gpu_check(sxfir_create(&plan, SXFIR_DECIMATE, taps.data(), ntaps_, decim_, nchan_, fmt_, gpu_), "sxfir_create(rx)");
+        plan_.reset(plan);
         max_batch_ = kMinBatch;
         while (max_batch_ < kMaxBatchCap && 2 * max_batch_ * (size_t)decim_ * (size_t)nchan_ <= kMaxSource) max_batch_ *= 2;
-        for (int k = 0; k < 2; ++k) {
-            done_[k] = ran_[k] = nullptr;
-            gpu_check(sxfir_event_create(&done_[k]), "sxfir_event_create");
-            gpu_check(sxfir_event_create(&ran_[k]), "sxfir_event_create");
-        }
-        direct_done_ = nullptr;
-        gpu_check(sxfir_event_create(&direct_done_), "sxfir_event_create");
     }
     ~RxChain()
     {
-        sxfir_stream_sync(stream_->get());
-        sxfir_stream_sync(copy_->get());
-        for (int k = 0; k < 2; ++k) {
-            sxfir_event_destroy(done_[k]);
-            sxfir_event_destroy(ran_[k]);
-        }
-        sxfir_event_destroy(direct_done_);
-        sxfir_destroy(plan_);
+        sxfir_stream_sync(stream_.get());
+        sxfir_stream_sync(copy_.get());
     }
     RxChain(const RxChain &) = delete;
     RxChain &operator=(const RxChain &) = delete;
@@ -282,14 +314,14 @@ public:
     sxfir_geometry geometry() const
     {
         sxfir_geometry g;
-        gpu_check(sxfir_launch_geometry(plan_, kMinBatch * (size_t)decim_, &g), "sxfir_launch_geometry");
+        gpu_check(sxfir_launch_geometry(plan_.get(), kMinBatch * (size_t)decim_, &g), "sxfir_launch_geometry");
         return g;
     }
 
     void reset()
     {
         next_ = -1;
-        slot_[0].n = slot_[1].n = 0;
+        drop_slots();
         grown_ = 0;
     }
 
@@ -301,120 +333,214 @@ public:
         gpu_check(sxfir_set_device(gpu_), "sxfir_set_device");
         // Large reads into page-locked (pinned / registered) caller memory: the pass goes from HBM into it by DMA,
         // no staging hop and no host copy.  Everything else goes through the pinned staging slots.
-        dst_locked_ = n >= kDirectFrom && page_locked(dsts, n);
+        const Dest dst{dsts, n >= kDirectFrom && page_locked(dsts, nchan_, n)};
         // a reader of megabyte blocks into page-locked memory: the batches read ahead for it stay in HBM and are
         // DMA-copied into ITS buffer when it asks (no staging hop, no host copy)
-        if (8 * n * (size_t)nchan_ >= kSdmaFromBytes) prefer_hbm_ = dst_locked_;
-        const bool go_direct = dst_locked_ && (pos != next_ || n > staged_from(pos));
-        if (pos != next_) {
+        if (8 * n * (size_t)nchan_ >= kSdmaFromBytes) prefer_hbm_ = dst.locked;
+        const bool jump = pos != next_;
+        const bool go_direct = dst.locked && (jump || n > staged_from(pos));
+        if (jump) {
             // a jump (overrun skip, restart): whatever was read ahead is for the wrong positions
-            slot_[0].n = slot_[1].n = 0;
+            drop_slots();
             prime(pos);
-            if (!go_direct) {
-                batch_ = pick_batch(n);
-                launch(cur_, pos, batch_);
-                launch(cur_ ^ 1, pos + (int64_t)batch_, batch_);
-            }
+            if (!go_direct) read_ahead(pos, n);
         }
-        size_t done = 0;
-        if (go_direct) {
-            // what the read-ahead already holds is handed out first: the filter has moved past it
-            done = drain_slots(pos, n, dsts);
-            const size_t from_slots = done;
-            int64_t p = pos + (int64_t)done;
-            void *st = stream_->get();
-            while (done < n) {
-                const size_t m = std::min(n - done, max_batch_);
-                // The pass lands in HBM and a DMA-engine copy, queued behind it on the same stream, carries it into
-                // the caller's memory.  (Until round 3 passes below a megabyte stored straight into the caller's
-                // hipHostRegister'ed memory from the kernel.  One full-suite run then saw the last 16 bytes of one
-                // tile of such a pass still unwritten when the completion event had fired -- never reproduced in
-                // 1500 repeats, tools/stress_direct_rx.py -- and the copy costs nothing measurable: a kernel's own
-                // stores cross PCIe at ~33 GB/s, the DMA engines write registered memory at ~36.  Kernels now store
-                // only into the chain's own hipHostMalloc'ed staging, the path every small read has always taken.)
-                run_to_hbm(0, p, m, st);
-                for (int c = 0; c < nchan_; ++c)
-                    gpu_check(sxfir_memcpy_d2h(dsts[c] + 2 * done, out_[0].at(8 * (size_t)c * m), 8 * m, st), "sxfir_memcpy_d2h");
-                p += (int64_t)m;
-                done += m;
-            }
-            gpu_check(sxfir_event_record(direct_done_, st), "sxfir_event_record");
-            gpu_check(sxfir_event_sync(direct_done_), "sxfir_event_sync");
-            direct_samples_ += (int64_t)(n - from_slots);
-            next_ = pos + (int64_t)n;
-            // keep the next batches in flight for whoever reads next
-            batch_ = pick_batch(n);
-            launch(cur_, next_, batch_);
-            launch(cur_ ^ 1, next_ + (int64_t)batch_, batch_);
-            return;
-        }
-        while (done < n) {
-            Slot &s = slot_[cur_];
-            const int64_t p = pos + (int64_t)done;
-            if (s.n == 0 || p >= s.pos + (int64_t)s.n) {
-                // current batch used up: the one in flight becomes current ...
-                const int64_t following = s.n ? s.pos + (int64_t)s.n : p;
-                cur_ ^= 1;
-                if (slot_[cur_].n == 0) launch(cur_, following, batch_);
-                else if (waited(cur_) && grown_ < max_batch_) {
-                    // the reader caught up with the batch in flight: a caller faster than one GPU round trip per
-                    // batch (no sample clock holding it back) gets batches twice as long from here on
-                    grown_ = std::max(grown_, batch_) * 2;
-                }
-                wait(cur_);
-                // ... and the batch after it goes in flight while the host hands this one out
-                // (what a reader EARNS by outrunning the read-ahead stops at kGrowCap: a staged batch is one D2H copy the
-                // reader of its first block waits for; only a request that is itself larger gets a larger pass, pick_batch)
-                batch_ = std::min(max_batch_, std::max(pick_batch(n), std::min(grown_, kGrowCap)));
-                launch(cur_ ^ 1, slot_[cur_].pos + (int64_t)slot_[cur_].n, batch_);
-                continue;
-            }
-            const size_t off = (size_t)(p - s.pos);
-            const size_t m = std::min(n - done, s.n - off);
-            hand_out(cur_, off, m, dsts, done);
-            done += m;
-        }
+        if (go_direct) direct(pos, n, dst);
+        else staged(pos, n, dst);
         next_ = pos + (int64_t)n;
     }
 
 private:
+    // One of the two read-ahead batches, with everything that belongs to it.
     struct Slot {
+        enum State {
+            Empty,      // nothing launched into this slot
+            InFlight,   // a pass into `stage` (for a large one: into `out`, with its DMA copy to `stage`) is queued; `done` fires behind it
+            Staged,     // the host may read the staged samples
+            InHbm,      // the batch is in `out` only (`ran` fires behind its pass): no copy to the host has been queued yet
+        };
+        State state = Empty;
         int64_t pos = 0;
-        size_t n = 0;         // 0 = nothing launched into this slot
-        bool ready = false;   // the host may read the staged samples
-        bool in_hbm = false;  // the batch is in out_[k] only: no copy to the host has been queued yet
+        size_t n = 0;
+        PinnedBuffer stage;
+        DeviceBuffer out;            // decimated block of a large pass, before its DMA copy to the host
+        GpuEvent done;               // recorded behind the slot's pass (its DMA copy, for a large one)
+        GpuEvent ran;                // recorded behind the pass that filled `out`
+
+        int64_t end() const { return pos + (int64_t)n; }
+        // samples of [p, ...) this slot holds (0: p is not in it)
+        size_t holds_from(int64_t p) const { return state != Empty && p >= pos && p < end() ? (size_t)(end() - p) : 0; }
+
+        // Every change of state:
+        void drop() { state = Empty; n = 0; }                                   // a jump, a reset, handed over to the direct route
+        void launched(int64_t p, size_t m, State s) { pos = p; n = m; state = s; }   // InFlight or InHbm
+        void copy_queued() { state = InFlight; }                                // InHbm -> an ordinary reader after all
+        // wait for THIS slot's pass only: the batch read ahead behind it stays in flight; true when the host really
+        // had to wait for it
+        bool wait()
+        {
+            if (state != InFlight) return false;     // (in HBM: ordered on the GPU, hand_out queues the copy)
+            const bool late = really_waited(done);
+            state = Staged;
+            return late;
+        }
     };
 
-    // samples [off, off+m) of slot k -> dsts[c] + 2*done
-    void hand_out(int k, size_t off, size_t m, float *const *dsts, size_t done)
+    // where this call's samples go: dsts[c] for channel c, and whether all of that is page-locked
+    struct Dest {
+        float *const *ptrs;
+        bool locked;
+        float *at(int c, size_t done) const { return ptrs[c] + 2 * done; }
+    };
+
+    void drop_slots()
     {
-        Slot &s = slot_[k];
-        if (s.in_hbm) {
-            if (dst_locked_) {
+        for (Slot &s : slot_) s.drop();
+    }
+
+    // which slot holds position p (the current one is asked first; -1: neither; how much of it from there: its holds_from(p))
+    int holder(int64_t p) const
+    {
+        for (int k : {cur_, cur_ ^ 1})
+            if (slot_[k].holds_from(p)) return k;
+        return -1;
+    }
+
+    // samples of [pos, ...) the two staging slots hold, contiguously from pos
+    size_t staged_from(int64_t pos) const
+    {
+        size_t have = 0;
+        for (int k; (k = holder(pos + (int64_t)have)) >= 0;) have += slot_[k].holds_from(pos + (int64_t)have);
+        return have;
+    }
+
+    // hand out whatever the two slots hold of [pos, pos+n), in stream order; returns the samples delivered.
+    // Afterwards both slots are empty (the filter state is at the end of the last launched batch).
+    size_t drain_slots(int64_t pos, size_t n, const Dest &dst)
+    {
+        size_t done = 0;
+        while (done < n) {
+            const int64_t p = pos + (int64_t)done;
+            const int k = holder(p);
+            if (k < 0) break;
+            Slot &s = slot_[k];
+            const size_t m = std::min(n - done, s.holds_from(p));
+            hand_out(s, (size_t)(p - s.pos), m, dst, done);
+            done += m;
+        }
+        // the filter has consumed the source up to the end of the furthest batch: the direct passes continue there
+        int64_t frontier = pos + (int64_t)done;
+        for (const Slot &s : slot_)
+            if (s.state != Slot::Empty) frontier = std::max(frontier, s.end());
+        if (frontier != pos + (int64_t)done) {
+            // read-ahead beyond what this call can use from staging (the request ends inside it, or the slots
+            // are ahead of a short tail): re-prime at the hand-over point instead of skipping samples
+            prime(pos + (int64_t)done);
+        }
+        drop_slots();
+        return done;
+    }
+
+    // put the next two batches in flight from position p, sized for a reader of `request` samples per call
+    void read_ahead(int64_t p, size_t request)
+    {
+        batch_ = pick_batch(request);
+        launch(slot_[cur_], p, batch_);
+        launch(slot_[cur_ ^ 1], p + (int64_t)batch_, batch_);
+    }
+
+    // A large read into page-locked caller memory that the read-ahead does not cover: passes of its own, DMA-copied
+    // straight into the caller's memory.
+    void direct(int64_t pos, size_t n, const Dest &dst)
+    {
+        // what the read-ahead already holds is handed out first: the filter has moved past it
+        size_t done = drain_slots(pos, n, dst);
+        const size_t from_slots = done;
+        // The route has no batch of its own: its passes run through the first slot's HBM block and `ran` event, which
+        // is theirs to take because drain_slots() has just left both slots empty.  (The throw is an assertion that stays
+        // in release builds, not an error a caller can reach: it says what the loan rests on.)
+        Slot &lent = slot_[0];
+        if (lent.state != Slot::Empty) throw std::logic_error("rx chain: the direct route needs an empty slot");
+        while (done < n) {
+            const size_t m = std::min(n - done, max_batch_);
+            // The pass lands in HBM and a DMA-engine copy, queued behind it on the same stream, carries it into
+            // the caller's memory.  (Until round 3 passes below a megabyte stored straight into the caller's
+            // hipHostRegister'ed memory from the kernel.  One full-suite run then saw the last 16 bytes of one
+            // tile of such a pass still unwritten when the completion event had fired -- never reproduced in
+            // 1500 repeats, tools/stress_direct_rx.py -- and the copy costs nothing measurable: a kernel's own
+            // stores cross PCIe at ~33 GB/s, the DMA engines write registered memory at ~36.  Kernels now store
+            // only into the chain's own hipHostMalloc'ed staging, the path every small read has always taken.)
+            run_to_hbm(lent, pos + (int64_t)done, m);
+            for (int c = 0; c < nchan_; ++c)
+                gpu_check(sxfir_memcpy_d2h(dst.at(c, done), lent.out.at(8 * (size_t)c * m), 8 * m, stream_.get()), "sxfir_memcpy_d2h");
+            done += m;
+        }
+        direct_done_.record(stream_);
+        direct_done_.sync();
+        direct_samples_ += (int64_t)(n - from_slots);
+        // keep the next batches in flight for whoever reads next
+        read_ahead(pos + (int64_t)n, n);
+    }
+
+    // Everything else: out of the staging slots, the next batch always in flight behind the current one.
+    void staged(int64_t pos, size_t n, const Dest &dst)
+    {
+        size_t done = 0;
+        while (done < n) {
+            Slot &s = slot_[cur_];
+            const int64_t p = pos + (int64_t)done;
+            if (s.state == Slot::Empty || p >= s.end()) {
+                // current batch used up: the one in flight becomes current ...
+                const int64_t following = s.state != Slot::Empty ? s.end() : p;
+                cur_ ^= 1;
+                Slot &c = slot_[cur_];
+                if (c.state == Slot::Empty) launch(c, following, batch_);
+                else if (c.wait() && grown_ < max_batch_) {
+                    // the reader caught up with the batch in flight: a caller faster than one GPU round trip per
+                    // batch (no sample clock holding it back) gets batches twice as long from here on
+                    // (what a reader EARNS by outrunning the read-ahead stops at kGrowCap: a staged batch is one D2H copy the
+                    // reader of its first block waits for; only a request that is itself larger gets a larger pass, pick_batch)
+                    grown_ = std::min(kGrowCap, std::max(grown_, batch_) * 2);
+                }
+                c.wait();
+                // ... and the batch after it goes in flight while the host hands this one out
+                batch_ = std::min(max_batch_, std::max(pick_batch(n), grown_));
+                launch(slot_[cur_ ^ 1], c.end(), batch_);
+                continue;
+            }
+            const size_t off = (size_t)(p - s.pos);
+            const size_t m = std::min(n - done, s.n - off);
+            hand_out(s, off, m, dst, done);
+            done += m;
+        }
+    }
+
+    // samples [off, off+m) of slot s -> the destination's sample `done` onwards
+    void hand_out(Slot &s, size_t off, size_t m, const Dest &dst, size_t done)
+    {
+        if (s.state == Slot::InHbm) {
+            if (dst.locked) {
                 // The batch's kernels are long through (the host checks, it does not queue a wait: a DMA copy
                 // queued behind a cross-stream wait makes hipMemcpyAsync itself block for milliseconds now and then
                 // on ROCm 7.2); the copy runs on the copy stream, beside the kernels of the batches read ahead.
-                void *cst = copy_->get();
-                gpu_check(sxfir_event_sync(ran_[k]), "sxfir_event_sync");
+                s.ran.sync();
                 for (int c = 0; c < nchan_; ++c)
-                    gpu_check(sxfir_memcpy_d2h(dsts[c] + 2 * done, out_[k].at(8 * ((size_t)c * s.n + off)), 8 * m, cst),
+                    gpu_check(sxfir_memcpy_d2h(dst.at(c, done), s.out.at(8 * ((size_t)c * s.n + off)), 8 * m, copy_.get()),
                               "sxfir_memcpy_d2h");
-                gpu_check(sxfir_event_record(done_[k], cst), "sxfir_event_record");
-                gpu_check(sxfir_event_sync(done_[k]), "sxfir_event_sync");
+                s.done.record(copy_);
+                s.done.sync();
                 direct_samples_ += (int64_t)m;
                 return;
             }
             // an ordinary destination after all: the batch takes the staging hop now
-            void *st = stream_->get();
-            grow(stage_[k], 8 * s.n * (size_t)nchan_);
-            gpu_check(sxfir_memcpy_d2h(stage_[k].floats(), out_[k].get(), 8 * s.n * (size_t)nchan_, st), "sxfir_memcpy_d2h");
-            gpu_check(sxfir_event_record(done_[k], st), "sxfir_event_record");
-            s.in_hbm = false;
-            s.ready = false;
+            grow(s.stage, 8 * s.n * (size_t)nchan_, stream_, copy_);
+            gpu_check(sxfir_memcpy_d2h(s.stage.floats(), s.out.get(), 8 * s.n * (size_t)nchan_, stream_.get()), "sxfir_memcpy_d2h");
+            s.done.record(stream_);
+            s.copy_queued();
         }
-        wait(k);
+        s.wait();
         for (int c = 0; c < nchan_; ++c)
-            pool_.copy(dsts[c] + 2 * done, stage_[k].floats() + 2 * ((size_t)c * s.n + off), 8 * m);
+            pool_.copy(dst.at(c, done), s.stage.floats() + 2 * ((size_t)c * s.n + off), 8 * m);
     }
 
     size_t pick_batch(size_t request) const
@@ -424,155 +550,67 @@ private:
         return b;
     }
 
-    // Are the caller's buffers page-locked (pinned / registered with sxfir_host_register), every channel's whole range?
-    // Then the DMA engines can write them as they are (any alignment, any layout: one copy per channel).
-    bool page_locked(float *const *dsts, size_t n) const
-    {
-        for (int c = 0; c < nchan_; ++c) {
-            void *d = nullptr;
-            if (sxfir_host_device_pointer(dsts[c], 8 * n, &d) != SXFIR_OK) return false;
-        }
-        return true;
-    }
-
-    // hand out whatever the two slots hold of [pos, pos+n), in stream order; returns the samples delivered.
-    // Afterwards both slots are empty (the filter state is at the end of the last launched batch).
-    size_t drain_slots(int64_t pos, size_t n, float *const *dsts)
-    {
-        size_t done = 0;
-        for (int pass = 0; pass < 2; ++pass) {
-            const int k = pass == 0 ? cur_ : cur_ ^ 1;
-            Slot &s = slot_[k];
-            const int64_t p = pos + (int64_t)done;
-            if (s.n == 0) continue;
-            if (p >= s.pos && p < s.pos + (int64_t)s.n && done < n) {
-                const size_t off = (size_t)(p - s.pos);
-                const size_t m = std::min(n - done, s.n - off);
-                hand_out(k, off, m, dsts, done);
-                done += m;
-            }
-        }
-        // the filter has consumed the source up to the end of the furthest batch: the direct passes continue there
-        int64_t frontier = pos + (int64_t)done;
-        for (int k = 0; k < 2; ++k)
-            if (slot_[k].n) frontier = std::max(frontier, slot_[k].pos + (int64_t)slot_[k].n);
-        if (frontier != pos + (int64_t)done) {
-            // read-ahead beyond what this call can use from staging (the request ends inside it, or the slots
-            // are ahead of a short tail): re-prime at the hand-over point instead of skipping samples
-            prime(pos + (int64_t)done);
-        }
-        slot_[0].n = slot_[1].n = 0;
-        return done;
-    }
-
     // stream samples [pos, pos+m) of all channels -> `out` (device-visible, channel stride out_stride samples)
-    void run(int64_t pos, size_t m, float *out, size_t out_stride, void *st)
+    void run(int64_t pos, size_t m, float *out, size_t out_stride)
     {
         size_t n_out = 0;
-        grow(in_, 8 * m * (size_t)decim_ * (size_t)nchan_);
+        grow(in_, 8 * m * (size_t)decim_ * (size_t)nchan_, stream_, copy_);
         gpu_check(sxfir_synth_fill(in_.get(), m * (size_t)decim_, m * (size_t)decim_, nchan_, seed_, first_channel_,
-                                   pos * decim_, fmt_, st),
+                                   pos * decim_, fmt_, stream_.get()),
                   "sxfir_synth_fill");
-        gpu_check(sxfir_decimate(plan_, in_.get(), m * (size_t)decim_, m * (size_t)decim_, out, out_stride, &n_out, st),
+        gpu_check(sxfir_decimate(plan_.get(), in_.get(), m * (size_t)decim_, m * (size_t)decim_, out, out_stride, &n_out, stream_.get()),
                   "sxfir_decimate");
         if (n_out != m) throw std::runtime_error("rx chain: decimator produced an unexpected block size");
     }
 
-    // stream samples [pos, pos+m) of all channels -> out_[k] in HBM (channel stride m); ran_[k] fires behind the pass
-    void run_to_hbm(int k, int64_t pos, size_t m, void *st)
+    // stream samples [pos, pos+m) of all channels -> s.out in HBM (channel stride m); s.ran fires behind the pass
+    void run_to_hbm(Slot &s, int64_t pos, size_t m)
     {
-        grow(out_[k], 8 * m * (size_t)nchan_);
-        run(pos, m, static_cast<float *>(out_[k].get()), m, st);
-        gpu_check(sxfir_event_record(ran_[k], st), "sxfir_event_record");
+        grow(s.out, 8 * m * (size_t)nchan_, stream_, copy_);
+        run(pos, m, static_cast<float *>(s.out.get()), m);
+        s.ran.record(stream_);
     }
 
-    // stream samples [pos, pos+m) of all channels -> staging slot k, asynchronously on the chain's stream
-    void launch(int k, int64_t pos, size_t m)
+    // stream samples [pos, pos+m) of all channels -> slot s, asynchronously on the chain's stream
+    void launch(Slot &s, int64_t pos, size_t m)
     {
-        void *st = stream_->get();
         const size_t bytes = 8 * m * (size_t)nchan_;
-        slot_[k].in_hbm = false;
         if (bytes >= kSdmaFromBytes && prefer_hbm_) {
             // large batch for a reader with page-locked buffers: it stays in HBM until that reader names its buffer
-            run_to_hbm(k, pos, m, st);
-            slot_[k].in_hbm = true;
-        } else if (bytes >= kSdmaFromBytes) {
+            run_to_hbm(s, pos, m);
+            s.launched(pos, m, Slot::InHbm);
+            return;
+        }
+        grow(s.stage, bytes, stream_, copy_);
+        if (bytes >= kSdmaFromBytes) {
             // large batch: HBM, then one DMA-engine copy into the pinned staging buffer, queued behind the kernels
             // on the same stream
-            grow(stage_[k], bytes);
-            run_to_hbm(k, pos, m, st);
-            gpu_check(sxfir_memcpy_d2h(stage_[k].floats(), out_[k].get(), bytes, st), "sxfir_memcpy_d2h");
-            gpu_check(sxfir_event_record(done_[k], st), "sxfir_event_record");
+            run_to_hbm(s, pos, m);
+            gpu_check(sxfir_memcpy_d2h(s.stage.floats(), s.out.get(), bytes, stream_.get()), "sxfir_memcpy_d2h");
         } else {
-            grow(stage_[k], bytes);
             // the decimator stores straight into the pinned staging buffer (device-visible host memory): the
             // outputs are 1/decim of the traffic and cross PCIe as they are produced, no separate D2H copy
-            run(pos, m, stage_[k].floats(), m, st);
-            gpu_check(sxfir_event_record(done_[k], st), "sxfir_event_record");
+            run(pos, m, s.stage.floats(), m);
         }
-        slot_[k].pos = pos;
-        slot_[k].n = m;
-        slot_[k].ready = false;
-    }
-
-    // a buffer is replaced by a larger one only when nothing queued on the chain's stream can still use it
-    template <class Buffer>
-    void grow(Buffer &b, size_t bytes)
-    {
-        if (b.fits(bytes)) return;
-        stream_->sync();
-        copy_->sync();
-        b.reserve(bytes);
-    }
-
-    // samples of [pos, ...) the two staging slots hold, contiguously from pos
-    size_t staged_from(int64_t pos) const
-    {
-        size_t have = 0;
-        int64_t p = pos;
-        for (int pass = 0; pass < 2; ++pass) {
-            const Slot &s = slot_[pass == 0 ? cur_ : cur_ ^ 1];
-            if (s.n && p >= s.pos && p < s.pos + (int64_t)s.n) {
-                have += (size_t)(s.pos + (int64_t)s.n - p);
-                p = s.pos + (int64_t)s.n;
-            }
-        }
-        return have;
-    }
-
-    // wait for THIS slot's pass; true when the host really had to wait for it (more than a few microseconds)
-    bool waited(int k)
-    {
-        if (slot_[k].ready || slot_[k].in_hbm) return false;
-        const auto t0 = std::chrono::steady_clock::now();
-        wait(k);
-        return std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(3);
-    }
-
-    // wait for THIS slot's pass only: the batch read ahead behind it stays in flight
-    void wait(int k)
-    {
-        if (slot_[k].ready || slot_[k].in_hbm) return;     // (in HBM: ordered on the GPU, hand_out queues the copy)
-        gpu_check(sxfir_event_sync(done_[k]), "sxfir_event_sync");
-        slot_[k].ready = true;
+        s.done.record(stream_);
+        s.launched(pos, m, Slot::InFlight);
     }
 
     // After a skip (overrun) or a restart the filter history is rebuilt from
     // the source: run the ntaps samples that precede `pos` through the plan.
     void prime(int64_t pos)
     {
-        void *st = stream_->get();
-        gpu_check(sxfir_reset(plan_, st), "sxfir_reset");
+        gpu_check(sxfir_reset(plan_.get(), stream_.get()), "sxfir_reset");
         const int64_t warm = (ntaps_ + decim_ - 1) / decim_;     // outputs whose inputs cover ntaps samples
-        grow(scratch_, 8 * (size_t)warm * (size_t)nchan_);
-        grow(in_, 8 * (size_t)(warm * decim_) * (size_t)nchan_);
+        grow(scratch_, 8 * (size_t)warm * (size_t)nchan_, stream_, copy_);
+        grow(in_, 8 * (size_t)(warm * decim_) * (size_t)nchan_, stream_, copy_);
         const int64_t from = pos - warm;                          // may be negative: source index < 0 is zero
         size_t n_out = 0;
         gpu_check(sxfir_synth_fill(in_.get(), (size_t)(warm * decim_), (size_t)(warm * decim_), nchan_, seed_,
-                                   first_channel_, from * decim_, fmt_, st),
+                                   first_channel_, from * decim_, fmt_, stream_.get()),
                   "sxfir_synth_fill");
-        gpu_check(sxfir_decimate(plan_, in_.get(), (size_t)(warm * decim_), (size_t)(warm * decim_), scratch_.get(),
-                                 (size_t)warm, &n_out, st),
+        gpu_check(sxfir_decimate(plan_.get(), in_.get(), (size_t)(warm * decim_), (size_t)(warm * decim_), scratch_.get(),
+                                 (size_t)warm, &n_out, stream_.get()),
                   "sxfir_decimate(prime)");
     }
 
@@ -580,23 +618,19 @@ private:
     uint64_t seed_;
     uint32_t first_channel_;
     int fmt_;
-    sxfir_plan *plan_;
-    std::unique_ptr<GpuStream> stream_;
+    DeviceSelect device_;            // in front of everything created on the device
+    GpuStream stream_;
+    GpuStream copy_;                 // DMA copies out of HBM into page-locked caller memory, beside the kernels on stream_
+    PlanHandle plan_;
     DeviceBuffer in_, scratch_;      // wideband source block; outputs of the priming pass (discarded)
-    std::unique_ptr<GpuStream> copy_;   // DMA copies out of HBM into page-locked caller memory, beside the kernels on stream_
-    DeviceBuffer out_[2];            // decimated block of a large pass, before its DMA copy to the host
-    void *ran_[2];                   // recorded behind the pass that filled out_[k]
     CopyPool pool_;
-    PinnedBuffer stage_[2];
     Slot slot_[2];
-    void *done_[2];                  // recorded behind each slot's pass (its DMA copy, for a large one)
-    void *direct_done_;
+    GpuEvent direct_done_;
     int64_t next_;
     int cur_;
     size_t batch_, max_batch_;
     int64_t direct_samples_ = 0;     // samples that reached page-locked caller memory without a host copy
-    size_t grown_ = 0;               // batch length a reader that outran the read-ahead has earned (0 = none)
-    bool dst_locked_ = false;        // this call's destination is page-locked
+    size_t grown_ = 0;               // batch length a reader that outran the read-ahead has earned (0 = none; at most kGrowCap)
     bool prefer_hbm_ = false;        // the last megabyte-sized read went to page-locked memory
 };
 
@@ -619,51 +653,29 @@ public:
     // wire_s32: the DAC-rate sink holds S32_LE I2S words with the transmitter-keying bits
     // (convert_tx_buffer, SoapySX.cpp:116-137, fused into the interpolator's store).
     TxChain(int gpu, int interp, int taps_per_phase, size_t ring_frames, int nchan, bool wire_s32)
-        : gpu_(gpu), interp_(interp), ntaps_(interp * taps_per_phase), nchan_(nchan), plan_(nullptr),
-          ring_len_(ring_frames * (size_t)interp), next_(0), accepted_(0), written_(0), slot_(0), pend_(0)
+        : gpu_(gpu), interp_(interp), ntaps_(interp * taps_per_phase), nchan_(nchan), ring_len_(ring_frames * (size_t)interp),
+          device_(gpu), plan_(nullptr, sxfir_destroy), next_(0), accepted_(0), written_(0), slot_(0), pend_(0)
     {
         slot_frames_ = kMinSlotFrames;
         max_slot_frames_ = kMinSlotFrames;
         while (2 * max_slot_frames_ * 8 * (size_t)nchan_ <= kMaxSlotBytes) max_slot_frames_ *= 2;
-        gpu_check(sxfir_set_device(gpu_), "sxfir_set_device");
-        stream_.reset(new GpuStream());
-        copy_.reset(new GpuStream());
         std::vector<float> taps((size_t)ntaps_);
         // gain = interp: unity pass-band gain after zero stuffing
         gpu_check(sxfir_design_lowpass(ntaps_, interp_, 8.0, (double)interp_, taps.data()), "sxfir_design_lowpass");
-        gpu_check(sxfir_create(&plan_, SXFIR_INTERPOLATE, taps.data(), ntaps_, interp_, nchan_,
-                               wire_s32 ? SXFIR_S32 : SXFIR_CF32, gpu_),
+        sxfir_plan *plan = nullptr;
+        gpu_check(sxfir_create(&plan, SXFIR_INTERPOLATE, taps.data(), ntaps_, interp_, nchan_, wire_s32 ? SXFIR_S32 : SXFIR_CF32, gpu_),
                   "sxfir_create(tx)");
+        plan_.reset(plan);
         ring_.reserve(8 * ring_len_ * (size_t)nchan_);
         stage_.reserve(8 * slot_frames_ * (size_t)nchan_ * kSlots);
         keyed_.reserve(64);
         zero_keyed();
         set_threshold2(thr2_);                             // the plan and the chain count with the same threshold bits
-        for (int k = 0; k < kSlots; ++k) {
-            busy_[k] = false;
-            done_[k] = nullptr;
-            gpu_check(sxfir_event_create(&done_[k]), "sxfir_event_create");
-        }
-        direct_done_ = nullptr;
-        gpu_check(sxfir_event_create(&direct_done_), "sxfir_event_create");
-        for (int j = 0; j < 2; ++j) {
-            copied_[j] = used_[j] = nullptr;
-            in_used_[j] = false;
-            gpu_check(sxfir_event_create(&copied_[j]), "sxfir_event_create");
-            gpu_check(sxfir_event_create(&used_[j]), "sxfir_event_create");
-        }
     }
     ~TxChain()
     {
-        sxfir_stream_sync(stream_->get());
-        sxfir_stream_sync(copy_->get());
-        for (int k = 0; k < kSlots; ++k) sxfir_event_destroy(done_[k]);
-        sxfir_event_destroy(direct_done_);
-        for (int j = 0; j < 2; ++j) {
-            sxfir_event_destroy(copied_[j]);
-            sxfir_event_destroy(used_[j]);
-        }
-        sxfir_destroy(plan_);
+        sxfir_stream_sync(stream_.get());
+        sxfir_stream_sync(copy_.get());
     }
     TxChain(const TxChain &) = delete;
     TxChain &operator=(const TxChain &) = delete;
@@ -673,7 +685,7 @@ public:
     sxfir_geometry geometry() const
     {
         sxfir_geometry g;
-        gpu_check(sxfir_launch_geometry(plan_, 4096, &g), "sxfir_launch_geometry");
+        gpu_check(sxfir_launch_geometry(plan_.get(), 4096, &g), "sxfir_launch_geometry");
         return g;
     }
     int64_t written() const { return written_; }
@@ -682,7 +694,7 @@ public:
     void set_threshold2(float thr2)
     {
         thr2_ = thr2;
-        gpu_check(sxfir_set_tx_threshold(plan_, thr2), "sxfir_set_tx_threshold");
+        gpu_check(sxfir_set_tx_threshold(plan_.get(), thr2), "sxfir_set_tx_threshold");
     }
 
     // Transmitter keying of convert_tx_buffer (SoapySX.cpp:132-133): how many application samples of channel 0
@@ -694,7 +706,7 @@ public:
         gpu_check(sxfir_set_device(gpu_), "sxfir_set_device");
         flush();
         unsigned long long v = 0;
-        gpu_check(sxfir_memcpy_d2h(&v, keyed_.get(), sizeof(v), stream_->get()), "sxfir_memcpy_d2h");
+        gpu_check(sxfir_memcpy_d2h(&v, keyed_.get(), sizeof(v), stream_.get()), "sxfir_memcpy_d2h");
         drain();
         return (int64_t)v;
     }
@@ -704,7 +716,7 @@ public:
         gpu_check(sxfir_set_device(gpu_), "sxfir_set_device");
         pend_ = 0;                  // what was not passed to the GPU yet is dropped with the rest of the sink
         drain();
-        gpu_check(sxfir_reset(plan_, stream_->get()), "sxfir_reset");
+        gpu_check(sxfir_reset(plan_.get(), stream_.get()), "sxfir_reset");
         next_ = 0;
         accepted_ = 0;
         written_ = 0;
@@ -720,7 +732,7 @@ public:
         gpu_check(sxfir_set_device(gpu_), "sxfir_set_device");
         if (pos < accepted_) throw std::runtime_error("tx chain: position moved backwards");
         feed(nullptr, (size_t)(pos - accepted_));
-        if (n >= kDirectFrom && device_visible(srcs, n)) direct(srcs, n);
+        if (n >= kDirectFrom && page_locked(srcs, nchan_, n)) direct(srcs, n);
         else feed(srcs, n);
         written_ += (int64_t)n;
     }
@@ -740,7 +752,7 @@ public:
             const size_t off = (size_t)((dac_pos + (int64_t)done) % (int64_t)ring_len_);
             const size_t m = std::min(n - done, ring_len_ - off);
             gpu_check(sxfir_memcpy_d2h(host_dst + 2 * done, ring_.at(8 * ((size_t)channel * ring_len_ + off)), 8 * m,
-                                       stream_->get()),
+                                       stream_.get()),
                       "sxfir_memcpy_d2h");
             done += m;
         }
@@ -748,11 +760,23 @@ public:
     }
 
 private:
+    // One of the pinned slots the caller's samples gather in (a quarter of stage_).
+    struct PinnedSlot {
+        GpuEvent done;               // recorded behind the slot's GPU pass (behind its DMA copies, for a large one)
+        bool busy = false;           // ... which may still be reading the slot
+    };
+    // One of the two alternating input blocks of large passes in HBM (DMA-copied from the slot or the caller).
+    struct InputBlock {
+        DeviceBuffer buf;
+        GpuEvent copied, used;       // buf filled (copy stream) / read by its kernels (stream_)
+        bool in_use = false;         // `used` has been recorded: kernels may still be reading buf
+    };
+
     void drain()
     {
-        copy_->sync();
-        stream_->sync();
-        for (int k = 0; k < kSlots; ++k) busy_[k] = false;
+        copy_.sync();
+        stream_.sync();
+        for (PinnedSlot &s : slots_) s.busy = false;
     }
 
     // n stream samples per channel (srcs == nullptr: silence) are appended to the current pinned slot
@@ -769,15 +793,14 @@ private:
         }
         size_t done = 0;
         while (done < n) {
-            if (pend_ == 0 && busy_[slot_]) {
+            PinnedSlot &s = slots_[slot_];
+            if (pend_ == 0 && s.busy) {
                 // the slot's last H2D may still be reading it: wait for THAT pass only, not for the newer ones
-                const auto t0 = std::chrono::steady_clock::now();
-                gpu_check(sxfir_event_sync(done_[slot_]), "sxfir_event_sync");
-                busy_[slot_] = false;
+                const bool late = really_waited(s.done);
+                s.busy = false;
                 // a writer that comes round to a slot still in use is faster than one GPU pass per kFlushFrames
                 // samples (no sample clock holding it back): gather twice as much per pass from here on
-                if (flush_frames_ < slot_frames_ && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(3))
-                    flush_frames_ *= 2;
+                if (flush_frames_ < slot_frames_ && late) flush_frames_ *= 2;
             }
             const size_t m = std::min(slot_frames_ - pend_, n - done);
             float *host = stage_.floats() + 2 * slot_frames_ * (size_t)nchan_ * (size_t)slot_;
@@ -802,26 +825,20 @@ private:
     void flush()
     {
         if (pend_ == 0) return;
-        void *st = stream_->get();
+        PinnedSlot &s = slots_[slot_];
         const size_t slot_off = slot_frames_ * (size_t)nchan_ * (size_t)slot_;
         const char *host = reinterpret_cast<const char *>(stage_.floats() + 2 * slot_off);
         if (8 * pend_ * (size_t)nchan_ >= kH2dFromBytes) {
             // large pass: DMA-engine copies into HBM on the copy stream, beside the kernels of the pass before; the
             // slot is free again as soon as they are through
-            void *cst = begin_copy();
-            for (int c = 0; c < nchan_; ++c)
-                gpu_check(sxfir_memcpy_h2d(in_dev_[cur_in_].at(8 * (size_t)c * max_slot_frames_),
-                                           host + 8 * (size_t)c * slot_frames_, 8 * pend_, cst),
-                          "sxfir_memcpy_h2d");
-            gpu_check(sxfir_event_record(done_[slot_], cst), "sxfir_event_record");
-            pass_copied(pend_, st);
+            pass_by_dma([&](int c) { return host + 8 * (size_t)c * slot_frames_; }, pend_, &s.done);
         } else {
             // the interpolator reads its input straight from the pinned slot (device-visible host memory): the
             // input is 1/interp of the traffic and crosses PCIe as the kernel fetches it, no separate H2D copy
-            pass(host, slot_frames_, pend_, st);
-            gpu_check(sxfir_event_record(done_[slot_], st), "sxfir_event_record");
+            pass(host, slot_frames_, pend_);
+            s.done.record(stream_);
         }
-        busy_[slot_] = true;
+        s.busy = true;
         slot_ = (slot_ + 1) % kSlots;
         pend_ = 0;
     }
@@ -829,8 +846,9 @@ private:
     // `frames` stream samples per channel at `base` (device-visible, channel stride `stride` samples) -> the
     // interpolator -> sink ring at ring position next_*interp (in two passes where the ring wraps); the ranges of
     // data_ (application data, relative to base) take part in the keying count
-    void pass(const char *base, size_t stride, size_t frames, void *st)
+    void pass(const char *base, size_t stride, size_t frames)
     {
+        void *st = stream_.get();
         // One range of application data (the usual case: a slot is all data, or data behind a timed gap): the
         // interpolator takes the keying count itself from the tile it has staged in LDS, so a pass read in place from
         // the pinned slot crosses PCIe once (round 3: a second kernel read the slot again, 1.2-1.8 GS/s for 4096 ...
@@ -845,11 +863,11 @@ private:
             // this call's share of the keying range, relative to its first sample
             const size_t lo = std::min(std::max(k_lo, done), done + m) - done, hi = std::min(std::max(k_hi, done), done + m) - done;
             if (fused && hi > lo)
-                gpu_check(sxfir_interpolate_keyed(plan_, base + 8 * done, m, stride, ring_.at(8 * off), ring_len_, &n_out, lo,
+                gpu_check(sxfir_interpolate_keyed(plan_.get(), base + 8 * done, m, stride, ring_.at(8 * off), ring_len_, &n_out, lo,
                                                   hi - lo, keyed_counter(), st),
                           "sxfir_interpolate_keyed");
             else
-                gpu_check(sxfir_interpolate(plan_, base + 8 * done, m, stride, ring_.at(8 * off), ring_len_, &n_out, st),
+                gpu_check(sxfir_interpolate(plan_.get(), base + 8 * done, m, stride, ring_.at(8 * off), ring_len_, &n_out, st),
                           "sxfir_interpolate");
             next_ += (int64_t)m;
             done += m;
@@ -861,60 +879,45 @@ private:
         data_.clear();
     }
 
-    // Are the caller's blocks page-locked (pinned / registered with sxfir_host_register)?  Then the DMA engines
-    // can take them as they are.
-    bool device_visible(const float *const *srcs, size_t n) const
-    {
-        for (int c = 0; c < nchan_; ++c) {
-            void *d = nullptr;
-            if (sxfir_host_device_pointer(srcs[c], 8 * n, &d) != SXFIR_OK) return false;
-        }
-        return true;
-    }
-
     // A large write from page-locked caller memory: no staging copy.  The blocks go to HBM by DMA and through the
     // kernels from there; the call returns when the last copy has read the caller's memory (the kernels run on).
     void direct(const float *const *srcs, size_t n)
     {
         flush();                                           // what was gathered before comes first
-        void *st = stream_->get();
         size_t done = 0;
         while (done < n) {
             const size_t m = std::min(n - done, max_slot_frames_);
-            void *cst = begin_copy();
-            for (int c = 0; c < nchan_; ++c)
-                gpu_check(sxfir_memcpy_h2d(in_dev_[cur_in_].at(8 * (size_t)c * max_slot_frames_), srcs[c] + 2 * done, 8 * m, cst),
-                          "sxfir_memcpy_h2d");
-            if (done + m == n) gpu_check(sxfir_event_record(direct_done_, cst), "sxfir_event_record");
             data_.emplace_back(0, m);
-            pass_copied(m, st);
+            pass_by_dma([&](int c) { return srcs[c] + 2 * done; }, m, done + m == n ? &direct_done_ : nullptr);
             done += m;
         }
-        gpu_check(sxfir_event_sync(direct_done_), "sxfir_event_sync");
+        direct_done_.sync();
         accepted_ += (int64_t)n;
         direct_samples_ += (int64_t)n;
     }
 
-    // The next input block in HBM (two alternate): it may be filled once the kernels that read its last contents
-    // are through.  Returns the copy stream.
-    void *begin_copy()
+    // Copy `m` frames per channel from source(c) into the next input block in HBM (two alternate) by DMA on the copy
+    // stream -- `read`, if given, is recorded behind the copies: the source is free again when it fires -- and run the
+    // pass over the block behind them.
+    template <class Source>
+    void pass_by_dma(Source source, size_t m, const GpuEvent *read)
     {
-        grow(in_dev_[cur_in_], 8 * max_slot_frames_ * (size_t)nchan_);
+        InputBlock &b = in_dev_[cur_in_];
+        grow(b.buf, 8 * max_slot_frames_ * (size_t)nchan_, copy_, stream_);
+        // The block may be filled once the kernels that read its last contents are through.
         // (the HOST waits here, not the copy stream: the application thread is then never more than two passes
         // ahead of the GPU.  With the wait queued on the copy stream instead, a caller that runs ahead makes
         // hipMemcpyAsync itself block for 7-8 ms now and then on ROCm 7.2 -- measured, tools/devpath_probe.py.)
-        if (in_used_[cur_in_]) gpu_check(sxfir_event_sync(used_[cur_in_]), "sxfir_event_sync");
-        return copy_->get();
-    }
-
-    // ... and the kernels over it, once the copies queued since begin_copy() are through
-    void pass_copied(size_t frames, void *st)
-    {
-        gpu_check(sxfir_event_record(copied_[cur_in_], copy_->get()), "sxfir_event_record");
-        gpu_check(sxfir_stream_wait_event(st, copied_[cur_in_]), "sxfir_stream_wait_event");
-        pass(in_dev_[cur_in_].at(0), max_slot_frames_, frames, st);
-        gpu_check(sxfir_event_record(used_[cur_in_], st), "sxfir_event_record");
-        in_used_[cur_in_] = true;
+        if (b.in_use) b.used.sync();
+        for (int c = 0; c < nchan_; ++c)
+            gpu_check(sxfir_memcpy_h2d(b.buf.at(8 * (size_t)c * max_slot_frames_), source(c), 8 * m, copy_.get()), "sxfir_memcpy_h2d");
+        if (read) read->record(copy_);
+        // ... and the kernels over it, once the copies are through
+        b.copied.record(copy_);
+        b.copied.hold(stream_);
+        pass(b.buf.at(0), max_slot_frames_, m);
+        b.used.record(stream_);
+        b.in_use = true;
         cur_in_ ^= 1;
     }
 
@@ -927,45 +930,33 @@ private:
         slot_ = 0;
     }
 
-    // a buffer is replaced by a larger one only when nothing queued on the chain's stream can still use it
-    template <class Buffer>
-    void grow(Buffer &b, size_t bytes)
-    {
-        if (b.fits(bytes)) return;
-        copy_->sync();
-        stream_->sync();
-        b.reserve(bytes);
-    }
-
     unsigned long long *keyed_counter() const { return static_cast<unsigned long long *>(keyed_.get()); }
     void zero_keyed()
     {
         static const unsigned long long zero = 0;
-        gpu_check(sxfir_memcpy_h2d(keyed_.get(), &zero, sizeof(zero), stream_->get()), "sxfir_memcpy_h2d");
-        stream_->sync();
+        gpu_check(sxfir_memcpy_h2d(keyed_.get(), &zero, sizeof(zero), stream_.get()), "sxfir_memcpy_h2d");
+        stream_.sync();
     }
 
     int gpu_, interp_, ntaps_, nchan_;
-    sxfir_plan *plan_;
     size_t ring_len_;
-    std::unique_ptr<GpuStream> stream_;
+    DeviceSelect device_;                                 // in front of everything created on the device
+    GpuStream stream_;
+    GpuStream copy_;                                      // DMA copies of large passes, beside the kernels on stream_
+    PlanHandle plan_;
     DeviceBuffer ring_;
     PinnedBuffer stage_;
-    std::unique_ptr<GpuStream> copy_;                     // DMA copies of large passes, beside the kernels on stream_
-    DeviceBuffer in_dev_[2];                              // input blocks of large passes (DMA-copied from the slot or the caller)
-    void *copied_[2], *used_[2];                          // in_dev_[j] filled (copy stream) / read by its kernels (stream_)
-    bool in_used_[2];
+    InputBlock in_dev_[2];
     int cur_in_ = 0;
     CopyPool pool_;
     size_t slot_frames_, max_slot_frames_;
     size_t flush_frames_ = kFlushFrames;                  // samples gathered before a GPU pass; grows for writers that outrun the passes
-    void *direct_done_;
+    GpuEvent direct_done_;
     int64_t direct_samples_ = 0;                          // samples taken straight from page-locked caller memory
     DeviceBuffer keyed_;                                  // the keying counter (device memory, read back on demand)
     float thr2_ = 1.0e-6f;
     std::vector<std::pair<size_t, size_t>> data_;         // (offset, length) of application data in the current slot
-    bool busy_[kSlots];
-    void *done_[kSlots];  // recorded behind each slot's GPU pass
+    PinnedSlot slots_[kSlots];
     int64_t next_;        // stream samples passed to the GPU so far (written + silence)
     int64_t accepted_;    // next_ + what is gathered in the current slot
     int64_t written_;     // stream samples that carried application data

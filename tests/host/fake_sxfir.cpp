@@ -14,6 +14,18 @@
 // happens-before edges between a stream's thread and the caller).  Stricter than the hardware in one respect: copies
 // from or to ordinary (pageable) host memory are queued like any other, where hipMemcpyAsync would stage them before
 // returning.
+//
+// TRACE MODE (fake_sxfir_trace_open, called by chains_probe's `trace` argument) locks WHICH calls the host code issues,
+// which the sample checks do not cover: every queued item runs inline on the calling thread (no stream threads, no
+// jitter), the arithmetic is skipped, and every traced call appends one line to a file.  That alone is not yet
+// deterministic: the chains time their waits against 3 us, and an inline wait that writes a trace line or is preempted
+// can take longer -- chains_probe therefore gives the chains a clock that stands still while it traces (SX_WAIT_CLOCK).  Streams, events,
+// plans and allocations are never named by address or creation order: each gets a small integer in order of its first
+// appearance in the section, a pointer is written as kind + number + byte offset (dev = sxfir_malloc, pin =
+// sxfir_host_alloc, lock / page = the caller's page-locked / pageable range for this call as the probe declared it,
+// host = anything else, e.g. a variable of the chain's own), so a trace is invariant under a renaming of objects and
+// nothing else.  Creation / destruction of streams, events and plans, the two frees, sxfir_set_device,
+// sxfir_host_device_pointer and sxfir_launch_geometry are not traced (they may move when members are reordered).
 #include <sxfir.h>
 
 #include <atomic>
@@ -24,6 +36,7 @@
 #include <cstring>
 #include <deque>
 #include <functional>
+#include <map>
 #include <mutex>
 #include <random>
 #include <string>
@@ -35,6 +48,51 @@ extern "C" {
 }
 
 namespace {
+
+// ---- trace mode (single-threaded by construction: everything runs on the calling thread)
+struct Trace {
+    FILE *f = nullptr;
+    std::map<const void *, int> streams, events, plans;
+    struct Range { const char *base; size_t bytes; int id; const char *kind; };
+    std::vector<Range> allocs, caller;                    // live sxfir_malloc / sxfir_host_alloc blocks; this call's caller ranges
+    std::map<std::string, int> next_id;                   // per kind
+
+    bool on() const { return f != nullptr; }
+    void section()
+    {
+        streams.clear(); events.clear(); plans.clear(); caller.clear(); next_id.clear();
+        for (Range &r : allocs) r.id = -1;                 // still allocated (none, between the probe's scripts): renumbered on sight
+    }
+    int number(std::map<const void *, int> &m, const void *p)
+    {
+        auto it = m.find(p);
+        if (it == m.end()) it = m.emplace(p, (int)m.size()).first;
+        return it->second;
+    }
+    std::string stream(const void *p) { return "s" + std::to_string(number(streams, p)); }
+    std::string event(const void *p) { return "e" + std::to_string(number(events, p)); }
+    std::string plan(const void *p) { return "p" + std::to_string(number(plans, p)); }
+    std::string ptr(const void *p)
+    {
+        const char *c = static_cast<const char *>(p);
+        for (std::vector<Range> *v : {&caller, &allocs})
+            for (Range &r : *v)
+                if (c >= r.base && c < r.base + r.bytes) {
+                    if (r.id < 0) r.id = next_id[r.kind]++;
+                    return std::string(r.kind) + std::to_string(r.id) + "+" + std::to_string((size_t)(c - r.base));
+                }
+        return "host";
+    }
+    void allocated(const void *p, size_t bytes, const char *kind) { allocs.push_back(Range{static_cast<const char *>(p), bytes, -1, kind}); }
+    void freed(const void *p)
+    {
+        for (size_t i = 0; i < allocs.size(); ++i)
+            if (allocs[i].base == p) { allocs.erase(allocs.begin() + i); return; }
+    }
+};
+Trace g_trace;
+#define TRACE(...) do { if (g_trace.on()) std::fprintf(g_trace.f, __VA_ARGS__); } while (0)
+#define Z(x) ((unsigned long long)(x))
 
 struct Stream {
     std::mutex m;
@@ -50,7 +108,7 @@ struct Stream {
     {
         const char *e = std::getenv("FAKE_SXFIR_JITTER_US");
         jitter_us = e ? std::atoi(e) : 40;
-        worker = std::thread([this] { serve(); });
+        if (!g_trace.on()) worker = std::thread([this] { serve(); });
     }
     ~Stream()
     {
@@ -59,7 +117,7 @@ struct Stream {
             stop = true;
         }
         cv.notify_all();
-        worker.join();
+        if (worker.joinable()) worker.join();
     }
     void serve()
     {
@@ -80,6 +138,7 @@ struct Stream {
     }
     void push(std::function<void()> f)
     {
+        if (g_trace.on()) { f(); return; }               // trace mode: inline, on the calling thread
         {
             std::lock_guard<std::mutex> lk(m);
             q.push_back(std::move(f));
@@ -174,17 +233,30 @@ int sxfir_device_info(int, char *name, char *arch, int *compute_units, size_t *h
     if (hbm_bytes) *hbm_bytes = 0;
     return SXFIR_OK;
 }
-int sxfir_malloc(void **dev, size_t bytes) { *dev = std::malloc(bytes ? bytes : 1); return *dev ? SXFIR_OK : SXFIR_ENOMEM; }
-int sxfir_free(void *dev) { drain_all(); std::free(dev); return SXFIR_OK; }
+int sxfir_malloc(void **dev, size_t bytes)
+{
+    *dev = std::malloc(bytes ? bytes : 1);
+    if (!*dev) return SXFIR_ENOMEM;
+    if (g_trace.on()) {
+        g_trace.allocated(*dev, bytes ? bytes : 1, "dev");
+        TRACE("malloc %s %llu\n", g_trace.ptr(*dev).c_str(), Z(bytes));
+    }
+    return SXFIR_OK;
+}
+int sxfir_free(void *dev) { drain_all(); if (g_trace.on()) g_trace.freed(dev); std::free(dev); return SXFIR_OK; }
 int sxfir_host_alloc(void **host, size_t bytes)
 {
     *host = std::malloc(bytes ? bytes : 1);
     if (!*host) return SXFIR_ENOMEM;
+    if (g_trace.on()) {
+        g_trace.allocated(*host, bytes ? bytes : 1, "pin");
+        TRACE("host_alloc %s %llu\n", g_trace.ptr(*host).c_str(), Z(bytes));
+    }
     std::lock_guard<std::mutex> lk(g_locked_m);
     g_locked.emplace_back((const char *)*host, bytes ? bytes : 1);
     return SXFIR_OK;
 }
-int sxfir_host_free(void *host) { drain_all(); unlock(host); std::free(host); return SXFIR_OK; }
+int sxfir_host_free(void *host) { drain_all(); if (g_trace.on()) g_trace.freed(host); unlock(host); std::free(host); return SXFIR_OK; }
 int sxfir_host_register(void *host, size_t bytes)
 {
     std::lock_guard<std::mutex> lk(g_locked_m);
@@ -215,12 +287,18 @@ int sxfir_stream_destroy(void *stream)
     delete s;
     return SXFIR_OK;
 }
-int sxfir_stream_sync(void *stream) { S(stream)->sync(); return SXFIR_OK; }
+int sxfir_stream_sync(void *stream)
+{
+    TRACE("stream_sync %s\n", g_trace.stream(stream).c_str());
+    S(stream)->sync();
+    return SXFIR_OK;
+}
 int sxfir_event_create(void **event) { *event = new Event(); return SXFIR_OK; }
 int sxfir_event_destroy(void *event) { delete static_cast<Event *>(event); return SXFIR_OK; }
 int sxfir_event_record(void *event, void *stream)
 {
     Event *e = static_cast<Event *>(event);
+    TRACE("event_record %s %s\n", g_trace.event(event).c_str(), g_trace.stream(stream).c_str());
     unsigned long long gen;
     {
         std::lock_guard<std::mutex> lk(e->m);
@@ -237,6 +315,7 @@ int sxfir_event_sync(void *event)
 {
     // an event that was never recorded counts as complete (hipEventSynchronize)
     Event *e = static_cast<Event *>(event);
+    TRACE("event_sync %s\n", g_trace.event(event).c_str());
     std::unique_lock<std::mutex> lk(e->m);
     const unsigned long long gen = e->recorded;
     e->cv.wait(lk, [&] { return e->fired >= gen; });
@@ -245,6 +324,7 @@ int sxfir_event_sync(void *event)
 int sxfir_stream_wait_event(void *stream, void *event)
 {
     Event *e = static_cast<Event *>(event);
+    TRACE("stream_wait_event %s %s\n", g_trace.stream(stream).c_str(), g_trace.event(event).c_str());
     unsigned long long gen;
     {
         std::lock_guard<std::mutex> lk(e->m);
@@ -258,11 +338,13 @@ int sxfir_stream_wait_event(void *stream, void *event)
 }
 int sxfir_memcpy_h2d(void *dst, const void *src, size_t bytes, void *stream)
 {
+    TRACE("memcpy_h2d %s %s %llu %s\n", g_trace.ptr(dst).c_str(), g_trace.ptr(src).c_str(), Z(bytes), g_trace.stream(stream).c_str());
     S(stream)->push([dst, src, bytes] { std::memcpy(dst, src, bytes); });
     return SXFIR_OK;
 }
 int sxfir_memcpy_d2h(void *dst, const void *src, size_t bytes, void *stream)
 {
+    TRACE("memcpy_d2h %s %s %llu %s\n", g_trace.ptr(dst).c_str(), g_trace.ptr(src).c_str(), Z(bytes), g_trace.stream(stream).c_str());
     S(stream)->push([dst, src, bytes] { std::memcpy(dst, src, bytes); });
     return SXFIR_OK;
 }
@@ -278,6 +360,11 @@ static void count_keyed_now(const float *src, size_t n, float thr2, unsigned lon
 }
 int sxfir_count_keyed(const float *src, size_t n, float thr2, unsigned long long *counter, void *stream)
 {
+    if (g_trace.on()) {                                  // the arithmetic is skipped
+        TRACE("count_keyed %s %llu %.9g %s %s\n", g_trace.ptr(src).c_str(), Z(n), (double)thr2, g_trace.ptr(counter).c_str(),
+              g_trace.stream(stream).c_str());
+        return SXFIR_OK;
+    }
     S(stream)->push([=] { count_keyed_now(src, n, thr2, counter); });
     return SXFIR_OK;
 }
@@ -321,16 +408,27 @@ int sxfir_launch_geometry(const sxfir_plan *p, size_t n_in, sxfir_geometry *g)
 int sxfir_destroy(sxfir_plan *p) { drain_all(); delete p; return SXFIR_OK; }
 int sxfir_reset(sxfir_plan *p, void *stream)
 {
+    TRACE("reset %s %s\n", g_trace.plan(p).c_str(), g_trace.stream(stream).c_str());
     S(stream)->push([p] { std::fill(p->hist.begin(), p->hist.end(), 0.0f); });
     return SXFIR_OK;
 }
 int sxfir_set_history(sxfir_plan *, const void *, size_t, size_t, void *) { g_err = "not in the fake"; return SXFIR_EUNSUPPORTED; }
-int sxfir_set_tx_threshold(sxfir_plan *p, float t) { p->thr2 = t; return SXFIR_OK; }
+int sxfir_set_tx_threshold(sxfir_plan *p, float t)
+{
+    TRACE("set_tx_threshold %s %.9g\n", g_trace.plan(p).c_str(), (double)t);
+    p->thr2 = t;
+    return SXFIR_OK;
+}
 
 int sxfir_synth_fill(void *out_dev, size_t n, size_t stride, int nchan, uint64_t seed, uint32_t first_channel,
                      int64_t start, int fmt, void *stream)
 {
     if (fmt != SXFIR_CF32) return fail("fake backend: CF32 only");
+    if (g_trace.on()) {
+        TRACE("synth_fill %s n %llu stride %llu nchan %d first %u start %lld %s\n", g_trace.ptr(out_dev).c_str(), Z(n), Z(stride),
+              nchan, first_channel, (long long)start, g_trace.stream(stream).c_str());
+        return SXFIR_OK;
+    }
     S(stream)->push([=] {
         for (int c = 0; c < nchan; ++c)
             sxo_synth_iq(seed, first_channel + (uint32_t)c, start, n, (float *)out_dev + 2 * (size_t)c * stride);
@@ -359,6 +457,15 @@ static void run_all(sxfir_plan *p, const void *in_dev, size_t n_in, size_t in_st
         run_channel(p, c, (const float *)in_dev + 2 * (size_t)c * in_stride, n_in, (float *)out_dev + 2 * (size_t)c * out_stride, n_out);
 }
 
+// trace mode: the pass's line (without its end), and the arithmetic is skipped
+static bool traced_pass(const char *what, sxfir_plan *p, const void *in_dev, size_t n_in, size_t in_stride, void *out_dev,
+                        size_t out_stride, void *stream)
+{
+    TRACE("%s %s in %s n %llu stride %llu out %s stride %llu %s", what, g_trace.plan(p).c_str(), g_trace.ptr(in_dev).c_str(), Z(n_in),
+          Z(in_stride), g_trace.ptr(out_dev).c_str(), Z(out_stride), g_trace.stream(stream).c_str());
+    return g_trace.on();
+}
+
 int sxfir_decimate(sxfir_plan *p, const void *in_dev, size_t n_in, size_t in_stride, void *out_dev, size_t out_stride,
                    size_t *n_out, void *stream)
 {
@@ -366,6 +473,7 @@ int sxfir_decimate(sxfir_plan *p, const void *in_dev, size_t n_in, size_t in_str
     ++g_fake_launches;
     const size_t no = n_in / (size_t)p->ratio;
     *n_out = no;
+    if (traced_pass("decimate", p, in_dev, n_in, in_stride, out_dev, out_stride, stream)) { TRACE("\n"); return SXFIR_OK; }
     S(stream)->push([=] { run_all(p, in_dev, n_in, in_stride, out_dev, out_stride, no); });
     return SXFIR_OK;
 }
@@ -377,6 +485,7 @@ int sxfir_interpolate(sxfir_plan *p, const void *in_dev, size_t n_in, size_t in_
     ++g_fake_launches;
     const size_t no = n_in * (size_t)p->ratio;
     *n_out = no;
+    if (traced_pass("interpolate", p, in_dev, n_in, in_stride, out_dev, out_stride, stream)) { TRACE("\n"); return SXFIR_OK; }
     S(stream)->push([=] { run_all(p, in_dev, n_in, in_stride, out_dev, out_stride, no); });
     return SXFIR_OK;
 }
@@ -390,12 +499,41 @@ int sxfir_interpolate_keyed(sxfir_plan *p, const void *in_dev, size_t n_in, size
     ++g_fake_launches;
     const size_t no = n_in * (size_t)p->ratio;
     *n_out = no;
+    if (traced_pass("interpolate_keyed", p, in_dev, n_in, in_stride, out_dev, out_stride, stream)) {
+        TRACE(" key %llu %llu %s\n", Z(key_first), Z(key_count), g_trace.ptr(counter).c_str());
+        return SXFIR_OK;
+    }
     const float thr2 = p->thr2;                          // as the real launch: the threshold in force when the pass is queued
     S(stream)->push([=] {
         run_all(p, in_dev, n_in, in_stride, out_dev, out_stride, no);
         count_keyed_now((const float *)in_dev + 2 * key_first, key_count, thr2, counter);
     });
     return SXFIR_OK;
+}
+
+// ---- trace mode's switches (test only; declared by chains_probe.cpp)
+int fake_sxfir_trace_open(const char *path)              // before anything else is created; NULL closes
+{
+    if (g_trace.f) std::fclose(g_trace.f);
+    g_trace.f = path ? std::fopen(path, "w") : nullptr;
+    return (path && !g_trace.f) ? SXFIR_EINVAL : SXFIR_OK;
+}
+void fake_sxfir_trace_section(const char *name)          // a new script: the numbering starts again
+{
+    g_trace.section();
+    TRACE("== %s\n", name);
+}
+// one call of the script: `what` heads its lines, and ptrs[c], bytes each, are the caller's memory for it
+void fake_sxfir_trace_call(const char *what, const void *const *ptrs, int nptrs, size_t bytes)
+{
+    if (!g_trace.on()) return;
+    g_trace.caller.clear();
+    for (int c = 0; c < nptrs; ++c) {
+        void *d = nullptr;
+        const bool locked = sxfir_host_device_pointer(ptrs[c], bytes, &d) == SXFIR_OK;
+        g_trace.caller.push_back(Trace::Range{static_cast<const char *>(ptrs[c]), bytes, -1, locked ? "lock" : "page"});
+    }
+    TRACE("-- %s\n", what);
 }
 
 }  // extern "C"

@@ -211,6 +211,52 @@ def test_gpu_chains_over_fake_backend(sanitized, flavour):
     assert keyed[1] == keyed[3] and int(keyed[1]) > 0 and "tx_keyed_after_reset 0" in lines
 
 
+def chains_call_trace(workdir):
+    """chains_probe built plain over the fake backend and run in trace mode: {script: [the ABI calls the chains issued]}."""
+    csrc = os.path.join(ROOT, "sxxcvr_amd", "csrc")
+    odir = os.path.join(ROOT, "oracle")
+    host = os.path.join(ROOT, "tests", "host")
+    exe, trace = os.path.join(workdir, "chains_probe"), os.path.join(workdir, "chains_calls.trace")
+    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), "-I" + csrc, "-I" + odir,
+           os.path.join(host, "chains_probe.cpp"), os.path.join(host, "fake_sxfir.cpp"), "-o", exe,
+           "-L" + odir, "-lsxoracle", "-Wl,-rpath," + odir, "-pthread"]
+    subprocess.run(cmd, check=True)
+    subprocess.run([exe, "trace", trace], check=True, stdout=subprocess.DEVNULL, timeout=300)
+    sections = {}
+    for line in open(trace).read().splitlines():
+        if line.startswith("== "):
+            sections[line[3:]] = cur = []
+        else:
+            cur.append(line)
+    return sections
+
+
+def test_gpu_chains_issue_the_recorded_calls(oracle, tmp_path):
+    """WHICH calls GpuChains.hpp issues, which the sample checks above do not cover: chains_probe replays its six call
+    scripts (rx_test, tx_test, rx_large_test, tx_large_test, rx_random_test's 90 operations, tx_random_test's 70; the
+    same block sizes, jumps and page-locked flags) over the fake backend in trace mode, and every traced ABI call --
+    allocations with their sizes, passes with their sizes and strides, copies, event records and waits, stream waits and
+    syncs, resets, thresholds; objects numbered by first appearance, pointers as kind + number + offset -- must equal
+    tests/golden/chains_calls.json line for line.  That file was recorded once, from the GpuChains.hpp of before the
+    chains were rewritten around slot and event types, and is not re-recorded: a difference is a change in what the
+    chains ask of the GPU.
+
+    Not covered, as expected: neither "the host really had to wait" branch fires -- batch growth for a fast reader
+    (grown_) and flush growth for a fast writer (flush_frames_) are not exercised here.  Running every queued item inline
+    does not ensure that by itself (an inline wait that flushes the trace file or is preempted can outlast the 3 us the
+    chains compare with, and a trace in which batches grew differs from the record): while it traces, the probe gives the
+    chains a clock that stands still (SX_WAIT_CLOCK in GpuChains.hpp, ProbeClock in chains_probe.cpp), so a traced wait
+    takes no time at all.  The growth paths stay covered by the asynchronous probes above, on samples and counters."""
+    import json
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "chains_calls.json")))["sections"]
+    got = chains_call_trace(str(tmp_path))
+    assert list(got) == list(golden)
+    for name, want in golden.items():
+        first = next((i for i, (a, b) in enumerate(zip(got[name], want)) if a != b), min(len(got[name]), len(want)))
+        assert got[name] == want, "%s: %d lines against %d recorded, first difference at line %d:\n  now      %s\n  recorded %s" % (
+            name, len(got[name]), len(want), first + 1, got[name][first:first + 1], want[first:first + 1])
+
+
 @pytest.mark.parametrize("flavour", ["plain", "asan", "tsan"])
 def test_device_threads_over_fake_backend(sanitized, flavour):
     """tests/host/device_probe.cpp: SoapySXHip.cpp + sx_device_capi.cpp as they ship, driven through include/sx_device.h
