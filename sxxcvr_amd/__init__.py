@@ -9,6 +9,6 @@ libraries and mirrors the reference's Python-facing call pattern; there is no
 CPU implementation and nothing here imports the oracle.
 """
 from ._native import NativeError, load_sxfir  # noqa: F401
-from .resampler import Channelizer, PipelinedResampler, Resampler, Synthesizer, design_bandpass, design_lowpass, pin_array, synth_fill, unpin_array  # noqa: F401
+from .resampler import Channelizer, ComplexInterpolator, PipelinedResampler, Resampler, Synthesizer, design_bandpass, design_lowpass, pin_array, synth_fill, unpin_array  # noqa: F401
 
-__all__ = ["NativeError", "load_sxfir", "Resampler", "Channelizer", "Synthesizer", "PipelinedResampler", "design_lowpass", "design_bandpass", "synth_fill", "pin_array", "unpin_array"]
+__all__ = ["NativeError", "load_sxfir", "Resampler", "ComplexInterpolator", "Channelizer", "Synthesizer", "PipelinedResampler", "design_lowpass", "design_bandpass", "synth_fill", "pin_array", "unpin_array"]

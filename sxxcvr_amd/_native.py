@@ -124,6 +124,9 @@ def load_sxfir(profiling=False):
         "sxfir_create_complex": (ci, [P(vp), ci, vp, ci, ci, ci, ci, ci]),
         "sxfir_taps_are_complex": (ci, [vp, P(ci)]),
         "sxfir_design_bandpass": (ci, [ci, ci, dbl, dbl, ci, ci, vp]),
+        # include/sxfir_complex_tx.h: complex-tap (band-pass) interpolators
+        "sxfir_complex_tx_abi_version": (ci, []),
+        "sxfir_create_complex_interpolator": (ci, [P(vp), vp, ci, ci, ci, ci, ci]),
         # include/sxfir_channelizer.h: the 4-band channelizer
         "sxfir_channelizer_abi_version": (ci, []),
         "sxfir_create_channelizer": (ci, [P(vp), vp, ci, ci, ci, ci, ci]),

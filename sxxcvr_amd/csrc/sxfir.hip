@@ -2,6 +2,7 @@
 // "thin extern C shim": plan bookkeeping, kernel selection and launches.
 #include "../../include/sxfir.h"
 #include "../../include/sxfir_complex.h"
+#include "../../include/sxfir_complex_tx.h"
 #include "../../include/sxfir_channelizer.h"
 #include "../../include/sxfir_channelizer_os.h"
 #include "../../include/sxfir_synthesizer.h"
@@ -80,6 +81,7 @@
 #include "sxfir_synthesis4.hip.h"               // the 4-band synthesizer (include/sxfir_synthesizer.h)
 #include "sxfir_chan4x2.hip.h"                  // the 2x oversampled 4-band channelizer (include/sxfir_channelizer_os.h)
 #include "sxfir_synthesis4x2.hip.h"             // the 2x oversampled 4-band synthesizer (include/sxfir_synthesizer_os.h)
+#include "sxfir_interp_cx.hip.h"                // x4 x 128, x8 x 256 complex taps (include/sxfir_complex_tx.h)
 
 namespace {
 
@@ -114,6 +116,7 @@ inline size_t sample_bytes(int fmt) { return fmt == SXFIR_CF16 ? 4 : 8; }   // C
 #include "sxfir_runtime.hip.h"   // synthetic source, converters, time arithmetic, tap design, memory / stream / event helpers
 #include "sxfir_comm.hip.h"      // sxfir_comm_*: the RCCL gather
 #include "sxfir_complex.hip.h"   // sxfir_create_complex, sxfir_design_bandpass (include/sxfir_complex.h)
+#include "sxfir_complex_tx.hip.h"   // sxfir_create_complex_interpolator (include/sxfir_complex_tx.h)
 #include "sxfir_channelizer.hip.h"   // sxfir_create_channelizer, sxfir_channelize (include/sxfir_channelizer.h)
 #include "sxfir_synthesizer.hip.h"   // sxfir_create_synthesizer, sxfir_synthesize (include/sxfir_synthesizer.h)
 #include "sxfir_channelizer_os.hip.h"   // sxfir_create_channelizer_os, sxfir_plan_oversampling (include/sxfir_channelizer_os.h)

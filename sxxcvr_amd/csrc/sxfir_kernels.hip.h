@@ -230,6 +230,47 @@ __global__ __launch_bounds__(256) void interp_generic_kernel(const GenericArgs a
     FO::store(out, n, make_float2(pi[0], pq[0]), a.thr2);
 }
 
+// One output of the real-tap interpolator under the contract: phase r of input index q on `taps` (ntaps floats).  jsplit <= 2 for
+// every interpolator (real_tap_contract), so the adjacent-pair tree is P0 + P1: named registers, no per-thread array.
+template <typename F>
+__device__ __forceinline__ float2 interp_generic_output(const GenericArgs &a, const float *taps, const void *in, const void *hist,
+                                                        long long q, int r)
+{
+    const int L = a.ratio;
+    const int jl = a.ntaps / L / a.jsplit;
+    float2 y = make_float2(0.0f, 0.0f);
+    for (int p = 0; p < a.jsplit; ++p) {
+        float si = 0.0f, sq = 0.0f;
+        for (int j = (p + 1) * jl - 1; j >= p * jl; --j) {
+            const float2 x = sample_at<F>(a, in, hist, q - j);
+            const float t = taps[j * L + r];
+            si = __builtin_fmaf(t, x.x, si);
+            sq = __builtin_fmaf(t, x.y, sq);
+        }
+        y = p == 0 ? make_float2(si, sq) : make_float2(__fadd_rn(y.x, si), __fadd_rn(y.y, sq));
+    }
+    return y;
+}
+
+// Complex taps h = a + j b (a.taps: a[0, ntaps) then b[0, ntaps)), one output per thread: A = a (*) x and B = b (*) x are two
+// real-tap interpolator outputs under the contract above, then y.re = A.re - B.im, y.im = A.im + B.re, one rounding each
+// (DESIGN.md 3); FO::store rounds to half once for CF16 and makes the wire words of the combined value for S32.
+template <typename F, typename FO = F>
+__global__ __launch_bounds__(256) void interp_cx_generic_kernel(const GenericArgs a)
+{
+    const long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= a.n_out) return;
+    const int ch = blockIdx.y;
+    const char *in = (const char *)a.in + sizeof(typename F::storage) * a.in_stride * ch;
+    const char *hist = (const char *)a.hist + sizeof(typename F::storage) * a.hist_stride * ch;
+    char *out = (char *)a.out + sizeof(typename FO::storage) * a.out_stride * ch;
+    const long long q = n / a.ratio;
+    const int r = (int)(n - q * a.ratio);
+    const float2 A = interp_generic_output<F>(a, a.taps, in, hist, q, r);
+    const float2 B = interp_generic_output<F>(a, a.taps + a.ntaps, in, hist, q, r);
+    FO::store(out, n, make_float2(__fsub_rn(A.x, B.y), __fadd_rn(A.y, B.x)), a.thr2);
+}
+
 // History carry-over for the generic path: hist_out <- last hist_len samples of (hist ++ in[0, n_in)).
 // Out of place (the plan keeps two history buffers and swaps them, as the tiled kernels do), so it is
 // one element per thread over a grid of any size: no limit on hist_len.

@@ -364,7 +364,7 @@ static sxfir::InterpTileArgs interp_tile_args(const sxfir_plan *p, const CallIO 
     t.hist = (const float *)p->hist_dev;
     t.hist_out = (float *)p->hist_alt;
     t.out = (float *)c.out;
-    t.taps = geom.kind == GEOM_IPASS ? p->taps_scaled_dev : p->taps_dev;      // the pass-major table
+    t.taps = geom.kind == GEOM_IPASS || geom.kind == GEOM_ICX ? p->taps_scaled_dev : p->taps_dev;      // the pass-major table(s)
     t.n_in = (long long)c.n_in;
     t.in_stride = (long long)c.in_stride;
     t.out_stride = (long long)c.out_stride;
@@ -453,6 +453,14 @@ static int launch_interp(sxfir_plan *p, const CallIO &c, bool *history_done, con
     if (geom.kind == GEOM_IPASS)
         if (int rc = need_tap_table(p, TAPS_PASS8, "interp8_pass_kernel")) return rc;
     if (geom.n_tiles * geom.split > 0x7fffffffLL) return fail(SXFIR_EINVAL, "call too large");
+    if (geom.kind == GEOM_ICX) {
+        // complex taps: no keyed instance -- the count depends on the input alone and runs as the generic path's pass of its own
+        if (int rc = need_tap_table(p, TAPS_PASS8_CX, "interp_cx_pass_kernel")) return rc;
+        if (int rc = launch(p->k.interp_cx, grid, (unsigned)p->form->threads, c.st, interp_tile_args(p, c, geom, nullptr))) return rc;
+        *history_done = true;
+        if (key && key->hi > key->lo && key_pending) *key_pending = true;
+        return SXFIR_OK;
+    }
     if (p->fmt == SXFIR_CF16 && key) return fail(SXFIR_EUNSUPPORTED, "the keying count is defined on CF32 input");
     const sxfir::InterpTileArgs t = interp_tile_args(p, c, geom, key);
     *history_done = true;

@@ -22,12 +22,13 @@ enum PlanKind { KIND_REAL = 0, KIND_COMPLEX = 1, KIND_CHANNELIZER = 2, KIND_SYNT
 // TAPS_PASS8: the pass-major table of interp8_pass_kernel (pass (c, p) at 64 (2c + p), (jj, rr) at 4 jj + rr);
 // TAPS_BLOCKS16: the block-major table of decim_blocks_kernel, of the ROTATED taps (times 2^-31 for S32 plans);
 // TAPS_PHASED: the phase-major table of synthesis4_kernel and synthesis4x2_kernel (h[ratio j + r] at (ntaps / ratio) r + j: four
-// phases, or the two output parities of the oversampled plan); TAPS_NONE: the plan's kernels read taps_dev alone.
+// phases, or the two output parities of the oversampled plan); TAPS_NONE: the plan's kernels read taps_dev alone;
+// TAPS_PASS8_CX: interp_cx_pass_kernel's, 2 x ntaps floats -- the TAPS_PASS8 table of a, then that of b.
 // Every launch that hands taps_scaled_dev to a kernel checks the plan's layout first (need_tap_table).
-enum TapTable { TAPS_SCALED = 0, TAPS_SUBSET8 = 1, TAPS_PASS8 = 2, TAPS_BLOCKS16 = 3, TAPS_PHASED = 4, TAPS_NONE = 5 };
+enum TapTable { TAPS_SCALED = 0, TAPS_SUBSET8 = 1, TAPS_PASS8 = 2, TAPS_BLOCKS16 = 3, TAPS_PHASED = 4, TAPS_NONE = 5, TAPS_PASS8_CX = 6 };
 
 // Which kernel family a call launches (LaunchGeom::kind, sxfir_launch.hip.h)
-enum { GEOM_GENERIC = 0, GEOM_MULTI = 1, GEOM_WIDE = 2, GEOM_TILE = 3, GEOM_IPASS = 4, GEOM_ITILE = 5, GEOM_CX = 6, GEOM_CHAN4 = 7, GEOM_SYN4 = 8, GEOM_CHAN4X2 = 9, GEOM_SYN4X2 = 10 };
+enum { GEOM_GENERIC = 0, GEOM_MULTI = 1, GEOM_WIDE = 2, GEOM_TILE = 3, GEOM_IPASS = 4, GEOM_ITILE = 5, GEOM_CX = 6, GEOM_CHAN4 = 7, GEOM_SYN4 = 8, GEOM_CHAN4X2 = 9, GEOM_SYN4X2 = 10, GEOM_ICX = 11 };
 
 // One typed kernel pointer per launch-argument family, and a plan's kernels: resolved once by the plan's creator
 // (resolve_kernels below), read by the occupancy query there and by the launches (sxfir_launch.hip.h).
@@ -45,11 +46,12 @@ typedef void (*SynOsTileFn)(sxfir::SynOsTileArgs);
 typedef void (*SynOsGenericFn)(sxfir::SynOsGenericArgs);
 struct KernelTable {
     const char *generic_name;    // the plan's generic kernel, as sxfir_launch_geometry reports it: every plan has exactly one of the five
-    GenericFn generic;           // decim_generic_kernel / decim_cx_generic_kernel / interp_generic_kernel: real and complex taps
+    GenericFn generic;           // decim_generic_kernel / decim_cx_generic_kernel / interp_generic_kernel / interp_cx_generic_kernel: real and complex taps
     DecimMultiFn dense;          // decim_dense_kernel (/8, /16, /32)
     DecimBlocksFn blocks[2];     // decim_blocks_kernel (/48, /96): [0] the walking form, [1] SPLIT, (tile, block) items
     DecimTileFn tile, wide, cx;  // /4: decim4_tile_kernel, decim4_wide_kernel, decim4_cx_kernel (complex taps)
     InterpTileFn interp[2][2];   // [keyed][split]: interp8_pass_kernel; interp_tile_kernel on CF16 storage ([0][0] alone)
+    InterpTileFn interp_cx;      // complex-tap interpolators (include/sxfir_complex_tx.h): interp_cx_pass_kernel (x4 x 128, x8 x 256, CF32)
     ChanTileFn chan4;            // channelizer plans (include/sxfir_channelizer.h): chan4_kernel (4 bands x 128 taps, CF32) ...
     ChanGenericFn chan_generic;  // ... and chan_generic_kernel, which every channelizer plan has INSTEAD of `generic`
     ChanTileFn chan4x2;          // 2x oversampled channelizer plans (include/sxfir_channelizer_os.h): chan4x2_kernel (4 bands x 128 taps, CF32) ...
@@ -128,10 +130,15 @@ struct sxfir_plan {
 static GenericFn generic_kernel(int mode, int fmt, bool cx)
 {
     using namespace sxfir;
-    if (cx) {
+    if (cx && mode == SXFIR_DECIMATE) {
         if (fmt == SXFIR_CF32) return decim_cx_generic_kernel<CF32>;
         if (fmt == SXFIR_CF16) return decim_cx_generic_kernel<CF16>;
         return decim_cx_generic_kernel<S32, CF32>;
+    }
+    if (cx) {
+        if (fmt == SXFIR_CF32) return interp_cx_generic_kernel<CF32>;
+        if (fmt == SXFIR_CF16) return interp_cx_generic_kernel<CF16>;
+        return interp_cx_generic_kernel<CF32, S32>;
     }
     if (mode == SXFIR_DECIMATE) {
         if (fmt == SXFIR_CF32) return decim_generic_kernel<CF32>;
@@ -242,6 +249,15 @@ static InterpTileFn interp_kernel(int ratio, int fmt, bool keyed, bool split)
     return nullptr;
 }
 
+// Complex-tap interpolators, 32 taps per phase on CF32: interp_cx_pass_kernel<QI, LL> on the pass kernel's frame -- x4 with four
+// inputs per lane, x8 with two (sxfir_interp_cx.hip.h)
+static InterpTileFn interp_cx_kernel(int ratio)
+{
+    if (ratio == 4) return sxfir::interp_cx_pass_kernel<4, 4>;
+    if (ratio == 8) return sxfir::interp_cx_pass_kernel<2, 8>;
+    return nullptr;
+}
+
 // 2x oversampled channelizer plans: four chains and the butterflies of the output's parity per thread
 static ChanOsGenericFn chan4x2_generic_kernel_for(int fmt)
 {
@@ -310,6 +326,9 @@ static const PlanForm FORM_ITILE = {"interp_tile_kernel", GEOM_ITILE, TILE_ITILE
 static const PlanForm FORM_ITILE_BLOCKS = {"interp_tile_kernel", GEOM_ITILE, TILE_ITILE, 64, 1, 2, false, 2, 16, TAPS_SCALED};
 // decim4_cx_kernel: complex taps, /4 x 128 on CF32, on the wide kernel's frame
 static const PlanForm FORM_CX = {"decim4_cx_kernel", GEOM_CX, 512, 64, 1, 2, true, 16, 8, TAPS_NONE};
+// interp_cx_pass_kernel: complex taps, x4 x 128 and x8 x 256 on CF32, on the pass kernel's frame and with its tiles and generations;
+// a small call keeps four tiles per workgroup as the other complex-tap and band kernels' do (a tile is twice the pass kernel's work)
+static const PlanForm FORM_ICX = {"interp_cx_pass_kernel", GEOM_ICX, TILE_IPASS, 64, 1, 2, true, 8, 8, TAPS_PASS8_CX};
 
 // The ratio whose kernel a tile of interp_tile_kernel runs: x48 is three phase blocks of the x16 kernel, x96 three of the x32 kernel
 static int itile_base(int ratio) { return ratio > 32 ? ratio / 3 : ratio; }
@@ -385,10 +404,13 @@ static void resolve_kernels(sxfir_plan *p)
         if (geom == GEOM_SYN4X2) k.syn4x2 = sxfir::synthesis4x2_kernel;
         return;
     }
-    k.generic_name = p->kind == KIND_COMPLEX ? "decim_cx_generic_kernel" : p->mode == SXFIR_DECIMATE ? "decim_generic_kernel" : "interp_generic_kernel";
-    k.generic = generic_kernel(p->mode, p->fmt, p->kind == KIND_COMPLEX);
+    const bool cx = p->kind == KIND_COMPLEX;
+    if (p->mode == SXFIR_DECIMATE) k.generic_name = cx ? "decim_cx_generic_kernel" : "decim_generic_kernel";
+    else k.generic_name = cx ? "interp_cx_generic_kernel" : "interp_generic_kernel";
+    k.generic = generic_kernel(p->mode, p->fmt, cx);
     switch (geom) {
     case GEOM_CX: k.cx = sxfir::decim4_cx_kernel; break;
+    case GEOM_ICX: k.interp_cx = interp_cx_kernel(p->ratio); break;
     case GEOM_MULTI:
         if (!p->blocks) k.dense = dense_kernel(p->ratio, p->fmt);
         for (int split = 0; split < 2; ++split) k.blocks[split] = blocks_kernel(p->blocks, p->fmt, split != 0);
@@ -414,6 +436,7 @@ static const void *occupancy_instance(const sxfir_plan *p)
     case GEOM_TILE: return (const void *)tile_kernel(p->ntaps, SXFIR_CF32);
     case GEOM_IPASS: return (const void *)interp_kernel(p->ratio < 16 ? p->ratio : 16, SXFIR_CF32, false, false);
     case GEOM_CX: return (const void *)k.cx;
+    case GEOM_ICX: return (const void *)k.interp_cx;
     case GEOM_CHAN4: return (const void *)k.chan4;
     case GEOM_CHAN4X2: return (const void *)k.chan4x2;
     case GEOM_SYN4: return (const void *)k.syn4;
@@ -597,11 +620,22 @@ static void taps_phased(std::vector<float> &t, const float *taps, int ratio)
         for (int j = 0; j < jt; ++j) t[(size_t)(jt * r + j)] = taps[ratio * j + r];
 }
 
-// p->ntaps floats in the layout p->tap_table names
+// interp_cx_pass_kernel: the planar taps a[0, ntaps) then b[0, ntaps), each as taps_pass8 lays it out, a's table then b's
+static void taps_pass8_cx(std::vector<float> &t, const float *planar, int ntaps, int ratio)
+{
+    std::vector<float> half((size_t)ntaps);
+    for (int part = 0; part < 2; ++part) {
+        taps_pass8(half, planar + (size_t)part * ntaps, ratio);
+        std::copy(half.begin(), half.end(), t.begin() + (size_t)part * ntaps);
+    }
+}
+
+// p->ntaps floats in the layout p->tap_table names (TAPS_PASS8_CX: twice as many, from the planar complex taps)
 static std::vector<float> second_tap_table(const sxfir_plan *p, const float *taps)
 {
-    std::vector<float> t(taps, taps + p->ntaps);
+    std::vector<float> t(taps, taps + (p->tap_table == TAPS_PASS8_CX ? 2 : 1) * (size_t)p->ntaps);
     switch (p->tap_table) {
+    case TAPS_PASS8_CX: taps_pass8_cx(t, taps, p->ntaps, p->ratio); break;
     case TAPS_SCALED: taps_scaled(t, taps); break;
     case TAPS_SUBSET8: taps_subset8(t, taps, p->fmt); break;
     case TAPS_BLOCKS16: taps_blocks16(t, taps, p->ratio, p->rot, p->fmt); break;
@@ -622,7 +656,10 @@ static int plan_to_device(sxfir_plan **out, sxfir_plan *p, const float *taps, si
 {
     const size_t hist_bytes = sample_bytes(p->fmt) * (size_t)p->hist_len * (size_t)p->nchan;
     hipError_t e = upload(&p->taps_dev, taps, n_taps);
-    if (e == hipSuccess && p->tap_table != TAPS_NONE) e = upload(&p->taps_scaled_dev, second_tap_table(p, taps).data(), (size_t)p->ntaps);
+    if (e == hipSuccess && p->tap_table != TAPS_NONE) {
+        const std::vector<float> second = second_tap_table(p, taps);
+        e = upload(&p->taps_scaled_dev, second.data(), second.size());
+    }
     if (e == hipSuccess) e = hipMalloc(&p->hist_dev, hist_bytes);
     if (e == hipSuccess) e = hipMalloc(&p->hist_alt, hist_bytes);
     if (e == hipSuccess) e = hipMemset(p->hist_dev, 0, hist_bytes);

@@ -1,4 +1,4 @@
-"""Python face of the C ABI in include/sxfir.h, include/sxfir_complex.h, include/sxfir_channelizer.h and include/sxfir_synthesizer.h.
+"""Python face of the C ABI in include/sxfir.h, include/sxfir_complex.h, include/sxfir_complex_tx.h, include/sxfir_channelizer.h and include/sxfir_synthesizer.h.
 
 Device memory comes either from torch (complex64 / int32 CUDA tensors, the
 current torch stream is used) or from the library's own sxfir_malloc for
@@ -54,7 +54,11 @@ def design_lowpass(ntaps, ratio, beta=8.0, gain=1.0):
 def design_bandpass(ntaps, ratio, num, den, beta=8.0, gain=1.0):
     """Complex band-pass taps (complex64): the design_lowpass prototype turned to the band centre num/den cycles per INPUT
     sample (sxfir_design_bandpass); k/ratio is sub-band k of the output raster.  Resampler(DECIMATE, these taps, ratio) takes
-    that band out in one pass and leaves its centre at 0 Hz of the output."""
+    that band out in one pass and leaves its centre at 0 Hz of the output.
+
+    The TX reading: for ComplexInterpolator(these taps, ratio) the phasors are on the OUTPUT side -- num/den is the band centre in
+    cycles per OUTPUT sample, and gain=ratio keeps the stream's level through the zero stuffing: design_bandpass(ntaps, ratio, k,
+    ratio, gain=ratio) places the input at sub-band k of the x ratio raster."""
     lib = load_sxfir()
     taps = np.empty(ntaps, dtype=np.complex64)
     check(lib.sxfir_design_bandpass(ntaps, ratio, beta, gain, int(num), int(den), taps.ctypes.data_as(C.c_void_p)))
@@ -347,6 +351,22 @@ class Resampler(_Plan):
             lib.sxfir_free(din)
             lib.sxfir_free(dout)
         return y[0] if squeeze else y
+
+
+class ComplexInterpolator(Resampler):
+    """A complex-tap (band-pass) interpolator (include/sxfir_complex_tx.h): one narrowband stream onto a band of the x ratio raster
+    in one pass -- the way back from Resampler(DECIMATE, complex taps, ratio).  `taps`: complex, ntaps a multiple of ratio;
+    design_bandpass(ntaps, ratio, k, ratio, gain=ratio) places the input at sub-band k, k / ratio cycles per output sample.  The plan
+    is an interpolator plan (mode INTERPOLATE) in everything else: the same methods as Resampler."""
+
+    def __init__(self, taps, ratio, nchan=1, fmt="CF32", device=-1, profiling=False):
+        self._lib = load_sxfir(profiling)
+        self.profiling = bool(profiling)
+        self._plan = C.c_void_p()
+        taps = np.ascontiguousarray(taps, dtype=np.complex64)
+        self.mode, self.ratio, self.nchan, self.fmt, self.ntaps = INTERPOLATE, int(ratio), int(nchan), _FMT[fmt], taps.size
+        self._ck(self._lib.sxfir_create_complex_interpolator(C.byref(self._plan), taps.ctypes.data_as(C.c_void_p), taps.size,
+                                                             int(ratio), int(nchan), self.fmt, int(device)))
 
 
 class _BandPlan(_Plan):

@@ -3,7 +3,7 @@
     python3 tools/shipped_isa.py [substring of the kernel name] [--json]
 
 (`chan4` lists the channelizer kernels of DESIGN.md 5.6, `chan4x2` the oversampled channelizer's of 5.8, `synthesis` the synthesizer's,
-`synthesis4x2` the oversampled synthesizer's of 5.9.)
+`synthesis4x2` the oversampled synthesizer's of 5.9, `interp_cx` the complex-tap interpolators' of 5.10.)
 
 Registers / LDS / scratch come from the code object's metadata notes, instruction counts from its disassembly:
 v_pk_fma_f32, ds_read_b128, global_load_lds_dwordx4 (and how many of those carry `nt`), s_barrier, v_mfma, DPP and
@@ -85,6 +85,10 @@ def kernels(lib=None):
                     r["counted_wait"] = cw
             else:
                 r["phase_block_wait"] = phase_block_wait(body)
+        if "interp_cx_pass_kernel" in r["name"]:                     # the pass kernel's frame: the same wait at the loop head
+            cw = counted_wait(body)
+            if cw:
+                r["counted_wait"] = cw
         rows.append(r)
     return rows
 
