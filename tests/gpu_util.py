@@ -74,7 +74,8 @@ def band_proto(gain=1.0):
     return sxxcvr_amd.design_lowpass(128, 4, 8.0, gain)
 
 
-# ---- the band plans' references (tests/test_gpu_channelizer.py, test_gpu_synthesizer.py, test_gpu_call_frame.py) -------------
+# ---- the band plans' references (tests/test_gpu_channelizer.py, test_gpu_synthesizer.py and their _os files, test_gpu_call_frame.py,
+# tests/band_cases.py) ---------------------------------------------------------------------------------------------------------
 def chan_ref(oracle, h, x, threads=None):
     """[4, n_out] complex64: the four bands of one channelizer pass over x from zero history."""
     h = np.ascontiguousarray(h, dtype=np.float32)
@@ -127,6 +128,81 @@ def syn_ref(oracle, h, x, jsplit, threads=None):
         y = oracle.interp_f32(h, 4, v[r], jsplit) if threads is None else oracle.interp_f32_mt(h, 4, v[r], jsplit, threads=threads)
         w[r::4] = y[r::4]
     return w
+
+
+def chan_os_ref(oracle, h, x, threads=None):
+    """[4, ceil(n / 2)] complex64: the four bands of one 2x oversampled channelizer pass over x from zero history (the butterflies
+    on (u0, u1, u2, u3) in the even columns and on (u2, u3, u0, u1) in the odd ones)."""
+    h = np.ascontiguousarray(h, dtype=np.float32)
+    u = []
+    for r in range(4):
+        hr = np.zeros_like(h)                               # +0.0
+        hr[r::4] = h[r::4]
+        u.append(oracle.decim_f32(hr, 2, x, 1, 1, threads=threads))
+    odd = (np.arange(u[0].size) & 1) == 1
+    a = [np.where(odd, u[(r + 2) % 4], u[r]) for r in range(4)]          # odd times: the branch sums shifted by two
+    re = [np.ascontiguousarray(v.real) for v in a]
+    im = [np.ascontiguousarray(v.imag) for v in a]
+    s0re, s0im, s1re, s1im = re[0] + re[2], im[0] + im[2], re[0] - re[2], im[0] - im[2]
+    t0re, t0im, t1re, t1im = re[1] + re[3], im[1] + im[3], re[1] - re[3], im[1] - im[3]
+    assert s0re.dtype == np.float32 and t1im.dtype == np.float32
+    y = np.empty((4, u[0].size), dtype=np.complex64)
+    y[0].real, y[0].imag = s0re + t0re, s0im + t0im
+    y[1].real, y[1].imag = s1re - t1im, s1im + t1re
+    y[2].real, y[2].imag = s0re - t0re, s0im - t0im
+    y[3].real, y[3].imag = s1re + t1im, s1im - t1re
+    return y
+
+
+def syn_os_ref(oracle, h, x, jsplit, m0=0, threads=None):
+    """[2 n] complex64: one 2x oversampled synthesizer pass over the four bands x [4, n] from zero history, the first input at the
+    absolute per-band index m0."""
+    h = np.ascontiguousarray(h, dtype=np.float32)
+    x = np.ascontiguousarray(x, dtype=np.complex64)
+    v = butterflies_f32(x)
+    n = np.arange(2 * x.shape[1])
+    w = np.empty(n.size, dtype=np.complex64)
+    for r in range(4):
+        y = oracle.interp_f32(h, 2, v[r], jsplit) if threads is None else oracle.interp_f32_mt(h, 2, v[r], jsplit, threads=threads)
+        pick = ((n + 2 * m0) & 3) == r
+        w[pick] = y[pick]
+    return w
+
+
+# ---- the complex-tap plans' taps and references (tests/test_gpu_complex_taps.py, test_gpu_complex_interp.py) --------------------
+def random_taps_cx(n, seed=5):
+    """Complex taps with no structure to lean on."""
+    rng = np.random.default_rng(seed)
+    return ((rng.standard_normal(n) + 1j * rng.standard_normal(n)) / 64.0).astype(np.complex64)
+
+
+def _cx_combine(A, B):
+    ref = np.empty(A.shape, dtype=np.complex64)
+    ref.real = A.real - B.imag                          # float32, one rounding each
+    ref.imag = A.imag + B.real
+    return ref
+
+
+def cx_decim_ref(oracle, h, D, x, contract, threads=None):
+    """A complex-tap decimator pass: two real-tap oracle passes (Re h, Im h) under `contract` (with its .rot), combined in float32."""
+    rot = contract.rot                                  # (read first: the pair alone does not state a rotated contract)
+    js, cw = contract
+    a = np.ascontiguousarray(h.real, dtype=np.float32)
+    b = np.ascontiguousarray(h.imag, dtype=np.float32)
+    A = oracle.decim_f32(a, D, x, js, cw, rot=rot, threads=threads)
+    B = oracle.decim_f32(b, D, x, js, cw, rot=rot, threads=threads)
+    return _cx_combine(A, B)
+
+
+def cx_interp_ref(oracle, h, L, x, jsplit, threads=None):
+    """A complex-tap interpolator pass: two real-tap oracle passes (Re h, Im h) under jsplit, combined in float32."""
+    a = np.ascontiguousarray(h.real, dtype=np.float32)
+    b = np.ascontiguousarray(h.imag, dtype=np.float32)
+    if threads is None:
+        A, B = oracle.interp_f32(a, L, x, jsplit), oracle.interp_f32(b, L, x, jsplit)
+    else:
+        A, B = oracle.interp_f32_mt(a, L, x, jsplit, threads=threads), oracle.interp_f32_mt(b, L, x, jsplit, threads=threads)
+    return _cx_combine(A, B)
 
 
 # ---- the (tile, block) join of the decimators by 48 and 96 (decim_blocks_kernel<..., SPLIT>) --------------------------------

@@ -1,14 +1,18 @@
-"""The streaming call of every plan kind, through each of the six ways into it (sxfir_launch.hip.h: stream_call): a stream
+"""The streaming call of every plan kind, through each of the nine ways into it (sxfir_launch.hip.h: stream_call): a stream
 cut anywhere gives the oracle's bits and the arithmetic positions, a refused call leaves the plan and the output alone, and
 destroying a plan gives its device memory back.
 
-The six ways: sxfir_decimate on real taps (/4 x 128) and on complex taps (/4 x 128), sxfir_channelize (4 x 128),
-sxfir_interpolate (x4 x 128), sxfir_interpolate_keyed (x8 x 256) and sxfir_synthesize (4 x 128); CF32, one channel.
+The nine ways: sxfir_decimate on real taps (/4 x 128) and on complex taps (/4 x 128), sxfir_channelize (4 x 128, critically
+sampled and 2x oversampled), sxfir_interpolate on real and on complex taps (x4 x 128), sxfir_interpolate_keyed (x8 x 256) and
+sxfir_synthesize (4 x 128, critically sampled and 2x oversampled); CF32, one channel.
 
 Cut anywhere: the calls are [0, 1, 2, 1, T, 3, T + 4, rest] with T the tiled kernel's input tile (2048 for the decimator kinds;
-256 for x4 and the synthesizer, 128 for x8).  The decimator kinds' stream is 2 * 2048 + 11 samples, which the seven calls use up
-(the rest is a second call of nothing, off an output boundary).  The interpolator kinds' stream is 3 * 256 + 3 inputs per band:
-the seven calls take 2 T + 11 inputs, more than two tiles and three, and the rest is a ragged call of its own."""
+256 for x4 and the synthesizer, 512 for the oversampled synthesizer, 128 for x8).  The decimator kinds' stream is 2 * 2048 + 11
+samples, which the seven calls use up (the rest is a second call of nothing, off an output boundary).  The interpolator kinds'
+stream is 3 T + 3 inputs per band (3 * 256 + 3 at x8): the seven calls take 2 T + 11 inputs, more than two tiles and three, and
+the rest is a ragged call of its own.  The oversampled channelizer, whose tiled kernel takes a stream position that is a multiple
+of 4, has calls of its own, [0, 1, 2, 1, T, 2, T + 4, 3, rest] on 2 * 2048 + 15 samples: the calls of T + 4 and of 3 start ON an
+output boundary at a position = 2 mod 4 -- an odd output index -- and run the generic kernel for that alone."""
 import ctypes as C
 
 import numpy as np
@@ -17,14 +21,14 @@ import pytest
 import sxxcvr_amd
 from sxxcvr_amd import design_bandpass, design_lowpass
 from sxxcvr_amd.resampler import DECIMATE, INTERPOLATE
-from gpu_util import assert_bands, assert_bit_exact, chan_ref, syn_ref, to_cpu
-from test_gpu_complex_taps import cx_ref
+from gpu_util import assert_bands, assert_bit_exact, chan_os_ref, chan_ref, cx_decim_ref, cx_interp_ref, syn_os_ref, syn_ref, to_cpu
 
 pytestmark = pytest.mark.gpu
 
 SEED = 0xF4A3E
 THR2 = np.float32(0.49)
-WAYS = ["decimate", "decimate_cx", "channelize", "interpolate", "interpolate_keyed", "synthesize"]
+WAYS = ["decimate", "decimate_cx", "channelize", "interpolate", "interpolate_keyed", "synthesize", "channelize_os", "synthesize_os",
+        "interpolate_cx"]
 ENTRIES = ["sxfir_decimate", "sxfir_interpolate", "sxfir_interpolate_keyed", "sxfir_channelize", "sxfir_synthesize",
            "sxfir_time_decimate", "sxfir_time_interpolate"]
 EINVAL, EUNSUPPORTED = -1, -4
@@ -35,16 +39,25 @@ class Way:
 
     def __init__(self, name):
         self.name = name
-        self.decim = name in ("decimate", "decimate_cx", "channelize")
-        self.banded_in = name == "synthesize"               # input [4, n]
-        self.banded_out = name == "channelize"              # output [4, n_out]
-        self.ratio = 8 if name == "interpolate_keyed" else 4
-        self.tile = 2048 if self.decim else (128 if self.ratio == 8 else 256)
-        self.stream = 2 * 2048 + 11 if self.decim else 3 * 256 + 3
+        self.decim = name in ("decimate", "decimate_cx", "channelize", "channelize_os")
+        self.banded_in = name in ("synthesize", "synthesize_os")            # input [4, n]
+        self.banded_out = name in ("channelize", "channelize_os")           # output [4, n_out]
+        self.oversampled = name.endswith("_os")
+        self.ratio = 8 if name == "interpolate_keyed" else 2 if self.oversampled else 4
+        self.tile = 2048 if self.decim else 512 if name == "synthesize_os" else (128 if self.ratio == 8 else 256)
+        self.stream = 2 * 2048 + 11 if self.decim else 3 * max(self.tile, 256) + 3
+        self.cuts = [0, 1, 2, 1, self.tile, 3, self.tile + 4]
+        if name == "channelize_os":
+            self.stream = 2 * 2048 + 15
+            self.cuts = [0, 1, 2, 1, self.tile, 2, self.tile + 4, 3]
         if name == "decimate_cx":
             self.taps = design_bandpass(128, 4, 1, 4)
+        elif name == "interpolate_cx":
+            self.taps = design_bandpass(128, 4, 1, 4, gain=4.0)
         elif self.decim:
             self.taps = design_lowpass(128, 4)
+        elif name == "synthesize_os":
+            self.taps = design_lowpass(128, 4, 8.0, 2.0)    # a x2 interpolator's low-pass with the /4 band edge
         else:
             self.taps = design_lowpass(32 * self.ratio, self.ratio, 8.0, float(self.ratio))
         self.own = {"decimate": {"sxfir_decimate", "sxfir_time_decimate"},
@@ -52,14 +65,21 @@ class Way:
                     "channelize": {"sxfir_channelize"},
                     "interpolate": {"sxfir_interpolate", "sxfir_interpolate_keyed", "sxfir_time_interpolate"},
                     "interpolate_keyed": {"sxfir_interpolate", "sxfir_interpolate_keyed", "sxfir_time_interpolate"},
-                    "synthesize": {"sxfir_synthesize"}}[name]
-        self.entry = "sxfir_" + name.replace("_cx", "")
+                    "synthesize": {"sxfir_synthesize"},
+                    "channelize_os": {"sxfir_channelize"},
+                    "synthesize_os": {"sxfir_synthesize"},
+                    "interpolate_cx": {"sxfir_interpolate", "sxfir_interpolate_keyed", "sxfir_time_interpolate"}}[name]
+        self.entry = "sxfir_" + name.replace("_cx", "").replace("_os", "")
 
     def plan(self, nchan=1):
-        if self.name == "channelize":
-            return sxxcvr_amd.Channelizer(self.taps, nchan=nchan)
-        if self.name == "synthesize":
-            return sxxcvr_amd.Synthesizer(self.taps, nchan=nchan)
+        if self.banded_out:
+            return sxxcvr_amd.Channelizer(self.taps, nchan=nchan, oversample=2 if self.oversampled else 1)
+        if self.banded_in:
+            return sxxcvr_amd.Synthesizer(self.taps, nchan=nchan, oversample=2 if self.oversampled else 1)
+        if self.name == "interpolate_cx":
+            p = sxxcvr_amd.ComplexInterpolator(self.taps, self.ratio, nchan=nchan)
+            p.set_tx_threshold(float(THR2))
+            return p
         p = sxxcvr_amd.Resampler(DECIMATE if self.decim else INTERPOLATE, self.taps, self.ratio, nchan=nchan)
         if not self.decim:
             p.set_tx_threshold(float(THR2))
@@ -77,17 +97,24 @@ class Way:
     def n_out(self, n_in, consumed=0):
         if not self.decim:
             return n_in * self.ratio
-        return (consumed + n_in + 3) // 4 - (consumed + 3) // 4
+        r = self.ratio
+        return (consumed + n_in + r - 1) // r - (consumed + r - 1) // r
 
     def reference(self, oracle, plan, xs):
         if self.name == "decimate":
             return oracle.decim_f32(self.taps, 4, xs, *plan.contract)
         if self.name == "decimate_cx":
-            return cx_ref(oracle, self.taps, 4, xs, plan.contract)
+            return cx_decim_ref(oracle, self.taps, 4, xs, plan.contract)
+        if self.name == "interpolate_cx":
+            return cx_interp_ref(oracle, self.taps, 4, xs, plan.contract[0])
         if self.name == "channelize":
             return chan_ref(oracle, self.taps, xs)
+        if self.name == "channelize_os":
+            return chan_os_ref(oracle, self.taps, xs)
         if self.name == "synthesize":
             return syn_ref(oracle, self.taps, xs, plan.contract[0])
+        if self.name == "synthesize_os":
+            return syn_os_ref(oracle, self.taps, xs, plan.contract[0])
         return oracle.interp_f32(self.taps, self.ratio, xs, plan.contract[0])
 
     def call(self, lib, entry, plan, x, n, in_stride, band_in, out, out_stride, band_out, n_out, key=None):
@@ -122,7 +149,7 @@ def test_cut_anywhere(oracle, name):
     probe = plan.geometry(4 * 2048)
     assert probe["tiled"] and probe["tile_samples"] == (T if w.decim else T * w.ratio), probe
     x, xs = w.source(oracle, w.stream)
-    calls = [0, 1, 2, 1, T, 3, T + 4]
+    calls = list(w.cuts)
     calls.append(w.stream - sum(calls))
     assert calls[-1] >= 0
     total_out = w.n_out(w.stream)
@@ -134,6 +161,8 @@ def test_cut_anywhere(oracle, name):
         asked = plan.outputs_for(n)
         assert asked == w.n_out(n, pos_in)
         kernels.add(plan.geometry(n)["kernel"] if asked or not w.decim else "history only")
+        if w.decim and asked:       # the tiled kernels' position rule: a multiple of 4, for /4 an output boundary, for the oversampled channelizer one of even index
+            assert plan.geometry(n)["tiled"] == (pos_in % 4 == 0), (n, pos_in)
         # a buffer of its own for every call, the empty ones included: 16-byte aligned, an even band stride (the tiled stores)
         row = max(asked + (asked & 1), 2)
         out = torch.zeros((4, row) if w.banded_out else (row,), dtype=torch.complex64, device="cuda")
@@ -212,7 +241,7 @@ def test_refusals_leave_the_plan_alone(oracle, name):
     for entry in ENTRIES:                                                                    # every entry point that is not this kind's
         if entry not in w.own:
             refused(plan, out, entry, plan._plan, xp, *good)
-    if name == "synthesize":
+    if w.banded_in:
         with pytest.raises(sxxcvr_amd.NativeError) as ei:
             plan.set_history_ptr(xp, n, n)
         assert ei.value.code == EUNSUPPORTED and plan.position == (0, 0)

@@ -13,7 +13,8 @@ import pytest
 import sxxcvr_amd
 from sxxcvr_amd import design_lowpass
 from sxxcvr_amd.resampler import DECIMATE, KERNEL_AUTO, KERNEL_GENERIC, KERNEL_TILED
-from gpu_util import OUT_FILL, assert_bands, assert_bit_exact, band_proto, random_taps, run, to_cpu, to_gpu, wideband_source
+from gpu_util import (OUT_FILL, assert_bands, assert_bit_exact, band_proto, chan_os_ref, random_taps, run, to_cpu, to_gpu,
+                      wideband_source)
 from test_channelizer_os_host import (EDGE_TONE_BAND0_DB, EDGE_TONE_BAND1_DB, EDGE_TONE_BIN0, EDGE_TONE_BIN1, edge_tone,
                                       edge_tone_spectra)
 
@@ -23,29 +24,6 @@ SEED = 0xC4A77E2
 TILE_IN = 2048
 TILED, GENERIC = "chan4x2_kernel", "chan4x2_generic_kernel"
 source = functools.partial(wideband_source, seed=SEED)
-
-
-def chan_os_ref(oracle, h, x, threads=None):
-    """[4, ceil(n / 2)] complex64: the four bands of one oversampled pass over x from zero history."""
-    h = np.ascontiguousarray(h, dtype=np.float32)
-    u = []
-    for r in range(4):
-        hr = np.zeros_like(h)                               # +0.0
-        hr[r::4] = h[r::4]
-        u.append(oracle.decim_f32(hr, 2, x, 1, 1, threads=threads))
-    odd = (np.arange(u[0].size) & 1) == 1
-    a = [np.where(odd, u[(r + 2) % 4], u[r]) for r in range(4)]          # odd times: the branch sums shifted by two
-    re = [np.ascontiguousarray(v.real) for v in a]
-    im = [np.ascontiguousarray(v.imag) for v in a]
-    s0re, s0im, s1re, s1im = re[0] + re[2], im[0] + im[2], re[0] - re[2], im[0] - im[2]
-    t0re, t0im, t1re, t1im = re[1] + re[3], im[1] + im[3], re[1] - re[3], im[1] - im[3]
-    assert s0re.dtype == np.float32 and t1im.dtype == np.float32
-    y = np.empty((4, u[0].size), dtype=np.complex64)
-    y[0].real, y[0].imag = s0re + t0re, s0im + t0im
-    y[1].real, y[1].imag = s1re - t1im, s1im + t1re
-    y[2].real, y[2].imag = s0re - t0re, s0im - t0im
-    y[3].real, y[3].imag = s1re + t1im, s1im - t1re
-    return y
 
 
 def os_plan(h, **kw):

@@ -8,32 +8,13 @@ import pytest
 import sxxcvr_amd
 from sxxcvr_amd import ComplexInterpolator, design_bandpass, design_lowpass
 from sxxcvr_amd.resampler import INTERPOLATE, KERNEL_AUTO, KERNEL_GENERIC, KERNEL_TILED
-from gpu_util import assert_bit_exact, to_cpu, to_gpu
+from gpu_util import assert_bit_exact, cx_interp_ref as cx_ref, random_taps_cx as random_taps, to_cpu, to_gpu
 
 pytestmark = pytest.mark.gpu
 
 SEED = 0x7C0FFEE
 TILE_IN = {4: 256, 8: 128}                  # inputs per tile of interp_cx_pass_kernel
 CX_TILED, CX_GENERIC = "interp_cx_pass_kernel", "interp_cx_generic_kernel"
-
-
-def cx_ref(oracle, h, L, x, jsplit, threads=None):
-    a = np.ascontiguousarray(h.real, dtype=np.float32)
-    b = np.ascontiguousarray(h.imag, dtype=np.float32)
-    if threads is None:
-        A, B = oracle.interp_f32(a, L, x, jsplit), oracle.interp_f32(b, L, x, jsplit)
-    else:
-        A, B = oracle.interp_f32_mt(a, L, x, jsplit, threads=threads), oracle.interp_f32_mt(b, L, x, jsplit, threads=threads)
-    ref = np.empty(A.shape, dtype=np.complex64)
-    ref.real = A.real - B.imag                          # float32, one rounding each
-    ref.imag = A.imag + B.real
-    return ref
-
-
-def random_taps(n, seed=5):
-    """Complex taps with no structure to lean on."""
-    rng = np.random.default_rng(seed)
-    return ((rng.standard_normal(n) + 1j * rng.standard_normal(n)) / 64.0).astype(np.complex64)
 
 
 def band_taps(L, k=1):

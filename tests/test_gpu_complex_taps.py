@@ -8,32 +8,13 @@ import pytest
 import sxxcvr_amd
 from sxxcvr_amd import design_bandpass, design_lowpass
 from sxxcvr_amd.resampler import DECIMATE, INTERPOLATE, KERNEL_GENERIC, KERNEL_TILED
-from gpu_util import assert_bit_exact, to_cpu, to_gpu
+from gpu_util import assert_bit_exact, cx_decim_ref as cx_ref, random_taps_cx as random_taps, to_cpu, to_gpu
 
 pytestmark = pytest.mark.gpu
 
 SEED = 0xC0FFEE
 TILE_IN = 2048
 CX_TILED, CX_GENERIC = "decim4_cx_kernel", "decim_cx_generic_kernel"
-
-
-def cx_ref(oracle, h, D, x, contract, threads=None):
-    rot = contract.rot                                  # (read first: the pair alone does not state a rotated contract)
-    js, cw = contract
-    a = np.ascontiguousarray(h.real, dtype=np.float32)
-    b = np.ascontiguousarray(h.imag, dtype=np.float32)
-    A = oracle.decim_f32(a, D, x, js, cw, rot=rot, threads=threads)
-    B = oracle.decim_f32(b, D, x, js, cw, rot=rot, threads=threads)
-    ref = np.empty(A.shape, dtype=np.complex64)
-    ref.real = A.real - B.imag                          # float32, one rounding each
-    ref.imag = A.imag + B.real
-    return ref
-
-
-def random_taps(n, seed=5):
-    """Complex taps with no structure to lean on."""
-    rng = np.random.default_rng(seed)
-    return ((rng.standard_normal(n) + 1j * rng.standard_normal(n)) / 64.0).astype(np.complex64)
 
 
 def source(oracle, channel, n, start=0):

@@ -13,7 +13,7 @@ import pytest
 import sxxcvr_amd
 from sxxcvr_amd import design_lowpass
 from sxxcvr_amd.resampler import INTERPOLATE, KERNEL_GENERIC, KERNEL_TILED
-from gpu_util import OUT_FILL, assert_bit_exact, band_proto, butterflies_f32, four_band_source, random_taps, run, to_cpu, to_gpu
+from gpu_util import OUT_FILL, assert_bit_exact, band_proto, four_band_source, random_taps, run, syn_os_ref, to_cpu, to_gpu
 from test_channelizer_os_host import edge_tone
 from test_synthesizer_host import band_tone, spectrum_db, tone_and_rest
 from test_synthesizer_os_host import (BAND_TONE_BIN, BAND_TONE_DB, BAND_TONE_DROP, BAND_TONE_KEEP, BAND_TONE_N, CRIT_IMAGE_BIN,
@@ -26,20 +26,6 @@ T = 512                                                     # inputs per band of
 HIST = 64                                                   # a band's history: ntaps / 2
 TILED, GENERIC = "synthesis4x2_kernel", "synthesis_os_generic_kernel"
 source = functools.partial(four_band_source, seed=SEED)
-
-
-def syn_os_ref(oracle, h, x, jsplit, m0=0, threads=None):
-    """[2 n] complex64: one pass over the four bands x [4, n] from zero history, the first input at the absolute per-band index m0."""
-    h = np.ascontiguousarray(h, dtype=np.float32)
-    x = np.ascontiguousarray(x, dtype=np.complex64)
-    v = butterflies_f32(x)
-    n = np.arange(2 * x.shape[1])
-    w = np.empty(n.size, dtype=np.complex64)
-    for r in range(4):
-        y = oracle.interp_f32(h, 2, v[r], jsplit) if threads is None else oracle.interp_f32_mt(h, 2, v[r], jsplit, threads=threads)
-        pick = ((n + 2 * m0) & 3) == r
-        w[pick] = y[pick]
-    return w
 
 
 def os_plan(h, **kw):
