@@ -145,6 +145,12 @@ def load_sxfir(profiling=False):
         "sxfir_synthesizer_os_abi_version": (ci, []),
         "sxfir_create_synthesizer_os": (ci, [P(vp), vp, ci, ci, ci, ci, ci, ci]),
         "sxfir_plan_synthesis_oversampling": (ci, [vp, P(ci)]),
+        # include/sxfir_rational.h: rational up / down resamplers
+        "sxfir_rational_abi_version": (ci, []),
+        "sxfir_create_rational": (ci, [P(vp), vp, ci, ci, ci, ci, ci, ci]),
+        "sxfir_resample": (ci, [vp, vp, sz, sz, vp, sz, P(sz), vp]),
+        "sxfir_time_resample": (ci, [vp, vp, sz, sz, vp, sz, ci, vp, P(C.c_float)]),
+        "sxfir_plan_rational": (ci, [vp, P(ci), P(ci)]),
     }
     if profiling:
         sig["sxfir_debug_clock"] = (ci, [vp, P(dbl)])

@@ -1,7 +1,7 @@
 // Launches of the C ABI: the launch geometry of a call (which kernel family, which grid), one builder per argument struct,
 // launch_decim / launch_interp / launch_synth, and the call frame every streaming entry point ends in: stream_call (launch_call,
 // history carry-over, keyed count, position commit) behind the entry point's own argument checks -- sxfir_decimate,
-// sxfir_interpolate and sxfir_interpolate_keyed here, sxfir_channelize and sxfir_synthesize in their own headers.  WHICH instance a
+// sxfir_interpolate and sxfir_interpolate_keyed here, sxfir_channelize, sxfir_synthesize and sxfir_resample in their own headers.  WHICH instance a
 // plan launches is not decided here: its creator resolved it from the kernel table (sxfir_plan.hip.h) into p->k.  The product path
 // reads straight through; what the profiling build adds sits behind the prof_* hooks of sxfir_prof_dispatch.inc.  Included by
 // sxfir.hip after sxfir_plan.hip.h.
@@ -206,6 +206,19 @@ static LaunchGeom interp_geom(const sxfir_plan *p, long long n_in, bool aligned,
     return g;
 }
 
+// Rational plans: one thread per output of the generic kernel; the form's tiles (inputs, whole periods of `down`) for a call that
+// wants it, is aligned and starts at a position the form takes -- as decim_geom
+static LaunchGeom rational_geom(const sxfir_plan *p, long long n_in, long long n_out, bool aligned)
+{
+    LaunchGeom g = generic_geom(p, n_out, 1);
+    const PlanForm *f = p->form;
+    if (!(f && p->kernel != SXFIR_KERNEL_GENERIC && aligned && p->consumed % f->start_multiple == 0)) return g;
+    set_tiles(g, p, n_in, p->tile);
+    g.tile_samples = p->tile;                           // (the wideband side is the input)
+    set_groups(g, p, 1);
+    return g;
+}
+
 // ---- one builder per argument struct (value-initialised: what a kernel does not read is zero)
 static sxfir::GenericArgs generic_args(const sxfir_plan *p, const CallIO &c, long long first)
 {
@@ -357,6 +370,18 @@ static sxfir::SynOsGenericArgs syn_os_generic_args(const sxfir_plan *p, const Ca
     return a;
 }
 
+// rational plans: the generic kernel's struct of sxfir_resample.hip.h -- the call's first output has the absolute index
+// `produced`, its first input the absolute index `consumed`
+static sxfir::ResampleGenericArgs resample_generic_args(const sxfir_plan *p, const CallIO &c)
+{
+    sxfir::ResampleGenericArgs a{};
+    a.g = generic_args(p, c, 0);
+    a.down = p->down;
+    a.m_first = p->produced;
+    a.consumed = p->consumed;
+    return a;
+}
+
 static sxfir::InterpTileArgs interp_tile_args(const sxfir_plan *p, const CallIO &c, const LaunchGeom &geom, const KeyedRange *key)
 {
     sxfir::InterpTileArgs t{};
@@ -487,6 +512,24 @@ static int launch_synth(sxfir_plan *p, const CallIO &c, bool *history_done)
     return launch(p->k.syn4, grid, (unsigned)p->form->threads, c.st, syn_tile_args(p, c, geom));
 }
 
+// Rational plans (sxfir_resample): the kernel alone, as launch_interp.  resample45_kernel stands on the /4 kernels' argument
+// struct and schedule (decim_tile_args: XCD-blocked strided passes, the last tile's wave carries the history over).
+static int launch_rational(sxfir_plan *p, const CallIO &c, bool *history_done)
+{
+    *history_done = false;
+    const LaunchGeom geom = rational_geom(p, (long long)c.n_in, c.n_out, stores_aligned(p, c));
+    const dim3 grid((unsigned)geom.groups, (unsigned)p->nchan);
+    if (geom.kind == GEOM_GENERIC) {
+        if (p->kernel == SXFIR_KERNEL_TILED)
+            return fail(SXFIR_EUNSUPPORTED, "tiled resampler needs a 16-byte aligned output, an even output stride and a call that starts at a "
+                                            "stream position that is a multiple of %d", p->form ? p->form->start_multiple : 1);
+        return launch(p->k.rat_generic, grid, 256, c.st, resample_generic_args(p, c));
+    }
+    if (geom.n_tiles > 0x7fffffffLL) return fail(SXFIR_EINVAL, "call too large");
+    *history_done = true;
+    return launch(p->k.rat45, grid, (unsigned)p->form->threads, c.st, decim_tile_args(p, c, geom));
+}
+
 // Shapes the tiled kernels do not take: the keying count as a pass of its own (same rule, same counter).  Queued by
 // stream_call AFTER the history launch has succeeded, with the position commit: a call that fails half way has not
 // touched the counter, so a caller that retries the block does not count it twice (on the tiled paths the count is part of
@@ -505,6 +548,7 @@ static int launch_keyed_count(sxfir_plan *p, const void *in_dev, const KeyedRang
 static int launch_call(sxfir_plan *p, const CallIO &c, bool *history_done, const KeyedRange *key = nullptr, bool *key_pending = nullptr)
 {
     if (p->kind == KIND_SYNTHESIZER) return launch_synth(p, c, history_done);
+    if (p->kind == KIND_RATIONAL) return launch_rational(p, c, history_done);
     if (p->mode == SXFIR_DECIMATE) return launch_decim(p, c, history_done);
     return launch_interp(p, c, history_done, key, key_pending);
 }
@@ -545,18 +589,27 @@ static int check_band_layout(const sxfir_plan *p, const char *side, size_t chan_
     return fail(SXFIR_EINVAL, "bands and channels overlap (%s_stride %zu, band_stride %zu, %zu %sputs per band)", side, chan_stride, band_stride, n, side);
 }
 
-// sxfir_decimate, sxfir_interpolate and sxfir_time_*: real and complex taps
-static int check_io(const sxfir_plan *p, int mode, const CallIO &c)
+// One input and one output buffer per channel: real and complex taps, rational plans
+static int check_buffers(const sxfir_plan *p, const CallIO &c)
 {
-    if (p->kind == KIND_SYNTHESIZER) return fail(SXFIR_EINVAL, "a synthesizer plan takes sxfir_synthesize (include/sxfir_synthesizer.h)");
-    if (p->mode != mode) return fail(SXFIR_EINVAL, "plan was created for the other direction");
-    if (p->kind == KIND_CHANNELIZER) return fail(SXFIR_EINVAL, "a channelizer plan takes sxfir_channelize (include/sxfir_channelizer.h)");
     if ((c.n_in && !c.in) || (c.n_out > 0 && !c.out)) return fail(SXFIR_EINVAL, "NULL device buffer");
     if (p->nchan > 1 && (c.in_stride < c.n_in || c.out_stride < (size_t)c.n_out))
         return fail(SXFIR_EINVAL, "channel stride smaller than the block");
     if ((uintptr_t)c.in % sample_bytes(p->fmt) || (uintptr_t)c.out % sample_bytes(p->fmt))
         return fail(SXFIR_EINVAL, "buffers must be aligned to one complex sample");
     return SXFIR_OK;
+}
+
+static const char *const RATIONAL_TAKES = "a rational plan takes sxfir_resample (include/sxfir_rational.h)";
+
+// sxfir_decimate, sxfir_interpolate and sxfir_time_*: real and complex taps
+static int check_io(const sxfir_plan *p, int mode, const CallIO &c)
+{
+    if (p->kind == KIND_RATIONAL) return fail(SXFIR_EINVAL, "%s", RATIONAL_TAKES);
+    if (p->kind == KIND_SYNTHESIZER) return fail(SXFIR_EINVAL, "a synthesizer plan takes sxfir_synthesize (include/sxfir_synthesizer.h)");
+    if (p->mode != mode) return fail(SXFIR_EINVAL, "plan was created for the other direction");
+    if (p->kind == KIND_CHANNELIZER) return fail(SXFIR_EINVAL, "a channelizer plan takes sxfir_channelize (include/sxfir_channelizer.h)");
+    return check_buffers(p, c);
 }
 
 static int resample(sxfir_plan *p, int mode, const void *in_dev, size_t n_in, size_t in_stride, void *out_dev, size_t out_stride,
@@ -587,6 +640,7 @@ int sxfir_interpolate_keyed(sxfir_plan *p, const void *in_dev, size_t n_in, size
 {
     if (n_out_p) *n_out_p = 0;
     if (!p) return fail(SXFIR_EINVAL, "plan is NULL");
+    if (p->kind == KIND_RATIONAL) return fail(SXFIR_EINVAL, "%s", RATIONAL_TAKES);
     if (p->kind == KIND_SYNTHESIZER) return fail(SXFIR_EINVAL, "a synthesizer plan takes sxfir_synthesize (include/sxfir_synthesizer.h): no keying count in its version 1");
     if (p->mode != SXFIR_INTERPOLATE) return fail(SXFIR_EINVAL, "not an interpolator plan");
     if (p->fmt == SXFIR_CF16) return fail(SXFIR_EUNSUPPORTED, "the keying count is defined on CF32 input");
@@ -600,8 +654,9 @@ int sxfir_launch_geometry(const sxfir_plan *p, size_t n_in, sxfir_geometry *out)
 {
     if (!p || !out) return fail(SXFIR_EINVAL, "NULL argument");
     memset(out, 0, sizeof(*out));
-    const LaunchGeom g = p->mode == SXFIR_DECIMATE ? decim_geom(p, outputs_for(p, (long long)n_in), first_offset(p), true)
-                                                   : interp_geom(p, (long long)n_in, true, false);
+    const LaunchGeom g = p->kind == KIND_RATIONAL  ? rational_geom(p, (long long)n_in, outputs_for(p, (long long)n_in), true)
+                         : p->mode == SXFIR_DECIMATE ? decim_geom(p, outputs_for(p, (long long)n_in), first_offset(p), true)
+                                                     : interp_geom(p, (long long)n_in, true, false);
     snprintf(out->kernel, sizeof(out->kernel), "%s", g.kernel);
     out->tiled = g.kind != GEOM_GENERIC;
     out->split = g.split;

@@ -1,4 +1,4 @@
-// Plan bookkeeping of the C ABI (include/sxfir.h): what a plan holds and which of the four kinds it is, the kernel table (which
+// Plan bookkeeping of the C ABI (include/sxfir.h): what a plan holds and which of the five kinds it is, the kernel table (which
 // instance a shape launches: the one statement of it, for the occupancy query and the launches), the form rows (what the geometry
 // and launch code needs to know of a tiled kernel family: one row per family, one pointer per plan), settle_form (which row a
 // real-tap shape gets: the one statement of the product's shape-to-family rules), the tap-table layouts, the creation frame every
@@ -14,7 +14,9 @@
 // (sxfir_channelizer_os.hip.h: KIND_CHANNELIZER with ratio = bands / oversample), sxfir_create_synthesizer_os
 // (sxfir_synthesizer_os.hip.h: KIND_SYNTHESIZER with ratio = bands / oversample).  A complex-tap plan is a decimator whose taps_dev
 // holds a[0, ntaps) then b[0, ntaps); the band kinds are a /ratio decimator and a x ratio interpolator in everything about the stream.
-enum PlanKind { KIND_REAL = 0, KIND_COMPLEX = 1, KIND_CHANNELIZER = 2, KIND_SYNTHESIZER = 3 };
+// sxfir_create_rational (sxfir_rational.hip.h): KIND_RATIONAL, a x ratio interpolator (ratio = up) of which every down-th output is
+// computed -- an interpolator's history and contract, positions and output counts of its own (rational_produced).
+enum PlanKind { KIND_REAL = 0, KIND_COMPLEX = 1, KIND_CHANNELIZER = 2, KIND_SYNTHESIZER = 3, KIND_RATIONAL = 4 };
 
 // The layout of a plan's second tap table (taps_scaled_dev); one function per layout below (second_tap_table).
 // TAPS_SCALED: taps * 2^-31 (exact) in tap order, for the /4 scalar-tap kernels on S32 wire words;
@@ -28,7 +30,7 @@ enum PlanKind { KIND_REAL = 0, KIND_COMPLEX = 1, KIND_CHANNELIZER = 2, KIND_SYNT
 enum TapTable { TAPS_SCALED = 0, TAPS_SUBSET8 = 1, TAPS_PASS8 = 2, TAPS_BLOCKS16 = 3, TAPS_PHASED = 4, TAPS_NONE = 5, TAPS_PASS8_CX = 6 };
 
 // Which kernel family a call launches (LaunchGeom::kind, sxfir_launch.hip.h)
-enum { GEOM_GENERIC = 0, GEOM_MULTI = 1, GEOM_WIDE = 2, GEOM_TILE = 3, GEOM_IPASS = 4, GEOM_ITILE = 5, GEOM_CX = 6, GEOM_CHAN4 = 7, GEOM_SYN4 = 8, GEOM_CHAN4X2 = 9, GEOM_SYN4X2 = 10, GEOM_ICX = 11 };
+enum { GEOM_GENERIC = 0, GEOM_MULTI = 1, GEOM_WIDE = 2, GEOM_TILE = 3, GEOM_IPASS = 4, GEOM_ITILE = 5, GEOM_CX = 6, GEOM_CHAN4 = 7, GEOM_SYN4 = 8, GEOM_CHAN4X2 = 9, GEOM_SYN4X2 = 10, GEOM_ICX = 11, GEOM_RAT45 = 12 };
 
 // One typed kernel pointer per launch-argument family, and a plan's kernels: resolved once by the plan's creator
 // (resolve_kernels below), read by the occupancy query there and by the launches (sxfir_launch.hip.h).
@@ -44,8 +46,9 @@ typedef void (*SynTileFn)(sxfir::SynTileArgs);
 typedef void (*SynGenericFn)(sxfir::SynGenericArgs);
 typedef void (*SynOsTileFn)(sxfir::SynOsTileArgs);
 typedef void (*SynOsGenericFn)(sxfir::SynOsGenericArgs);
+typedef void (*ResampleGenericFn)(sxfir::ResampleGenericArgs);
 struct KernelTable {
-    const char *generic_name;    // the plan's generic kernel, as sxfir_launch_geometry reports it: every plan has exactly one of the five
+    const char *generic_name;    // the plan's generic kernel, as sxfir_launch_geometry reports it: every plan has exactly one of the six
     GenericFn generic;           // decim_generic_kernel / decim_cx_generic_kernel / interp_generic_kernel / interp_cx_generic_kernel: real and complex taps
     DecimMultiFn dense;          // decim_dense_kernel (/8, /16, /32)
     DecimBlocksFn blocks[2];     // decim_blocks_kernel (/48, /96): [0] the walking form, [1] SPLIT, (tile, block) items
@@ -60,6 +63,8 @@ struct KernelTable {
     SynGenericFn syn_generic;    // ... and synthesis_generic_kernel, which every synthesizer plan has INSTEAD of `generic`
     SynOsTileFn syn4x2;          // 2x oversampled synthesizer plans (include/sxfir_synthesizer_os.h): synthesis4x2_kernel (4 bands x 128 taps, CF32) ...
     SynOsGenericFn syn4x2_generic;     // ... and synthesis_os_generic_kernel, which every such plan has INSTEAD of `generic` and `syn_generic`
+    DecimTileFn rat45;           // rational plans (include/sxfir_rational.h): resample45_kernel (4/5 x 128 taps, CF32) ...
+    ResampleGenericFn rat_generic;     // ... and resample_generic_kernel, which every rational plan has INSTEAD of `generic`
 };
 
 // What the geometry and launch code needs to know of a tiled kernel family (FORM_* below).  A plan has at most one, settled at
@@ -84,6 +89,7 @@ struct PlanForm {
 struct sxfir_plan {
     int kind;              // PlanKind
     int mode, ntaps, ratio, nchan, fmt, device;
+    int down;              // rational plans: `down` of up / down (up is `ratio`); else 0
     int bands;             // the band kinds: 4 (= ratio, but for the oversampled plans); else 0.  A synthesizer's hist_dev holds
                            // bands x hist_len / bands samples per channel, band k's at k * hist_len / bands
     int oversample;        // channelizer plans: bands / ratio -- 1 critically sampled (sxfir_create_channelizer), 2 each band at fs/2
@@ -330,6 +336,11 @@ static const PlanForm FORM_CX = {"decim4_cx_kernel", GEOM_CX, 512, 64, 1, 2, tru
 // a small call keeps four tiles per workgroup as the other complex-tap and band kernels' do (a tile is twice the pass kernel's work)
 static const PlanForm FORM_ICX = {"interp_cx_pass_kernel", GEOM_ICX, TILE_IPASS, 64, 1, 2, true, 8, 8, TAPS_PASS8_CX};
 
+// resample45_kernel: rational 4/5 x 128 on CF32, tiles of Resample45::TILE_IN = 1280 inputs (256 periods of five), one wave per tile; a
+// call starts on a period (a stream position that is a multiple of 5).  Its prologue is light (the taps are re-loaded per tile), so a
+// small call spreads over the chip; generations and occupancy: tools/ratbench.py, profiles/rational.txt
+static const PlanForm FORM_RAT45 = {"resample45_kernel", GEOM_RAT45, sxfir::Resample45::TILE_IN, 64, 5, 2, false, 16, 8, TAPS_NONE};
+
 // The ratio whose kernel a tile of interp_tile_kernel runs: x48 is three phase blocks of the x16 kernel, x96 three of the x32 kernel
 static int itile_base(int ratio) { return ratio > 32 ? ratio / 3 : ratio; }
 
@@ -396,6 +407,12 @@ static void resolve_kernels(sxfir_plan *p)
         if (geom == GEOM_CHAN4X2) k.chan4x2 = sxfir::chan4x2_kernel;
         return;
     }
+    if (p->kind == KIND_RATIONAL) {
+        k.generic_name = "resample_generic_kernel";
+        k.rat_generic = p->fmt == SXFIR_CF16 ? sxfir::resample_generic_kernel<sxfir::CF16, sxfir::CF16> : sxfir::resample_generic_kernel<sxfir::CF32, sxfir::CF32>;
+        if (geom == GEOM_RAT45) k.rat45 = sxfir::resample45_kernel;
+        return;
+    }
     if (p->kind == KIND_SYNTHESIZER) {
         k.generic_name = os ? "synthesis_os_generic_kernel" : "synthesis_generic_kernel";
         if (os) k.syn4x2_generic = synthesis_os_generic_kernel_for(p->fmt);
@@ -441,6 +458,7 @@ static const void *occupancy_instance(const sxfir_plan *p)
     case GEOM_CHAN4X2: return (const void *)k.chan4x2;
     case GEOM_SYN4: return (const void *)k.syn4;
     case GEOM_SYN4X2: return (const void *)k.syn4x2;
+    case GEOM_RAT45: return (const void *)k.rat45;
     }
     return nullptr;
 }
@@ -546,6 +564,13 @@ static void real_tap_contract(sxfir_plan *p)
         p->jsplit = 1;
         p->cw = ratio;
     }
+}
+
+// A rational plan's outputs after `consumed` inputs: ceil(consumed * up / down) -- output m needs input floor(m * down / up).
+// (consumed < 2^63 / 4096: every stream position a caller can reach)
+static long long rational_produced(const sxfir_plan *p, long long consumed)
+{
+    return (consumed * p->ratio + p->down - 1) / p->down;
 }
 
 // The one list of what a plan owns
@@ -839,8 +864,9 @@ int sxfir_set_position(sxfir_plan *p, int64_t consumed)
     if (!p) return fail(SXFIR_EINVAL, "plan is NULL");
     if (consumed < 0) return fail(SXFIR_EINVAL, "negative stream position");
     p->consumed = (long long)consumed;
-    p->produced = p->mode == SXFIR_DECIMATE ? ((long long)consumed + p->ratio - 1) / p->ratio
-                                            : (long long)consumed * p->ratio;
+    if (p->kind == KIND_RATIONAL) p->produced = rational_produced(p, p->consumed);
+    else p->produced = p->mode == SXFIR_DECIMATE ? ((long long)consumed + p->ratio - 1) / p->ratio
+                                                 : (long long)consumed * p->ratio;
     return SXFIR_OK;
 }
 
@@ -849,8 +875,9 @@ int sxfir_set_kernel(sxfir_plan *p, int kernel)
     if (!p) return fail(SXFIR_EINVAL, "plan is NULL");
     if (kernel < SXFIR_KERNEL_AUTO || kernel > SXFIR_KERNEL_GENERIC) return fail(SXFIR_EINVAL, "bad kernel id");
     if (kernel == SXFIR_KERNEL_TILED && !p->form)
-        return fail(SXFIR_EUNSUPPORTED, "no tiled kernel for ntaps=%d ratio=%d fmt=%d mode=%d", p->ntaps,
-                    p->ratio, p->fmt, p->mode);
+        return p->kind == KIND_RATIONAL
+                   ? fail(SXFIR_EUNSUPPORTED, "no tiled kernel for ntaps=%d up=%d down=%d fmt=%d (4/5 x 128 on CF32 has one)", p->ntaps, p->ratio, p->down, p->fmt)
+                   : fail(SXFIR_EUNSUPPORTED, "no tiled kernel for ntaps=%d ratio=%d fmt=%d mode=%d", p->ntaps, p->ratio, p->fmt, p->mode);
     p->kernel = kernel;
     return SXFIR_OK;
 }
@@ -887,6 +914,7 @@ int sxfir_position(const sxfir_plan *p, int64_t *consumed, int64_t *produced)
 
 static long long outputs_for(const sxfir_plan *p, long long n_in)
 {
+    if (p->kind == KIND_RATIONAL) return rational_produced(p, p->consumed + n_in) - rational_produced(p, p->consumed);
     if (p->mode == SXFIR_INTERPOLATE) return n_in * p->ratio;
     const long long D = p->ratio;
     const long long before = (p->consumed + D - 1) / D;

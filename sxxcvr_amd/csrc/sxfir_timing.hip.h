@@ -6,25 +6,22 @@ extern "C" {
 
 // Timed launches (bench.py): `iters` back-to-back passes of the resampling kernel over the same buffers and
 // from the same filter state, bracketed by HIP events on the launch stream.
-static int time_passes(sxfir_plan *p, int mode, const void *in_dev, size_t n_in, size_t in_stride, void *out_dev,
-                       size_t out_stride, int iters, void *stream, float *ms_per_pass)
+// (behind the entry point's checks of the plan and the buffers: sxfir_time_resample of sxfir_rational.hip.h ends here too)
+static int time_call(sxfir_plan *p, const CallIO &c, int iters, float *ms_per_pass)
 {
-    if (!p || !ms_per_pass || iters < 1) return fail(SXFIR_EINVAL, "bad argument");
-    const CallIO c{in_dev, n_in, in_stride, out_dev, out_stride, outputs_for(p, (long long)n_in), S(stream)};
-    int rc = check_io(p, mode, c);
-    if (rc) return rc;
+    int rc = SXFIR_OK;
     if (c.n_out < 1) return fail(SXFIR_EINVAL, "nothing to do");
     HIPCHECK(hipSetDevice(p->device));
     hipEvent_t e0, e1;
     HIPCHECK(hipEventCreate(&e0));
     HIPCHECK(hipEventCreate(&e1));
-    HIPCHECK(hipEventRecord(e0, S(stream)));
+    HIPCHECK(hipEventRecord(e0, c.st));
     for (int i = 0; i < iters; ++i) {
         bool history_done = false;   // history buffers are not swapped: every pass filters from the same state
         rc = launch_call(p, c, &history_done);
         if (rc) break;
     }
-    hipError_t e = hipEventRecord(e1, S(stream));
+    hipError_t e = hipEventRecord(e1, c.st);
     if (e == hipSuccess) e = hipEventSynchronize(e1);
     float ms = 0.0f;
     if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
@@ -34,6 +31,15 @@ static int time_passes(sxfir_plan *p, int mode, const void *in_dev, size_t n_in,
     if (e != hipSuccess) return fail(SXFIR_EHIP, "event timing failed: %s", hipGetErrorString(e));
     *ms_per_pass = ms / (float)iters;
     return SXFIR_OK;
+}
+
+static int time_passes(sxfir_plan *p, int mode, const void *in_dev, size_t n_in, size_t in_stride, void *out_dev,
+                       size_t out_stride, int iters, void *stream, float *ms_per_pass)
+{
+    if (!p || !ms_per_pass || iters < 1) return fail(SXFIR_EINVAL, "bad argument");
+    const CallIO c{in_dev, n_in, in_stride, out_dev, out_stride, outputs_for(p, (long long)n_in), S(stream)};
+    if (int rc = check_io(p, mode, c)) return rc;
+    return time_call(p, c, iters, ms_per_pass);
 }
 
 int sxfir_time_decimate(sxfir_plan *p, const void *in_dev, size_t n_in, size_t in_stride, void *out_dev,

@@ -1,4 +1,4 @@
-"""Python face of the C ABI in include/sxfir.h, include/sxfir_complex.h, include/sxfir_complex_tx.h, include/sxfir_channelizer.h and include/sxfir_synthesizer.h.
+"""Python face of the C ABI in include/sxfir.h, include/sxfir_complex.h, include/sxfir_complex_tx.h, include/sxfir_channelizer.h, include/sxfir_synthesizer.h and include/sxfir_rational.h.
 
 Device memory comes either from torch (complex64 / int32 CUDA tensors, the
 current torch stream is used) or from the library's own sxfir_malloc for
@@ -63,6 +63,12 @@ def design_bandpass(ntaps, ratio, num, den, beta=8.0, gain=1.0):
     taps = np.empty(ntaps, dtype=np.complex64)
     check(lib.sxfir_design_bandpass(ntaps, ratio, beta, gain, int(num), int(den), taps.ctypes.data_as(C.c_void_p)))
     return taps
+
+
+def design_rational(up, down, taps_per_phase=32, beta=8.0):
+    """Unit-gain taps of RationalResampler(taps, up, down): the low-pass of the narrower side at the x up raster,
+    design_lowpass(up * taps_per_phase, max(up, down), beta, up)."""
+    return design_lowpass(int(up) * int(taps_per_phase), max(int(up), int(down)), beta, float(up))
 
 
 def _torch_stream(t):
@@ -367,6 +373,51 @@ class ComplexInterpolator(Resampler):
         self.mode, self.ratio, self.nchan, self.fmt, self.ntaps = INTERPOLATE, int(ratio), int(nchan), _FMT[fmt], taps.size
         self._ck(self._lib.sxfir_create_complex_interpolator(C.byref(self._plan), taps.ctypes.data_as(C.c_void_p), taps.size,
                                                              int(ratio), int(nchan), self.fmt, int(device)))
+
+
+class RationalResampler(Resampler):
+    """A rational up / down resampler (include/sxfir_rational.h): up outputs for every down inputs in one pass -- sample m * down
+    of the x up interpolator's output, bit for bit.  `taps`: real, ntaps a multiple of up (design_rational(up, down)); up and down
+    coprime, 2..4096 each; CF32 or CF16.  The plan is an interpolator plan of ratio `up` in its history and contract; call,
+    outputs_for, position, contract, geometry, set_kernel, set_history_ptr, set_position and close are Resampler's."""
+
+    def __init__(self, taps, up, down, nchan=1, fmt="CF32", device=0, profiling=False):
+        self._lib = load_sxfir(profiling)
+        self.profiling = bool(profiling)
+        self._plan = C.c_void_p()
+        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        self.mode, self.ratio, self.nchan, self.fmt, self.ntaps = INTERPOLATE, int(up), int(nchan), _FMT[fmt], taps.size
+        self._ck(self._lib.sxfir_create_rational(C.byref(self._plan), taps.ctypes.data_as(C.c_void_p), taps.size, int(up), int(down),
+                                                 int(nchan), self.fmt, int(device)))
+
+    def _ratio(self):
+        u, d = C.c_int(), C.c_int()
+        self._ck(self._lib.sxfir_plan_rational(self._plan, C.byref(u), C.byref(d)))
+        return u.value, d.value
+
+    @property
+    def up(self):
+        return self._ratio()[0]
+
+    @property
+    def down(self):
+        return self._ratio()[1]
+
+    def process_ptr(self, in_ptr, n_in, in_stride, out_ptr, out_stride, stream=0):
+        n_out = C.c_size_t()
+        self._ck(self._lib.sxfir_resample(self._plan, C.c_void_p(in_ptr), n_in, in_stride, C.c_void_p(out_ptr), out_stride,
+                                          C.byref(n_out), C.c_void_p(stream)))
+        return n_out.value
+
+    def time_resample_ptr(self, in_ptr, n_in, in_stride, out_ptr, out_stride, iters, stream=0):
+        """Mean milliseconds of `iters` back-to-back launches of the resampling kernel (sxfir_time_resample); position and
+        history are left alone."""
+        ms = C.c_float()
+        self._ck(self._lib.sxfir_time_resample(self._plan, C.c_void_p(in_ptr), n_in, in_stride, C.c_void_p(out_ptr), out_stride, iters,
+                                               C.c_void_p(stream), C.byref(ms)))
+        return ms.value
+
+    time_passes_ptr = time_resample_ptr
 
 
 class _BandPlan(_Plan):

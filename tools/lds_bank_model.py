@@ -103,8 +103,33 @@ def interp_model():
         print("x%-2d extra LDS cycles per sub-tile: window reads %d, transposition writes %d, read-back %d" % (L, rd, wr, rb))
 
 
+def rational_model():
+    """sxfir_resample.hip.h, resample45_kernel: a ds_read_b64 is served in two groups of 32 lanes, 64 banks of 4 bytes, a lane on
+    two of them.  One period per lane: windows 5 samples = 10 dwords apart in a linear image; two periods per lane: 20 dwords.
+    The output transposition is the wide kernel's swizzled layout: lane l writes chunks 2l, 2l + 1 of a round."""
+    halves = [list(range(32)), list(range(32, 64))]
+    for periods in (1, 2):
+        extra = 0
+        for w in range(19):                                     # the window samples of a half pass
+            for grp in halves:
+                banks = {}
+                for lane in grp:
+                    a = 10 * periods * lane + 2 + 2 * w         # dword address of the 8-byte read
+                    for d in (a, a + 1):
+                        banks.setdefault(d % 64, set()).add(d)
+                extra += max(len(x) for x in banks.values()) - 1
+        print("4/5, %d period(s) per lane: %d extra LDS cycles over the 19 ds_read_b64 of a half pass (%d-way)" % (periods, extra, 1 + extra // 38))
+    swz = lambda c: c ^ ((c >> 2) & 1) ^ ((c >> 3) & 3)
+    wr = sum(group_conflicts(WRITE_GROUPS, lambda l: swz(128 * k + 2 * l + e), 8) for k in (0, 1) for e in (0, 1))
+    rb = sum(group_conflicts(GROUPS, lambda l: 64 * k + (l ^ ((l >> 2) & 1) ^ ((l >> 3) & 3)), 16) for k in range(4))
+    assert sorted(swz(c) for c in range(256)) == list(range(256))
+    print("4/5 output transposition, per half of 512 outputs: writes %d, read-back %d extra LDS cycles" % (wr, rb))
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "interp":
+    if len(sys.argv) > 1 and sys.argv[1] == "rational":
+        rational_model()
+    elif len(sys.argv) > 1 and sys.argv[1] == "interp":
         interp_model()
     elif len(sys.argv) > 1 and sys.argv[1] == "search":
         for D in (32, 16, 8):

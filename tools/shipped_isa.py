@@ -3,7 +3,8 @@
     python3 tools/shipped_isa.py [substring of the kernel name] [--json]
 
 (`chan4` lists the channelizer kernels of DESIGN.md 5.6, `chan4x2` the oversampled channelizer's of 5.8, `synthesis` the synthesizer's,
-`synthesis4x2` the oversampled synthesizer's of 5.9, `interp_cx` the complex-tap interpolators' of 5.10.)
+`synthesis4x2` the oversampled synthesizer's of 5.9, `interp_cx` the complex-tap interpolators' of 5.10, `resample` the rational
+resamplers' of 5.11.)
 
 Registers / LDS / scratch come from the code object's metadata notes, instruction counts from its disassembly:
 v_pk_fma_f32, ds_read_b128, global_load_lds_dwordx4 (and how many of those carry `nt`), s_barrier, v_mfma, DPP and
@@ -61,7 +62,7 @@ def kernels(lib=None):
         cnt = lambda pat: sum(1 for o in ops if re.match(pat, o))
         r = dict(meta[sym])
         r["name"] = re.sub(r"\(.*\)$", "", pretty[sym]).replace("void sxfir::", "")
-        r.update({"v_pk_fma_f32": cnt(r"v_pk_fma_f32$"), "ds_read_b128": cnt(r"ds_read_b128$"),
+        r.update({"v_pk_fma_f32": cnt(r"v_pk_fma_f32$"), "ds_read_b128": cnt(r"ds_read_b128$"), "ds_read_b64": cnt(r"ds_read2?_b64$"),
                   "global_load_lds_dwordx4": cnt(r"global_load_lds_dwordx4$"),
                   "global_load_lds_dwordx4_nt": len(re.findall(r"global_load_lds_dwordx4[^\n]*\bnt\b", body)),
                   "s_barrier": cnt(r"s_barrier$"), "v_mfma": cnt(r"v_mfma"), "dpp_or_permlane": len(re.findall(r"_dpp|v_permlane", body)),
