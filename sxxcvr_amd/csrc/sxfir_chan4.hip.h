@@ -28,7 +28,8 @@
 // DESIGN.md 5.6 (tools/shipped_isa.py chan4).
 //
 // chan_generic_kernel -- every other tap count, CF16 storage, S32 wire words, off-boundary or misaligned calls -- is one thread
-// per output index: four chains in named registers, the butterflies, four stores.
+// per output index: four chains in named registers, the butterflies, four stores (chan_generic_output, which the oversampled
+// plan's generic kernel shares).
 //
 // New code: the reference decimates inside the SX1255, whose base-band decimator takes the one band around 0 Hz
 // (SoapySX.cpp:180-208 only programs the divider); the other three bands of the raster have no counterpart there.
@@ -64,19 +65,23 @@ struct Chan4 {
     static constexpr int NBANDS = 4;
     static constexpr int PCH = 47;                        // window chunks per pass
     static constexpr int P0FROM = 32;                     // pass 0 starts at window chunk 32 (slot 34)
-    static constexpr int NB = 16;                         // LDS read-ahead in chunks
+    static constexpr int NB = 16;                         // LDS read-ahead in chunks (the oversampled channelizer's too)
     static constexpr int BAND_SLOTS = 256;                // a band's 512 outputs in the dead image
 };
 
-// One window chunk CL of pass HALF (pass base: window chunk 0 for HALF = 1, 32 for HALF = 0).  Sample w = 2 CL + s meets output i
-// at tap 64 HALF + kl, kl = 4i + 64 - w; hs[m] = {h[64 HALF + 2m], h[64 HALF + 2m + 1]} (SGPR pairs); the tap's phase is kl & 3
-// and its accumulator u[kl & 3][i].  A function template per chunk: every tap index and accumulator index is a compile-time
-// constant.  Taps 127..124 (HALF = 1, kl >= 60) are the four chains' first: from +0.
-template <int CL, int HALF, int NB>
+// One window chunk of a pass: chunk CL of the pass is window chunk BASE + CL (BASE: 0 for pass 1 = HALF 1, P0FROM for pass 0; the
+// oversampled channelizer's odd times: one more).  Sample w = 2 CL + s of the pass meets output i at tap 64 HALF + kl,
+// kl = 4i + 64 - w; hs[m] = {h[64 HALF + 2m], h[64 HALF + 2m + 1]} (SGPR pairs); the tap's phase is kl & 3 and its accumulator
+// u[kl & 3][i].  A function template per chunk: every tap index and accumulator index is a compile-time constant.  Taps 127..124
+// (HALF = 1, kl >= 60) are the four chains' first: from +0.
+template <int CL, int HALF, int BASE, int NB>
 __device__ __forceinline__ void chan4_step(const f32x4 *win, f32x4 (&buf)[NB], const f32x2 (&hs)[32], f32x2 (&u)[4][8])
 {
     const f32x4 v = buf[CL % NB];
-    if constexpr (CL + NB < Chan4::PCH) buf[CL % NB] = win[(CL + NB) + ((CL + NB) >> 4)];
+    if constexpr (CL + NB < Chan4::PCH) {
+        constexpr int c = BASE + CL + NB;                  // (the image's pad slot after every 16 chunks)
+        buf[CL % NB] = win[c + (c >> 4)];
+    }
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
         const f32x2 x = s ? __builtin_shufflevector(v, v, 2, 3) : __builtin_shufflevector(v, v, 0, 1);
@@ -98,22 +103,36 @@ __device__ __forceinline__ void chan4_step(const f32x4 *win, f32x4 (&buf)[NB], c
     }
 }
 
-template <int HALF, int NB, int... Cs>
+template <int HALF, int BASE, int NB, int... Cs>
 __device__ __forceinline__ void chan4_pass(std::integer_sequence<int, Cs...>, const f32x4 *win, const f32x2 (&hs)[32], f32x2 (&u)[4][8])
 {
     f32x4 buf[NB];
-#pragma unroll
-    for (int c = 0; c < NB; ++c) buf[c] = win[c + (c >> 4)];
-    (chan4_step<Cs, HALF, NB>(win, buf, hs, u), ...);
+    fill_read_ahead<BASE>(win, buf);
+    (chan4_step<Cs, HALF, BASE, NB>(win, buf, hs, u), ...);
 }
 
-// taps: 128 floats.  `half` = 1: taps 64..127, 0: taps 0..63.  tp is an opaque scalar (the caller launders it per pass) so that
-// the loads stay inside the tile loop: hoisted, the two sets would need 128 SGPRs at once.
-__device__ __forceinline__ void load_chan4_taps(unsigned long long tp, int half, f32x2 (&hs)[32])
+// The branch sums of a lane's eight outputs: the two passes by tap half, the window ODD chunks further on (chan4_kernel: 0; the
+// oversampled channelizer's odd times: 1).  `taps` (128 floats) is laundered per pass so that the tap loads stay inside the tile
+// loop (load_tap_half, sxfir_common.hip.h).
+template <int ODD>
+__device__ __forceinline__ void chan4_sweep(const f32x4 *win, const float *taps, f32x2 (&u)[4][8])
 {
-    const __attribute__((address_space(4))) f32x2 *tq = (const __attribute__((address_space(4))) f32x2 *)tp;
-#pragma unroll
-    for (int m = 0; m < 32; ++m) hs[m] = tq[32 * half + m];
+    static_assert(ODD + Chan4::P0FROM + Chan4::PCH == DecimWide::WCH + ODD, "the two passes cover the window");
+    {
+        f32x2 hs[32];
+        unsigned long long tp = (unsigned long long)taps;
+        asm volatile("" : "+s"(tp));
+        load_tap_half(tp, 1, hs);
+        chan4_pass<1, ODD, Chan4::NB>(std::make_integer_sequence<int, Chan4::PCH>{}, win, hs, u);
+    }
+    {
+        f32x2 hs[32];
+        unsigned long long tp = (unsigned long long)taps;
+        // (after pass 1: the second tap set is loaded when the first is dead)
+        asm volatile("" : "+s"(tp) : "v"(u[0][0]), "v"(u[3][7]));
+        load_tap_half(tp, 0, hs);
+        chan4_pass<0, ODD + Chan4::P0FROM, Chan4::NB>(std::make_integer_sequence<int, Chan4::PCH>{}, win, hs, u);
+    }
 }
 
 // The radix-2 4-point DFT of one output's branch sums (I, Q pairs), one rounding per real operation.
@@ -131,7 +150,6 @@ __global__ __launch_bounds__(64) void chan4_kernel(const ChanTileArgs a)
 {
     using C = DecimWide;
     static_assert(C::CHUNKS % 16 == 0, "whole 16-chunk rows");
-    static_assert(Chan4::P0FROM + Chan4::PCH == C::WCH, "the two passes cover the window");
     static_assert(Chan4::NBANDS * Chan4::BAND_SLOTS <= C::SLOTS, "the four bands fit the dead image");
     static_assert(2 * Chan4::BAND_SLOTS == C::TILE_OUT, "a band's tile is the wide kernel's");
     __shared__ __attribute__((aligned(16))) f32x4 img[C::SLOTS];
@@ -167,21 +185,7 @@ __global__ __launch_bounds__(64) void chan4_kernel(const ChanTileArgs a)
         SXFIR_WAIT_VMCNT(0);
 
         f32x2 u[4][8];                                     // u[r][i]: branch sum r of output i
-        {
-            f32x2 hs[32];
-            unsigned long long tp = (unsigned long long)a.taps;
-            asm volatile("" : "+s"(tp));
-            load_chan4_taps(tp, 1, hs);
-            chan4_pass<1, Chan4::NB>(std::make_integer_sequence<int, Chan4::PCH>{}, win, hs, u);
-        }
-        {
-            f32x2 hs[32];
-            unsigned long long tp = (unsigned long long)a.taps;
-            // (after pass 1: the second tap set is loaded when the first is dead)
-            asm volatile("" : "+s"(tp) : "v"(u[0][0]), "v"(u[3][7]));
-            load_chan4_taps(tp, 0, hs);
-            chan4_pass<0, Chan4::NB>(std::make_integer_sequence<int, Chan4::PCH>{}, win + (Chan4::P0FROM + Chan4::P0FROM / 16), hs, u);
-        }
+        chan4_sweep<0>(win, a.taps, u);
         f32x4 y[Chan4::NBANDS][4];                         // y[k][q]: outputs 2q, 2q + 1 of band k
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -215,42 +219,46 @@ __global__ __launch_bounds__(64) void chan4_kernel(const ChanTileArgs a)
 
 // ---- every other shape: one thread per output index, four chains in registers
 
-struct ChanGenericArgs {
-    GenericArgs g;          // the stream fields of the generic decimator (ratio = 4; n_out = outputs per band)
-    long long band_stride;  // outputs between the bands of a channel
-};
-
-// Output m of every band: per tap row j (descending) one FMA of each chain, phases 0..3 by name -- no per-thread array that an
-// index could send to scratch.
-template <typename F, typename FO = F>
-__global__ __launch_bounds__(256) void chan_generic_kernel(const ChanGenericArgs a)
+// Output m of every band of a channelizer plan, critically sampled (OS false: the stream's ratio 4) or 2x oversampled (OS true:
+// ratio 2): per tap row j (descending) one FMA of each chain, phases 0..3 by name -- no per-thread array that an index could send
+// to scratch -- then the butterflies.  The oversampled plan ALONE shifts their operands by two where the absolute output index
+// a.m_first + m is odd (the branch sums shifted in front of the same butterflies); a critically sampled plan never does,
+// wherever its call starts.  a.n_out: outputs per band.
+template <typename F, typename FO, bool OS>
+__device__ __forceinline__ void chan_generic_output(const GenericArgs &a)
 {
+    constexpr int RATIO = OS ? 2 : 4;
     const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= a.g.n_out) return;
+    if (m >= a.n_out) return;
     const int ch = blockIdx.y;
-    const char *in = (const char *)a.g.in + sizeof(typename F::storage) * a.g.in_stride * ch;
-    const char *hist = (const char *)a.g.hist + sizeof(typename F::storage) * a.g.hist_stride * ch;
-    const long long newest = a.g.first + m * 4;
+    const char *in = (const char *)a.in + sizeof(typename F::storage) * a.in_stride * ch;
+    const char *hist = (const char *)a.hist + sizeof(typename F::storage) * a.hist_stride * ch;
+    const long long newest = a.first + m * RATIO;
     float2 u0 = make_float2(0.0f, 0.0f), u1 = u0, u2 = u0, u3 = u0;
-    for (int j = a.g.ntaps / 4 - 1; j >= 0; --j) {
-        const float *t = a.g.taps + 4 * j;
+    for (int j = a.ntaps / 4 - 1; j >= 0; --j) {
+        const float *t = a.taps + 4 * j;
         const long long at = newest - 4 * j;
-        const float2 x0 = sample_at<F>(a.g, in, hist, at), x1 = sample_at<F>(a.g, in, hist, at - 1);
-        const float2 x2 = sample_at<F>(a.g, in, hist, at - 2), x3 = sample_at<F>(a.g, in, hist, at - 3);
+        const float2 x0 = sample_at<F>(a, in, hist, at), x1 = sample_at<F>(a, in, hist, at - 1);
+        const float2 x2 = sample_at<F>(a, in, hist, at - 2), x3 = sample_at<F>(a, in, hist, at - 3);
         u0 = make_float2(__builtin_fmaf(t[0], x0.x, u0.x), __builtin_fmaf(t[0], x0.y, u0.y));
         u1 = make_float2(__builtin_fmaf(t[1], x1.x, u1.x), __builtin_fmaf(t[1], x1.y, u1.y));
         u2 = make_float2(__builtin_fmaf(t[2], x2.x, u2.x), __builtin_fmaf(t[2], x2.y, u2.y));
         u3 = make_float2(__builtin_fmaf(t[3], x3.x, u3.x), __builtin_fmaf(t[3], x3.y, u3.y));
     }
+    const bool odd = OS && ((a.m_first + m) & 1) != 0;
+    const float2 a0 = odd ? u2 : u0, a1 = odd ? u3 : u1, a2 = odd ? u0 : u2, a3 = odd ? u1 : u3;
     f32x2 y[4];
-    chan4_butterfly((f32x2){u0.x, u0.y}, (f32x2){u1.x, u1.y}, (f32x2){u2.x, u2.y}, (f32x2){u3.x, u3.y}, y);
+    chan4_butterfly((f32x2){a0.x, a0.y}, (f32x2){a1.x, a1.y}, (f32x2){a2.x, a2.y}, (f32x2){a3.x, a3.y}, y);
     // FO::store rounds to half once for CF16
-    char *out = (char *)a.g.out + sizeof(typename FO::storage) * a.g.out_stride * ch;
+    char *out = (char *)a.out + sizeof(typename FO::storage) * a.out_stride * ch;
     const long long bs = (long long)sizeof(typename FO::storage) * a.band_stride;
-    FO::store(out, m, make_float2(y[0].x, y[0].y), a.g.thr2);
-    FO::store(out + bs, m, make_float2(y[1].x, y[1].y), a.g.thr2);
-    FO::store(out + 2 * bs, m, make_float2(y[2].x, y[2].y), a.g.thr2);
-    FO::store(out + 3 * bs, m, make_float2(y[3].x, y[3].y), a.g.thr2);
+    FO::store(out, m, make_float2(y[0].x, y[0].y), a.thr2);
+    FO::store(out + bs, m, make_float2(y[1].x, y[1].y), a.thr2);
+    FO::store(out + 2 * bs, m, make_float2(y[2].x, y[2].y), a.thr2);
+    FO::store(out + 3 * bs, m, make_float2(y[3].x, y[3].y), a.thr2);
 }
+
+template <typename F, typename FO = F>
+__global__ __launch_bounds__(256) void chan_generic_kernel(const GenericArgs a) { chan_generic_output<F, FO, false>(a); }
 
 }  // namespace sxfir

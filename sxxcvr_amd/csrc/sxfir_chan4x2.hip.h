@@ -17,7 +17,8 @@
 //     window base chunk 16l.  Its even-time output 2i (i = 0..7) is chan4_kernel's output i: window sample w meets it at tap
 //     4i + 128 - w.  Its odd-time output 2i + 1 meets w at tap 4i + 130 - w: the same walk one chunk further on.  The lane's window
 //     is 80 chunks, one more than the wide kernel's 79, still inside the image: lane 63 reads up to sample 2175 of 2176;
-//   * TWO SWEEPS over the window, even times then odd times, each chan4_kernel's two passes by tap half (pass 1 = taps 127..64,
+//   * TWO SWEEPS over the window, even times then odd times (chan4_sweep<0>, chan4_sweep<1> of sxfir_chan4.hip.h: that kernel's
+//     own walk, the window one chunk further on for the odd times), each chan4_kernel's two passes by tap half (pass 1 = taps 127..64,
 //     pass 0 = taps 63..0, the 64 taps of a pass in 32 SGPR pairs re-loaded per pass behind a laundered pointer): 4 x 47 window
 //     ds_read_b128 and 2048 v_pk_fma_f32 per tile, every one with a scalar tap operand.  The even sweep's 32 butterfly results
 //     (64 VGPRs) are held while the odd sweep accumulates.  (The other layout -- ONE sweep in which a window sample feeds sixteen
@@ -36,7 +37,7 @@
 //
 // chan4x2_generic_kernel -- every other tap count, CF16 storage, S32 wire words, off-position or misaligned calls -- is one
 // thread per output index: four chains in named registers, the butterflies with their operands chosen by the parity of the
-// ABSOLUTE output index, four stores.
+// ABSOLUTE output index, four stores: chan_generic_output of sxfir_chan4.hip.h, the critically sampled plan's body with the shift.
 //
 // New code: the reference decimates inside the SX1255, whose base-band decimator takes the one band around 0 Hz
 // (SoapySX.cpp:180-208 only programs the divider); an oversampled raster has no counterpart there.
@@ -44,7 +45,7 @@
 
 #include <utility>
 
-#include "sxfir_chan4.hip.h"            // ChanTileArgs, Chan4, load_chan4_taps, chan4_butterfly; through it the wide tile's frame
+#include "sxfir_chan4.hip.h"            // ChanTileArgs, Chan4, chan4_sweep, chan4_butterfly, chan_generic_output; through it the wide tile's frame
 
 namespace sxfir {
 
@@ -53,84 +54,7 @@ struct Chan4x2 {
     static constexpr int WCH = DecimWide::WCH + 1;                // 80 window chunks per lane
     static constexpr int BAND_SLOTS = 512;                        // a band's 1024 outputs in the dead image
     static constexpr int TRIP_BANDS = 2;                          // bands per trip through the image
-    static constexpr int NB = 16;                                 // LDS read-ahead in chunks
 };
-
-// One window chunk of a pass: chunk CL of the pass is window chunk BASE + CL (BASE: 0 / 32 for the even times' passes 1 / 0, one
-// more for the odd times').  Inside the pass everything is chan4_step's: sample w = 2 CL + s meets output pair i at tap
-// 64 HALF + kl, kl = 4i + 64 - w, phase kl & 3, accumulator u[kl & 3][i]; taps 127..124 are the four chains' first: from +0.
-template <int CL, int HALF, int BASE, int NB>
-__device__ __forceinline__ void chan4x2_step(const f32x4 *win, f32x4 (&buf)[NB], const f32x2 (&hs)[32], f32x2 (&u)[4][8])
-{
-    const f32x4 v = buf[CL % NB];
-    if constexpr (CL + NB < Chan4::PCH) {
-        constexpr int c = BASE + CL + NB;                  // (the image's pad slot after every 16 chunks)
-        buf[CL % NB] = win[c + (c >> 4)];
-    }
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        const f32x2 x = s ? __builtin_shufflevector(v, v, 2, 3) : __builtin_shufflevector(v, v, 0, 1);
-        const int w = 2 * CL + s;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int kl = 4 * i + 64 - w;
-            if (kl >= 0 && kl < 64) {
-                if (HALF == 1 && kl >= 60) {
-                    if (kl & 1) pk_fma_s_hi_first(u[kl & 3][i], hs[kl >> 1], x);
-                    else pk_fma_s_lo_first(u[kl & 3][i], hs[kl >> 1], x);
-                } else if (kl & 1) {
-                    pk_fma_s_hi(u[kl & 3][i], hs[kl >> 1], x);
-                } else {
-                    pk_fma_s_lo(u[kl & 3][i], hs[kl >> 1], x);
-                }
-            }
-        }
-    }
-}
-
-template <int HALF, int BASE, int NB, int... Cs>
-__device__ __forceinline__ void chan4x2_pass(std::integer_sequence<int, Cs...>, const f32x4 *win, const f32x2 (&hs)[32], f32x2 (&u)[4][8])
-{
-    f32x4 buf[NB];
-#pragma unroll
-    for (int c = 0; c < NB; ++c) buf[c] = win[(BASE + c) + ((BASE + c) >> 4)];
-    (chan4x2_step<Cs, HALF, BASE, NB>(win, buf, hs, u), ...);
-}
-
-// The branch sums of the lane's eight outputs of one parity: chan4_kernel's two passes, the window ODD chunks further on.
-// `taps` is laundered per pass so that the tap loads stay inside the tile loop (two sets at once would need 128 SGPRs).
-template <int ODD>
-__device__ __forceinline__ void chan4x2_sweep(const f32x4 *win, const float *taps, f32x2 (&u)[4][8])
-{
-    static_assert(ODD + Chan4::P0FROM + Chan4::PCH == DecimWide::WCH + ODD, "the two passes cover the window");
-    {
-        f32x2 hs[32];
-        unsigned long long tp = (unsigned long long)taps;
-        asm volatile("" : "+s"(tp));
-        load_chan4_taps(tp, 1, hs);
-        chan4x2_pass<1, ODD, Chan4x2::NB>(std::make_integer_sequence<int, Chan4::PCH>{}, win, hs, u);
-    }
-    {
-        f32x2 hs[32];
-        unsigned long long tp = (unsigned long long)taps;
-        // (after pass 1: the second tap set is loaded when the first is dead)
-        asm volatile("" : "+s"(tp) : "v"(u[0][0]), "v"(u[3][7]));
-        load_chan4_taps(tp, 0, hs);
-        chan4x2_pass<0, ODD + Chan4::P0FROM, Chan4x2::NB>(std::make_integer_sequence<int, Chan4::PCH>{}, win, hs, u);
-    }
-}
-
-// ragged last tile of the call: element by element, straight from the registers (y[q]: outputs 2q, 2q + 1 of the lane's sixteen)
-__device__ __forceinline__ void chan4x2_store_ragged(float *out, long long m0, int lane, long long n_out, const f32x4 (&y)[8])
-{
-    const long long m = m0 + 16 * lane;
-    float *dst = out + 2 * m;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        if (m + 2 * q < n_out) { dst[4 * q] = y[q].x; dst[4 * q + 1] = y[q].y; }
-        if (m + 2 * q + 1 < n_out) { dst[4 * q + 2] = y[q].z; dst[4 * q + 3] = y[q].w; }
-    }
-}
 
 // a.n_out: outputs per channel and band at fs/2; the call starts at an EVEN output index (the host's business)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void chan4x2_kernel(const ChanTileArgs a)
@@ -182,12 +106,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
             f32x2 e[8][4];                                 // the even times' butterflies, held over the odd sweep
             {
                 f32x2 u[4][8];                             // u[r][i]: branch sum r of even-time output i
-                chan4x2_sweep<0>(win, a.taps, u);
+                chan4_sweep<0>(win, a.taps, u);
 #pragma unroll
                 for (int i = 0; i < 8; ++i) chan4_butterfly(u[0][i], u[1][i], u[2][i], u[3][i], e[i]);
             }
             f32x2 u[4][8];                                 // ... of odd-time output i
-            chan4x2_sweep<1>(win, a.taps, u);
+            chan4_sweep<1>(win, a.taps, u);
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 f32x2 o[4];
@@ -218,7 +142,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
             }
         } else {
 #pragma unroll
-            for (int k = 0; k < Chan4::NBANDS; ++k) chan4x2_store_ragged(out + 2 * a.band_stride * k, m0, lane, a.n_out, y[k]);
+            for (int k = 0; k < Chan4::NBANDS; ++k) wide_store_ragged(out + 2 * a.band_stride * k, m0, lane, a.n_out, y[k]);
         }
         // the next tile's DMA overwrites the image only after these LDS reads have returned
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -227,46 +151,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 
 // ---- every other shape: one thread per output index, four chains in registers
 
-struct ChanOsGenericArgs {
-    GenericArgs g;          // the stream fields of the generic decimator (ratio = 2; n_out = outputs per band)
-    long long band_stride;  // outputs between the bands of a channel
-    long long m_first;      // the absolute index (at fs/2) of the call's output 0: its parity chooses the butterflies' operands
-};
-
-// Output m of every band: per tap row j (descending) one FMA of each chain, phases 0..3 by name -- no per-thread array that an
-// index could send to scratch.
+// chan_generic_output (sxfir_chan4.hip.h) at the stream's ratio 2, the butterflies' operands by the parity of a.m_first + m
 template <typename F, typename FO = F>
-__global__ __launch_bounds__(256) void chan4x2_generic_kernel(const ChanOsGenericArgs a)
-{
-    const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= a.g.n_out) return;
-    const int ch = blockIdx.y;
-    const char *in = (const char *)a.g.in + sizeof(typename F::storage) * a.g.in_stride * ch;
-    const char *hist = (const char *)a.g.hist + sizeof(typename F::storage) * a.g.hist_stride * ch;
-    const long long newest = a.g.first + m * 2;
-    float2 u0 = make_float2(0.0f, 0.0f), u1 = u0, u2 = u0, u3 = u0;
-    for (int j = a.g.ntaps / 4 - 1; j >= 0; --j) {
-        const float *t = a.g.taps + 4 * j;
-        const long long at = newest - 4 * j;
-        const float2 x0 = sample_at<F>(a.g, in, hist, at), x1 = sample_at<F>(a.g, in, hist, at - 1);
-        const float2 x2 = sample_at<F>(a.g, in, hist, at - 2), x3 = sample_at<F>(a.g, in, hist, at - 3);
-        u0 = make_float2(__builtin_fmaf(t[0], x0.x, u0.x), __builtin_fmaf(t[0], x0.y, u0.y));
-        u1 = make_float2(__builtin_fmaf(t[1], x1.x, u1.x), __builtin_fmaf(t[1], x1.y, u1.y));
-        u2 = make_float2(__builtin_fmaf(t[2], x2.x, u2.x), __builtin_fmaf(t[2], x2.y, u2.y));
-        u3 = make_float2(__builtin_fmaf(t[3], x3.x, u3.x), __builtin_fmaf(t[3], x3.y, u3.y));
-    }
-    // odd time: the branch sums shifted by two in front of the same butterflies
-    const bool odd = ((a.m_first + m) & 1) != 0;
-    const float2 a0 = odd ? u2 : u0, a1 = odd ? u3 : u1, a2 = odd ? u0 : u2, a3 = odd ? u1 : u3;
-    f32x2 y[4];
-    chan4_butterfly((f32x2){a0.x, a0.y}, (f32x2){a1.x, a1.y}, (f32x2){a2.x, a2.y}, (f32x2){a3.x, a3.y}, y);
-    // FO::store rounds to half once for CF16
-    char *out = (char *)a.g.out + sizeof(typename FO::storage) * a.g.out_stride * ch;
-    const long long bs = (long long)sizeof(typename FO::storage) * a.band_stride;
-    FO::store(out, m, make_float2(y[0].x, y[0].y), a.g.thr2);
-    FO::store(out + bs, m, make_float2(y[1].x, y[1].y), a.g.thr2);
-    FO::store(out + 2 * bs, m, make_float2(y[2].x, y[2].y), a.g.thr2);
-    FO::store(out + 3 * bs, m, make_float2(y[3].x, y[3].y), a.g.thr2);
-}
+__global__ __launch_bounds__(256) void chan4x2_generic_kernel(const GenericArgs a) { chan_generic_output<F, FO, true>(a); }
 
 }  // namespace sxfir

@@ -1,6 +1,6 @@
 // The 4-band channelizer of the C ABI (include/sxfir_channelizer.h): plan creation and the streaming entry point.  The plan is
 // of KIND_CHANNELIZER: a /4 decimator in everything about the stream, created by create_band_plan (sxfir_plan.hip.h) -- the kernel
-// table gives it chan4_kernel and chan_generic_kernel, decim_geom / launch_decim (sxfir_launch.hip.h) choose between the two per
+// table gives it chan4_kernel and chan_generic_kernel, decim_geom / launch_call (sxfir_launch.hip.h) choose between the two per
 // call, the state entry points take it as it is; sxfir_decimate and its kin refuse it (check_io).  sxfir_channelize is its own
 // argument checks in front of stream_call.  Included by sxfir.hip last; not a stand-alone translation unit.
 #pragma once

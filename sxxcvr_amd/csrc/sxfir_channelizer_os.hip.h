@@ -1,7 +1,7 @@
 // The 2x oversampled 4-band channelizer of the C ABI (include/sxfir_channelizer_os.h): plan creation.  The plan is of
 // KIND_CHANNELIZER with ratio = nbands / oversample = 2 and bands = 4: a /2 decimator in everything about the stream, created
 // by create_band_plan (sxfir_plan.hip.h) -- the kernel table gives it chan4x2_kernel and chan4x2_generic_kernel, decim_geom /
-// launch_decim (sxfir_launch.hip.h) choose between the two per call, the state entry points take it as it is, and its calls come
+// launch_call (sxfir_launch.hip.h) choose between the two per call, the state entry points take it as it is, and its calls come
 // through sxfir_channelize (sxfir_channelizer.hip.h) unchanged.  Included by sxfir.hip last; not a stand-alone translation unit.
 #pragma once
 

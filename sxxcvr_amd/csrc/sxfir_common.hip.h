@@ -1,8 +1,8 @@
 // The base of the device code: what every kernel header builds on, and no kernel.  Vector types, the LDS-DMA front ends (untyped
 // global_load_lds_dwordx4 and the typed buffer_load_format_x ... lds of the CF16 storage path), lane swaps, the packed FMAs with the
 // tap in a VGPR pair or in an SGPR pair, half <-> float, the conflict-free lane maps' tables, the argument block of the multi-row
-// decimators, and the three pieces every tiled kernel repeats: the XCD-blocked deal of tiles, the edge chunk of an odd-length call
-// and the fused history carry-over.  Includes no kernel header; every kernel header includes this one.
+// decimators, and the pieces the tiled kernels repeat: the XCD-blocked deal of tiles, the tap set of a pass by tap half, the
+// read-ahead prologue of a pass over the padded image, the edge chunk of an odd-length call and the fused history carry-over.  Includes no kernel header; every kernel header includes this one.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -190,6 +190,24 @@ __device__ __forceinline__ unsigned pack_half2(float i, float q)
 __device__ __forceinline__ int xcd_blocked(int b, int w8)
 {
     return (b & 7) * w8 + (b >> 3);
+}
+
+// Taps 64 `half` .. 64 `half` + 63 of a 128-tap table as 32 SGPR pairs: the tap set of one pass of the kernels that walk a tile in
+// two passes by tap half (chan4_kernel, chan4x2_kernel, resample45_kernel).  tp is an opaque scalar (the caller launders it per
+// pass) so that the loads stay inside the tile loop: hoisted, the two sets would need 128 SGPRs at once.
+__device__ __forceinline__ void load_tap_half(unsigned long long tp, int half, f32x2 (&hs)[32])
+{
+    const __attribute__((address_space(4))) f32x2 *tq = (const __attribute__((address_space(4))) f32x2 *)tp;
+#pragma unroll
+    for (int m = 0; m < 32; ++m) hs[m] = tq[32 * half + m];
+}
+
+// The read-ahead prologue of a pass over a lane's window of the padded image: chunks BASE .. BASE + NB - 1 (a pad slot after every 16)
+template <int BASE, int NB>
+__device__ __forceinline__ void fill_read_ahead(const f32x4 *win, f32x4 (&buf)[NB])
+{
+#pragma unroll
+    for (int c = 0; c < NB; ++c) buf[c] = win[(BASE + c) + ((BASE + c) >> 4)];
 }
 
 // One 16-byte chunk of an edge tile's image: `slot0` is lane 0's slot of the DMA instruction.  With an odd n_in the call's last

@@ -1,6 +1,6 @@
 // Complex-tap (band-pass) decimators of the C ABI (include/sxfir_complex.h): plan creation and the band-pass designer.  The plan
 // is of KIND_COMPLEX: a decimator under the real-tap contract of its shape, created through the frame of sxfir_plan.hip.h -- the
-// kernel table gives it decim4_cx_kernel and decim_cx_generic_kernel, decim_geom / launch_decim (sxfir_launch.hip.h) choose between
+// kernel table gives it decim4_cx_kernel and decim_cx_generic_kernel, decim_geom / launch_call (sxfir_launch.hip.h) choose between
 // the two per call, every other entry point takes it as a decimator.  Included by sxfir.hip last; not a stand-alone translation unit.
 #pragma once
 

@@ -1,6 +1,6 @@
 // Complex-tap (band-pass) interpolators of the C ABI (include/sxfir_complex_tx.h): plan creation.  The plan is of KIND_COMPLEX: an
 // interpolator under the real-tap contract of its shape, created through the frame of sxfir_plan.hip.h -- the kernel table gives it
-// interp_cx_pass_kernel and interp_cx_generic_kernel, interp_geom / launch_interp (sxfir_launch.hip.h) choose between the two per
+// interp_cx_pass_kernel and interp_cx_generic_kernel, interp_geom / launch_call (sxfir_launch.hip.h) choose between the two per
 // call, every other entry point takes it as an interpolator.  Included by sxfir.hip behind sxfir_complex.hip.h; not a stand-alone
 // translation unit.
 #pragma once

@@ -77,8 +77,7 @@ __device__ __forceinline__ void fir_cx_pass(std::integer_sequence<int, Cs...>, c
                                             const f32x2 (&hv)[32], f32x2 (&aa)[8], f32x2 (&ab)[8])
 {
     f32x4 buf[NB];
-#pragma unroll
-    for (int c = 0; c < NB; ++c) buf[c] = win[c + (c >> 4)];
+    fill_read_ahead<0>(win, buf);
     (fir_cx_step<Cs, NB>(win, buf, hs, hv, aa, ab), ...);
 }
 

@@ -210,16 +210,22 @@ __device__ __forceinline__ void wide_store_full(const f32x4 *img, float *out, lo
     }
 }
 
-// ragged last tile of the call: element by element, straight from the registers
-__device__ __forceinline__ void wide_store_ragged(float *out, long long m0, int lane, long long n_out, const f32x4 (&y)[4])
+// ragged last tile of the call: element by element, straight from the registers.  The lane's 2 N consecutive outputs of the tile
+// (wide, complex-tap and channelizer tiles: N = 4; the oversampled channelizer's: N = 8), y[k] outputs 2k, 2k + 1 of them
+template <int N>
+__device__ __forceinline__ void store_ragged_from(float *out, long long m, long long n_out, const f32x4 (&y)[N])
 {
-    const long long m = m0 + 8 * lane;
     float *dst = out + 2 * m;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
+    for (int k = 0; k < N; ++k) {
         if (m + 2 * k < n_out) { dst[4 * k] = y[k].x; dst[4 * k + 1] = y[k].y; }
         if (m + 2 * k + 1 < n_out) { dst[4 * k + 2] = y[k].z; dst[4 * k + 3] = y[k].w; }
     }
+}
+template <int N>
+__device__ __forceinline__ void wide_store_ragged(float *out, long long m0, int lane, long long n_out, const f32x4 (&y)[N])
+{
+    store_ragged_from(out, m0 + 2 * N * lane, n_out, y);
 }
 
 // ABL (profiling): 0 = the real kernel, 1 = staging + stores without the FIR, 5 = phase stamps (per wave 8 x uint64:

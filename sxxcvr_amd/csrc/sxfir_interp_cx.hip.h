@@ -20,7 +20,7 @@
 //   * x8 stages its image with three DMA instructions instead of two, so that the rows no other tile reads (chunks 16 .. 63) are an
 //     instruction of their own and non-temporal, as the x4 image's middle instruction is;
 //   * no keyed and no wire-word instance: the keying count depends on the input alone and runs as count_keyed_kernel
-//     (launch_interp), S32 words and CF16 storage run interp_cx_generic_kernel (sxfir_kernels.hip.h).
+//     (launch_interp_tiled), S32 words and CF16 storage run interp_cx_generic_kernel (sxfir_kernels.hip.h).
 // The output path keeps the compiler's addressing at both ratios (the real x8 instance's hand-written store offsets are not
 // carried over).  Eight stores per tile at both ratios (CPL = QI L / 2 = 8): the counted wait is s_waitcnt vmcnt(8).
 //

@@ -94,6 +94,12 @@ struct GenericArgs {
     int jsplit, cw;         // numeric contract
     int rot;                // decimator: slot k' = j*D + r holds tap (k' + rot) mod ntaps (sxfir_contract_rotation)
     float thr2;             // S32 output only: transmitter-keying threshold (squared magnitude)
+    // what the band and rational plans' generic kernels read beside the stream fields (zero for every other plan)
+    long long band_stride;  // channelizers: outputs between the bands of a channel; synthesizers: input samples between them
+    long long m_first;      // absolute index of the call's first item: an oversampled channelizer's output (its parity chooses the
+                            // butterflies' operands), an oversampled synthesizer's per-band input, a rational plan's output
+    long long consumed;     // rational plans: absolute index of the call's first input
+    int down;               // rational plans: `down` of up / down (up is `ratio`)
 };
 
 template <typename F>

@@ -1,10 +1,10 @@
-// Launches of the C ABI: the launch geometry of a call (which kernel family, which grid), one builder per argument struct,
-// launch_decim / launch_interp / launch_synth, and the call frame every streaming entry point ends in: stream_call (launch_call,
-// history carry-over, keyed count, position commit) behind the entry point's own argument checks -- sxfir_decimate,
-// sxfir_interpolate and sxfir_interpolate_keyed here, sxfir_channelize, sxfir_synthesize and sxfir_resample in their own headers.  WHICH instance a
-// plan launches is not decided here: its creator resolved it from the kernel table (sxfir_plan.hip.h) into p->k.  The product path
-// reads straight through; what the profiling build adds sits behind the prof_* hooks of sxfir_prof_dispatch.inc.  Included by
-// sxfir.hip after sxfir_plan.hip.h.
+// Launches of the C ABI: the launch geometry of a call (which kernel family, which grid: call_geom), one builder per argument
+// struct, launch_call (the frame of every launch: geometry and grid, the plan's generic kernel or the form's tiled one), and the
+// call frame every streaming entry point ends in: stream_call (launch_call, history carry-over, keyed count, position commit)
+// behind the entry point's own argument checks -- sxfir_decimate, sxfir_interpolate and sxfir_interpolate_keyed here,
+// sxfir_channelize, sxfir_synthesize and sxfir_resample in their own headers.  WHICH instance a plan launches is not decided here:
+// its creator resolved it from the kernel table (sxfir_plan.hip.h) into p->k.  The product path reads straight through; what the
+// profiling build adds sits behind the prof_* hooks of sxfir_prof_dispatch.inc.  Included by sxfir.hip after sxfir_plan.hip.h.
 #pragma once
 
 // A launch that hands taps_scaled_dev to a kernel states which layout that kernel reads; the plan's creator took the layout
@@ -76,7 +76,7 @@ static int launch(void (*kernel)(P...), dim3 grid, unsigned threads, hipStream_t
 }
 
 // Launch geometry of a call: which kernel family, how many tiles, how many workgroups, how many of them the chip holds at
-// once.  One statement of it for launch_decim / launch_interp and for sxfir_launch_geometry (tools/sizebench.py, the Device's
+// once.  One statement of it (call_geom) for launch_call and for sxfir_launch_geometry (tools/sizebench.py, the Device's
 // log line for plans that fall to the generic kernels).
 struct LaunchGeom {
     int kind;                 // GEOM_* (sxfir_plan.hip.h)
@@ -219,7 +219,17 @@ static LaunchGeom rational_geom(const sxfir_plan *p, long long n_in, long long n
     return g;
 }
 
+// The geometry of a call of n_in samples (per band for a synthesizer), whatever the plan's kind
+static LaunchGeom call_geom(const sxfir_plan *p, long long n_in, bool aligned, bool keyed)
+{
+    if (p->kind == KIND_RATIONAL) return rational_geom(p, n_in, outputs_for(p, n_in), aligned);
+    if (p->mode == SXFIR_DECIMATE) return decim_geom(p, outputs_for(p, n_in), first_offset(p), aligned);
+    return interp_geom(p, n_in, aligned, keyed);
+}
+
 // ---- one builder per argument struct (value-initialised: what a kernel does not read is zero)
+// The one argument struct of every generic kernel.  `first`: a decimator's first_offset (the call's sample index of output 0's
+// newest sample); 0 for every other plan.
 static sxfir::GenericArgs generic_args(const sxfir_plan *p, const CallIO &c, long long first)
 {
     sxfir::GenericArgs a{};
@@ -240,6 +250,16 @@ static sxfir::GenericArgs generic_args(const sxfir_plan *p, const CallIO &c, lon
     a.cw = p->cw;
     a.rot = p->rot;                                 // (0 for every interpolator)
     a.thr2 = p->thr2;
+    a.band_stride = (long long)c.band_stride;
+    a.consumed = p->consumed;
+    a.down = p->down;
+    // the absolute index of the call's first item
+    if (p->kind == KIND_CHANNELIZER) a.m_first = (p->consumed + first) / p->ratio;     // `first` samples into the call lies that output
+    if (p->kind == KIND_SYNTHESIZER) {
+        a.m_first = p->consumed;                    // per-band input index
+        a.hist_len = p->hist_len / p->bands;        // a band's history; hist_stride stays the channel's
+    }
+    if (p->kind == KIND_RATIONAL) a.m_first = p->produced;
     return a;
 }
 
@@ -281,7 +301,7 @@ static sxfir::DecimTileArgs decim_tile_args(const sxfir_plan *p, const CallIO &c
     return a;
 }
 
-// channelizer plans: the two argument structs of sxfir_chan4.hip.h
+// channelizer plans, critically sampled and oversampled: the tiled kernels' argument struct of sxfir_chan4.hip.h
 static sxfir::ChanTileArgs chan_tile_args(const sxfir_plan *p, const CallIO &c, const LaunchGeom &geom)
 {
     sxfir::DecimTileArgs s{};
@@ -305,26 +325,7 @@ static sxfir::ChanTileArgs chan_tile_args(const sxfir_plan *p, const CallIO &c, 
     return a;
 }
 
-// 2x oversampled channelizer plans: ChanTileArgs for chan4x2_kernel (chan_tile_args), and the generic kernel's struct of
-// sxfir_chan4x2.hip.h -- `first` samples into the call lies the output of absolute index (consumed + first) / ratio
-static sxfir::ChanOsGenericArgs chan_os_generic_args(const sxfir_plan *p, const CallIO &c, long long first)
-{
-    sxfir::ChanOsGenericArgs a{};
-    a.g = generic_args(p, c, first);
-    a.band_stride = (long long)c.band_stride;
-    a.m_first = (p->consumed + first) / p->ratio;
-    return a;
-}
-
-static sxfir::ChanGenericArgs chan_generic_args(const sxfir_plan *p, const CallIO &c, long long first)
-{
-    sxfir::ChanGenericArgs a{};
-    a.g = generic_args(p, c, first);
-    a.band_stride = (long long)c.band_stride;
-    return a;
-}
-
-// synthesizer plans: the two argument structs of sxfir_synthesis4.hip.h
+// synthesizer plans: the tiled kernel's argument struct of sxfir_synthesis4.hip.h
 static sxfir::SynTileArgs syn_tile_args(const sxfir_plan *p, const CallIO &c, const LaunchGeom &geom)
 {
     sxfir::SynTileArgs a{};
@@ -343,42 +344,13 @@ static sxfir::SynTileArgs syn_tile_args(const sxfir_plan *p, const CallIO &c, co
     return a;
 }
 
-static sxfir::SynGenericArgs syn_generic_args(const sxfir_plan *p, const CallIO &c)
-{
-    sxfir::SynGenericArgs a{};
-    a.g = generic_args(p, c, 0);
-    a.g.hist_len = p->hist_len / p->bands;      // a band's history; hist_stride stays the channel's
-    a.band_stride = (long long)c.band_stride;
-    return a;
-}
-
-// 2x oversampled synthesizer plans: the two argument structs of sxfir_synthesis4x2.hip.h -- the call's first input has the
-// absolute per-band index `consumed`
+// 2x oversampled synthesizer plans: the tiled kernel's argument struct of sxfir_synthesis4x2.hip.h -- the call's first input has
+// the absolute per-band index `consumed`
 static sxfir::SynOsTileArgs syn_os_tile_args(const sxfir_plan *p, const CallIO &c, const LaunchGeom &geom)
 {
     sxfir::SynOsTileArgs a{};
     a.s = syn_tile_args(p, c, geom);
     a.par = (int)(p->consumed & 1);
-    return a;
-}
-
-static sxfir::SynOsGenericArgs syn_os_generic_args(const sxfir_plan *p, const CallIO &c)
-{
-    sxfir::SynOsGenericArgs a{};
-    a.s = syn_generic_args(p, c);
-    a.m_first = p->consumed;
-    return a;
-}
-
-// rational plans: the generic kernel's struct of sxfir_resample.hip.h -- the call's first output has the absolute index
-// `produced`, its first input the absolute index `consumed`
-static sxfir::ResampleGenericArgs resample_generic_args(const sxfir_plan *p, const CallIO &c)
-{
-    sxfir::ResampleGenericArgs a{};
-    a.g = generic_args(p, c, 0);
-    a.down = p->down;
-    a.m_first = p->produced;
-    a.consumed = p->consumed;
     return a;
 }
 
@@ -403,53 +375,39 @@ static sxfir::InterpTileArgs interp_tile_args(const sxfir_plan *p, const CallIO 
     return t;
 }
 
-// Launch only the resampling kernel (no history update, no position change).  *history_done: the kernel has written the next
-// call's history to hist_alt (every tiled kernel does; the caller swaps hist_dev / hist_alt when it commits the call).
-static int launch_decim(sxfir_plan *p, const CallIO &c, bool *history_done)
+// ---- the tiled launches of the families that have checks of their own, called from launch_call's switch
+
+// /8 .. /96 (GEOM_MULTI): decim_dense_kernel or decim_blocks_kernel
+static int launch_decim_multi(sxfir_plan *p, const CallIO &c, const LaunchGeom &geom, dim3 grid)
 {
-    *history_done = false;
-    const long long first = first_offset(p);
-    const LaunchGeom geom = decim_geom(p, c.n_out, first, stores_aligned(p, c));
-    const dim3 grid((unsigned)geom.groups, (unsigned)p->nchan);
-    if (geom.kind == GEOM_GENERIC) {
-        if (p->kernel == SXFIR_KERNEL_TILED)
-            return fail(SXFIR_EUNSUPPORTED,
-                        "tiled kernel needs a 16-byte aligned output, an even output stride and a call that starts on "
-                        "an output boundary%s", p->form && p->form->start_multiple == 4 ? " of even index (a stream position that is a multiple of 4)" : "");
-        // (a channelizer plan has its own generic kernel instead of `generic`)
-        if (p->k.chan4x2_generic) return launch(p->k.chan4x2_generic, grid, 256, c.st, chan_os_generic_args(p, c, first));
-        if (p->k.chan_generic) return launch(p->k.chan_generic, grid, 256, c.st, chan_generic_args(p, c, first));
-        return launch(p->k.generic, grid, 256, c.st, generic_args(p, c, first));
-    }
-    if (geom.n_tiles > 0x7fffffffLL) return fail(SXFIR_EINVAL, "call too large");
-    *history_done = true;
     const unsigned threads = (unsigned)p->form->threads;
-    if (geom.kind == GEOM_CHAN4) return launch(p->k.chan4, grid, threads, c.st, chan_tile_args(p, c, geom));
-    if (geom.kind == GEOM_CHAN4X2) return launch(p->k.chan4x2, grid, threads, c.st, chan_tile_args(p, c, geom));
-    if (geom.kind == GEOM_MULTI) {
-        sxfir::DecimMultiArgs a = decim_multi_args(p, c, geom);
-        if (p->blocks) {
-            // sixteen-column blocks, scalar taps from the block-major table of the rotated taps
-            if (int rc = need_tap_table(p, TAPS_BLOCKS16, "decim_blocks_kernel")) return rc;
-            a.taps = p->taps_scaled_dev;
-            sxfir::DecimBlocksJoin jn{};
-            jn.partials = (sxfir::f32x4 *)p->join_partials;
-            jn.arrived = p->join_arrived;
-            const int pr = prof_launch_blocks(p, geom, a, jn, grid, c.st);
-            if (pr < 0) return pr;
-            if (!pr)
-                if (int rc = launch(p->k.blocks[geom.split > 1], grid, threads, c.st, a, jn)) return rc;
-            return prof_join_drop_copy(p, geom, c.st);
-        }
-        // /8, /16, /32: decim_dense_kernel (profiling: its ablations, or the multi-column kernel it replaced)
-        if (const int pr = prof_launch_dense(p, a, grid, c.st)) return pr < 0 ? pr : SXFIR_OK;
-        if (p->form->taps == TAPS_SUBSET8) {
-            if (int rc = need_tap_table(p, TAPS_SUBSET8, p->fmt == SXFIR_CF16 ? "decim_dense_kernel<8, SUBSET, HALFIN>" : "decim_dense_kernel<8, SUBSET>")) return rc;
-            a.taps = p->taps_scaled_dev;                      // the subset-major tap table
-        }
-        return launch(p->k.dense, grid, threads, c.st, a);
+    sxfir::DecimMultiArgs a = decim_multi_args(p, c, geom);
+    if (p->blocks) {
+        // sixteen-column blocks, scalar taps from the block-major table of the rotated taps
+        if (int rc = need_tap_table(p, TAPS_BLOCKS16, "decim_blocks_kernel")) return rc;
+        a.taps = p->taps_scaled_dev;
+        sxfir::DecimBlocksJoin jn{};
+        jn.partials = (sxfir::f32x4 *)p->join_partials;
+        jn.arrived = p->join_arrived;
+        const int pr = prof_launch_blocks(p, geom, a, jn, grid, c.st);
+        if (pr < 0) return pr;
+        if (!pr)
+            if (int rc = launch(p->k.blocks[geom.split > 1], grid, threads, c.st, a, jn)) return rc;
+        return prof_join_drop_copy(p, geom, c.st);
     }
-    // /4: one wave (= one workgroup) per tile and pass
+    // /8, /16, /32: decim_dense_kernel (profiling: its ablations, or the multi-column kernel it replaced)
+    if (const int pr = prof_launch_dense(p, a, grid, c.st)) return pr < 0 ? pr : SXFIR_OK;
+    if (p->form->taps == TAPS_SUBSET8) {
+        if (int rc = need_tap_table(p, TAPS_SUBSET8, p->fmt == SXFIR_CF16 ? "decim_dense_kernel<8, SUBSET, HALFIN>" : "decim_dense_kernel<8, SUBSET>")) return rc;
+        a.taps = p->taps_scaled_dev;                      // the subset-major tap table
+    }
+    return launch(p->k.dense, grid, threads, c.st, a);
+}
+
+// /4 (GEOM_CX, GEOM_WIDE, GEOM_TILE): one wave (= one workgroup) per tile and pass
+static int launch_decim4(sxfir_plan *p, const CallIO &c, const LaunchGeom &geom, dim3 grid)
+{
+    const unsigned threads = (unsigned)p->form->threads;
     sxfir::DecimTileArgs a = decim_tile_args(p, c, geom);
     if (geom.kind == GEOM_CX) return launch(p->k.cx, grid, threads, c.st, a);
     if (p->fmt == SXFIR_S32)                               // only wire-word plans read taps_scaled
@@ -462,72 +420,38 @@ static int launch_decim(sxfir_plan *p, const CallIO &c, bool *history_done)
 
 extern "C" {
 
-// Launch only the interpolation kernel (no history swap, no position change).
-static int launch_interp(sxfir_plan *p, const CallIO &c, bool *history_done, const KeyedRange *key, bool *key_pending)
+// The interpolators (GEOM_IPASS, GEOM_ITILE, GEOM_ICX)
+static int launch_interp_tiled(sxfir_plan *p, const CallIO &c, const LaunchGeom &geom, dim3 grid, const KeyedRange *key, bool *key_pending)
 {
-    *history_done = false;
-    const LaunchGeom geom = interp_geom(p, (long long)c.n_in, stores_aligned(p, c), key != nullptr);
-    const dim3 grid((unsigned)geom.groups, (unsigned)p->nchan);
-    if (geom.kind == GEOM_GENERIC) {
-        if (p->kernel == SXFIR_KERNEL_TILED)
-            return fail(SXFIR_EUNSUPPORTED, "tiled interpolator needs a 16-byte aligned output and even strides");
-        if (int rc = launch(p->k.generic, grid, 256, c.st, generic_args(p, c, 0))) return rc;
-        if (key && key->hi > key->lo && key_pending) *key_pending = true;    // counted by the caller once the call is certain to commit
-        return SXFIR_OK;
-    }
+    const unsigned threads = (unsigned)p->form->threads;
     if (geom.kind == GEOM_IPASS)
         if (int rc = need_tap_table(p, TAPS_PASS8, "interp8_pass_kernel")) return rc;
-    if (geom.n_tiles * geom.split > 0x7fffffffLL) return fail(SXFIR_EINVAL, "call too large");
+    if (geom.n_tiles * geom.split > 0x7fffffffLL) return fail(SXFIR_EINVAL, "call too large");       // (PBSPLIT: items)
     if (geom.kind == GEOM_ICX) {
         // complex taps: no keyed instance -- the count depends on the input alone and runs as the generic path's pass of its own
         if (int rc = need_tap_table(p, TAPS_PASS8_CX, "interp_cx_pass_kernel")) return rc;
-        if (int rc = launch(p->k.interp_cx, grid, (unsigned)p->form->threads, c.st, interp_tile_args(p, c, geom, nullptr))) return rc;
-        *history_done = true;
+        if (int rc = launch(p->k.interp_cx, grid, threads, c.st, interp_tile_args(p, c, geom, nullptr))) return rc;
         if (key && key->hi > key->lo && key_pending) *key_pending = true;
         return SXFIR_OK;
     }
     if (p->fmt == SXFIR_CF16 && key) return fail(SXFIR_EUNSUPPORTED, "the keying count is defined on CF32 input");
     const sxfir::InterpTileArgs t = interp_tile_args(p, c, geom, key);
-    *history_done = true;
     if (const int pr = prof_launch_interp(p, geom, t, grid, key != nullptr, c.st)) return pr < 0 ? pr : SXFIR_OK;
-    return launch(p->k.interp[key != nullptr][geom.split > 1], grid, (unsigned)p->form->threads, c.st, t);
+    return launch(p->k.interp[key != nullptr][geom.split > 1], grid, threads, c.st, t);
 }
 
-// Synthesizer plans (sxfir_synthesize): the kernel alone, as launch_interp.
-static int launch_synth(sxfir_plan *p, const CallIO &c, bool *history_done)
+// SXFIR_KERNEL_TILED was asked for and the call falls to the generic kernel: the refusal, in the words of the plan's kind
+static int refuse_tiled(const sxfir_plan *p)
 {
-    *history_done = false;
-    const LaunchGeom geom = interp_geom(p, (long long)c.n_in, stores_aligned(p, c), false);
-    const dim3 grid((unsigned)geom.groups, (unsigned)p->nchan);
-    if (geom.kind == GEOM_GENERIC) {
-        if (p->kernel == SXFIR_KERNEL_TILED)
-            return fail(SXFIR_EUNSUPPORTED, "tiled synthesizer needs a 16-byte aligned output and an even output stride");
-        if (p->k.syn4x2_generic) return launch(p->k.syn4x2_generic, grid, 256, c.st, syn_os_generic_args(p, c));
-        return launch(p->k.syn_generic, grid, 256, c.st, syn_generic_args(p, c));
-    }
-    if (geom.n_tiles > 0x7fffffffLL) return fail(SXFIR_EINVAL, "call too large");
-    if (int rc = need_tap_table(p, TAPS_PHASED, p->form->tiled)) return rc;
-    *history_done = true;
-    if (geom.kind == GEOM_SYN4X2) return launch(p->k.syn4x2, grid, (unsigned)p->form->threads, c.st, syn_os_tile_args(p, c, geom));
-    return launch(p->k.syn4, grid, (unsigned)p->form->threads, c.st, syn_tile_args(p, c, geom));
-}
-
-// Rational plans (sxfir_resample): the kernel alone, as launch_interp.  resample45_kernel stands on the /4 kernels' argument
-// struct and schedule (decim_tile_args: XCD-blocked strided passes, the last tile's wave carries the history over).
-static int launch_rational(sxfir_plan *p, const CallIO &c, bool *history_done)
-{
-    *history_done = false;
-    const LaunchGeom geom = rational_geom(p, (long long)c.n_in, c.n_out, stores_aligned(p, c));
-    const dim3 grid((unsigned)geom.groups, (unsigned)p->nchan);
-    if (geom.kind == GEOM_GENERIC) {
-        if (p->kernel == SXFIR_KERNEL_TILED)
-            return fail(SXFIR_EUNSUPPORTED, "tiled resampler needs a 16-byte aligned output, an even output stride and a call that starts at a "
-                                            "stream position that is a multiple of %d", p->form ? p->form->start_multiple : 1);
-        return launch(p->k.rat_generic, grid, 256, c.st, resample_generic_args(p, c));
-    }
-    if (geom.n_tiles > 0x7fffffffLL) return fail(SXFIR_EINVAL, "call too large");
-    *history_done = true;
-    return launch(p->k.rat45, grid, (unsigned)p->form->threads, c.st, decim_tile_args(p, c, geom));
+    if (p->kind == KIND_SYNTHESIZER) return fail(SXFIR_EUNSUPPORTED, "tiled synthesizer needs a 16-byte aligned output and an even output stride");
+    if (p->kind == KIND_RATIONAL)
+        return fail(SXFIR_EUNSUPPORTED, "tiled resampler needs a 16-byte aligned output, an even output stride and a call that starts at a "
+                                        "stream position that is a multiple of %d", p->form ? p->form->start_multiple : 1);
+    if (p->mode == SXFIR_DECIMATE)
+        return fail(SXFIR_EUNSUPPORTED,
+                    "tiled kernel needs a 16-byte aligned output, an even output stride and a call that starts on "
+                    "an output boundary%s", p->form && p->form->start_multiple == 4 ? " of even index (a stream position that is a multiple of 4)" : "");
+    return fail(SXFIR_EUNSUPPORTED, "tiled interpolator needs a 16-byte aligned output and even strides");
 }
 
 // Shapes the tiled kernels do not take: the keying count as a pass of its own (same rule, same counter).  Queued by
@@ -544,13 +468,42 @@ static int launch_keyed_count(sxfir_plan *p, const void *in_dev, const KeyedRang
     return SXFIR_OK;
 }
 
-// The resampling kernel of a call alone (no history pass, no position change): what sxfir_time_* repeats
+// The resampling kernel of a call alone (no history pass, no position change): what stream_call launches and sxfir_time_* repeats.
+// The frame of every plan kind: geometry and grid; the plan's generic kernel; else the form's tiled kernel.  *history_done: the
+// kernel writes the next call's history to hist_alt (every tiled kernel does; the caller swaps hist_dev / hist_alt when it
+// commits the call).  *key_pending: the keying count is still to be queued, as a pass of its own (launch_keyed_count).
 static int launch_call(sxfir_plan *p, const CallIO &c, bool *history_done, const KeyedRange *key = nullptr, bool *key_pending = nullptr)
 {
-    if (p->kind == KIND_SYNTHESIZER) return launch_synth(p, c, history_done);
-    if (p->kind == KIND_RATIONAL) return launch_rational(p, c, history_done);
-    if (p->mode == SXFIR_DECIMATE) return launch_decim(p, c, history_done);
-    return launch_interp(p, c, history_done, key, key_pending);
+    *history_done = false;
+    const LaunchGeom geom = call_geom(p, (long long)c.n_in, stores_aligned(p, c), key != nullptr);
+    const dim3 grid((unsigned)geom.groups, (unsigned)p->nchan);
+    if (geom.kind == GEOM_GENERIC) {
+        if (p->kernel == SXFIR_KERNEL_TILED) return refuse_tiled(p);
+        const long long first = p->mode == SXFIR_DECIMATE ? first_offset(p) : 0;        // (a rational plan is an interpolator)
+        if (int rc = launch(p->k.generic, grid, 256, c.st, generic_args(p, c, first))) return rc;
+        if (key && key->hi > key->lo && key_pending) *key_pending = true;    // counted by the caller once the call is certain to commit
+        return SXFIR_OK;
+    }
+    if (geom.n_tiles > 0x7fffffffLL) return fail(SXFIR_EINVAL, "call too large");
+    *history_done = true;
+    const unsigned threads = (unsigned)p->form->threads;
+    switch (geom.kind) {
+    case GEOM_CHAN4: return launch(p->k.chan4, grid, threads, c.st, chan_tile_args(p, c, geom));
+    case GEOM_CHAN4X2: return launch(p->k.chan4x2, grid, threads, c.st, chan_tile_args(p, c, geom));
+    case GEOM_SYN4:
+    case GEOM_SYN4X2:
+        if (int rc = need_tap_table(p, TAPS_PHASED, p->form->tiled)) return rc;
+        if (geom.kind == GEOM_SYN4X2) return launch(p->k.syn4x2, grid, threads, c.st, syn_os_tile_args(p, c, geom));
+        return launch(p->k.syn4, grid, threads, c.st, syn_tile_args(p, c, geom));
+    // resample45_kernel stands on the /4 kernels' argument struct and schedule (decim_tile_args: XCD-blocked strided passes, the
+    // last tile's wave carries the history over)
+    case GEOM_RAT45: return launch(p->k.rat45, grid, threads, c.st, decim_tile_args(p, c, geom));
+    case GEOM_IPASS:
+    case GEOM_ITILE:
+    case GEOM_ICX: return launch_interp_tiled(p, c, geom, grid, key, key_pending);
+    case GEOM_MULTI: return launch_decim_multi(p, c, geom, grid);
+    }
+    return launch_decim4(p, c, geom, grid);
 }
 
 // Everything behind an entry point's argument checks (which have set *n_out_p to 0).  A call that fails changes nothing: the
@@ -654,9 +607,7 @@ int sxfir_launch_geometry(const sxfir_plan *p, size_t n_in, sxfir_geometry *out)
 {
     if (!p || !out) return fail(SXFIR_EINVAL, "NULL argument");
     memset(out, 0, sizeof(*out));
-    const LaunchGeom g = p->kind == KIND_RATIONAL  ? rational_geom(p, (long long)n_in, outputs_for(p, (long long)n_in), true)
-                         : p->mode == SXFIR_DECIMATE ? decim_geom(p, outputs_for(p, (long long)n_in), first_offset(p), true)
-                                                     : interp_geom(p, (long long)n_in, true, false);
+    const LaunchGeom g = call_geom(p, (long long)n_in, true, false);
     snprintf(out->kernel, sizeof(out->kernel), "%s", g.kernel);
     out->tiled = g.kind != GEOM_GENERIC;
     out->split = g.split;

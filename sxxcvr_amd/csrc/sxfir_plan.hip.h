@@ -40,31 +40,21 @@ typedef void (*DecimBlocksFn)(sxfir::DecimMultiArgs, sxfir::DecimBlocksJoin);
 typedef void (*DecimTileFn)(sxfir::DecimTileArgs);
 typedef void (*InterpTileFn)(sxfir::InterpTileArgs);
 typedef void (*ChanTileFn)(sxfir::ChanTileArgs);
-typedef void (*ChanGenericFn)(sxfir::ChanGenericArgs);
-typedef void (*ChanOsGenericFn)(sxfir::ChanOsGenericArgs);
 typedef void (*SynTileFn)(sxfir::SynTileArgs);
-typedef void (*SynGenericFn)(sxfir::SynGenericArgs);
 typedef void (*SynOsTileFn)(sxfir::SynOsTileArgs);
-typedef void (*SynOsGenericFn)(sxfir::SynOsGenericArgs);
-typedef void (*ResampleGenericFn)(sxfir::ResampleGenericArgs);
 struct KernelTable {
-    const char *generic_name;    // the plan's generic kernel, as sxfir_launch_geometry reports it: every plan has exactly one of the six
-    GenericFn generic;           // decim_generic_kernel / decim_cx_generic_kernel / interp_generic_kernel / interp_cx_generic_kernel: real and complex taps
+    const char *generic_name;    // the plan's generic kernel, as sxfir_launch_geometry reports it, and the instance: every plan of every
+    GenericFn generic;           // kind has exactly one (generic_kernel below), the kernel of every call its form does not take
     DecimMultiFn dense;          // decim_dense_kernel (/8, /16, /32)
     DecimBlocksFn blocks[2];     // decim_blocks_kernel (/48, /96): [0] the walking form, [1] SPLIT, (tile, block) items
     DecimTileFn tile, wide, cx;  // /4: decim4_tile_kernel, decim4_wide_kernel, decim4_cx_kernel (complex taps)
     InterpTileFn interp[2][2];   // [keyed][split]: interp8_pass_kernel; interp_tile_kernel on CF16 storage ([0][0] alone)
     InterpTileFn interp_cx;      // complex-tap interpolators (include/sxfir_complex_tx.h): interp_cx_pass_kernel (x4 x 128, x8 x 256, CF32)
-    ChanTileFn chan4;            // channelizer plans (include/sxfir_channelizer.h): chan4_kernel (4 bands x 128 taps, CF32) ...
-    ChanGenericFn chan_generic;  // ... and chan_generic_kernel, which every channelizer plan has INSTEAD of `generic`
-    ChanTileFn chan4x2;          // 2x oversampled channelizer plans (include/sxfir_channelizer_os.h): chan4x2_kernel (4 bands x 128 taps, CF32) ...
-    ChanOsGenericFn chan4x2_generic;   // ... and chan4x2_generic_kernel, which every such plan has INSTEAD of `generic` and `chan_generic`
-    SynTileFn syn4;              // synthesizer plans (include/sxfir_synthesizer.h): synthesis4_kernel (4 bands x 128 taps, CF32) ...
-    SynGenericFn syn_generic;    // ... and synthesis_generic_kernel, which every synthesizer plan has INSTEAD of `generic`
-    SynOsTileFn syn4x2;          // 2x oversampled synthesizer plans (include/sxfir_synthesizer_os.h): synthesis4x2_kernel (4 bands x 128 taps, CF32) ...
-    SynOsGenericFn syn4x2_generic;     // ... and synthesis_os_generic_kernel, which every such plan has INSTEAD of `generic` and `syn_generic`
-    DecimTileFn rat45;           // rational plans (include/sxfir_rational.h): resample45_kernel (4/5 x 128 taps, CF32) ...
-    ResampleGenericFn rat_generic;     // ... and resample_generic_kernel, which every rational plan has INSTEAD of `generic`
+    ChanTileFn chan4;            // channelizer plans (include/sxfir_channelizer.h): chan4_kernel (4 bands x 128 taps, CF32)
+    ChanTileFn chan4x2;          // 2x oversampled channelizer plans (include/sxfir_channelizer_os.h): chan4x2_kernel (4 bands x 128 taps, CF32)
+    SynTileFn syn4;              // synthesizer plans (include/sxfir_synthesizer.h): synthesis4_kernel (4 bands x 128 taps, CF32)
+    SynOsTileFn syn4x2;          // 2x oversampled synthesizer plans (include/sxfir_synthesizer_os.h): synthesis4x2_kernel (4 bands x 128 taps, CF32)
+    DecimTileFn rat45;           // rational plans (include/sxfir_rational.h): resample45_kernel (4/5 x 128 taps, CF32)
 };
 
 // What the geometry and launch code needs to know of a tiled kernel family (FORM_* below).  A plan has at most one, settled at
@@ -133,37 +123,35 @@ struct sxfir_plan {
 // the walking, non-SPLIT form for /48 and /96; interp_kernel(16, CF32, unkeyed, walking) for every x16 .. x96 plan whatever its
 // ratio, format or keying, (8, CF32, ...) for x8 and (4, CF32, ...) for x4; decim4_tile_kernel's CF32 instance for S32 words too.
 // The launch geometry of every plan was measured with these figures.
-static GenericFn generic_kernel(int mode, int fmt, bool cx)
+//
+// The generic kernels: one per plan kind (and, for the band kinds, per oversampling), one thread per item, all on GenericArgs.  A
+// kernel's three instances by format: the RX kinds take S32 wire words in and give CF32 (<S32, CF32>), the TX kinds take CF32 and
+// give wire words (<CF32, S32>); a rational plan has no wire-word form.
+struct GenericKernel { const char *name; GenericFn fn; };
+// (WI, WO: the storage formats of a wire-word plan's instance)
+#define SXFIR_GENERIC(K, WI, WO) \
+    return GenericKernel{#K, fmt == SXFIR_CF32 ? (GenericFn)K<CF32> : fmt == SXFIR_CF16 ? (GenericFn)K<CF16> : (GenericFn)K<WI, WO>}
+static GenericKernel generic_kernel(int kind, int oversample, int mode, int fmt)
 {
     using namespace sxfir;
-    if (cx && mode == SXFIR_DECIMATE) {
-        if (fmt == SXFIR_CF32) return decim_cx_generic_kernel<CF32>;
-        if (fmt == SXFIR_CF16) return decim_cx_generic_kernel<CF16>;
-        return decim_cx_generic_kernel<S32, CF32>;
+    const bool os = oversample == 2, rx = mode == SXFIR_DECIMATE;
+    switch (kind) {
+    case KIND_CHANNELIZER:      // four chains and the butterflies per thread (oversampled: of the output's parity)
+        if (os) SXFIR_GENERIC(chan4x2_generic_kernel, S32, CF32);
+        SXFIR_GENERIC(chan_generic_kernel, S32, CF32);
+    case KIND_SYNTHESIZER:      // the butterflies once per input index, four phase chains per thread (oversampled: the two DFT
+        if (os) SXFIR_GENERIC(synthesis_os_generic_kernel, CF32, S32);      // outputs an input index needs, two chains)
+        SXFIR_GENERIC(synthesis_generic_kernel, CF32, S32);
+    case KIND_RATIONAL:
+        return GenericKernel{"resample_generic_kernel", fmt == SXFIR_CF16 ? (GenericFn)resample_generic_kernel<CF16, CF16> : (GenericFn)resample_generic_kernel<CF32, CF32>};
+    case KIND_COMPLEX:
+        if (rx) SXFIR_GENERIC(decim_cx_generic_kernel, S32, CF32);
+        SXFIR_GENERIC(interp_cx_generic_kernel, CF32, S32);
     }
-    if (cx) {
-        if (fmt == SXFIR_CF32) return interp_cx_generic_kernel<CF32>;
-        if (fmt == SXFIR_CF16) return interp_cx_generic_kernel<CF16>;
-        return interp_cx_generic_kernel<CF32, S32>;
-    }
-    if (mode == SXFIR_DECIMATE) {
-        if (fmt == SXFIR_CF32) return decim_generic_kernel<CF32>;
-        if (fmt == SXFIR_CF16) return decim_generic_kernel<CF16>;
-        return decim_generic_kernel<S32, CF32>;
-    }
-    if (fmt == SXFIR_CF32) return interp_generic_kernel<CF32>;
-    if (fmt == SXFIR_CF16) return interp_generic_kernel<CF16>;
-    return interp_generic_kernel<CF32, S32>;
+    if (rx) SXFIR_GENERIC(decim_generic_kernel, S32, CF32);
+    SXFIR_GENERIC(interp_generic_kernel, CF32, S32);
 }
-
-// channelizer plans: four chains and the butterflies per thread
-static ChanGenericFn chan_generic_kernel_for(int fmt)
-{
-    using namespace sxfir;
-    if (fmt == SXFIR_CF32) return chan_generic_kernel<CF32>;
-    if (fmt == SXFIR_CF16) return chan_generic_kernel<CF16>;
-    return chan_generic_kernel<S32, CF32>;
-}
+#undef SXFIR_GENERIC
 
 // /8, /16, /32 with 32 taps per phase: decim_dense_kernel, non-temporal staging loads for the image rows no other tile reads
 // (NTLD = 2: both halos stay plain loads; round 4, profiles/round4h_kbench_both_halos_plain.txt: whole kernel -0.9 % at /32,
@@ -262,33 +250,6 @@ static InterpTileFn interp_cx_kernel(int ratio)
     if (ratio == 4) return sxfir::interp_cx_pass_kernel<4, 4>;
     if (ratio == 8) return sxfir::interp_cx_pass_kernel<2, 8>;
     return nullptr;
-}
-
-// 2x oversampled channelizer plans: four chains and the butterflies of the output's parity per thread
-static ChanOsGenericFn chan4x2_generic_kernel_for(int fmt)
-{
-    using namespace sxfir;
-    if (fmt == SXFIR_CF32) return chan4x2_generic_kernel<CF32>;
-    if (fmt == SXFIR_CF16) return chan4x2_generic_kernel<CF16>;
-    return chan4x2_generic_kernel<S32, CF32>;
-}
-
-// synthesizer plans: the butterflies once per input index, four phase chains per thread
-static SynGenericFn synthesis_generic_kernel_for(int fmt)
-{
-    using namespace sxfir;
-    if (fmt == SXFIR_CF32) return synthesis_generic_kernel<CF32>;
-    if (fmt == SXFIR_CF16) return synthesis_generic_kernel<CF16>;
-    return synthesis_generic_kernel<CF32, S32>;
-}
-
-// 2x oversampled synthesizer plans: the two DFT outputs an input index needs, two chains per thread
-static SynOsGenericFn synthesis_os_generic_kernel_for(int fmt)
-{
-    using namespace sxfir;
-    if (fmt == SXFIR_CF32) return synthesis_os_generic_kernel<CF32>;
-    if (fmt == SXFIR_CF16) return synthesis_os_generic_kernel<CF16>;
-    return synthesis_os_generic_kernel<CF32, S32>;
 }
 
 // The four band forms, [synthesizer][oversampled].  chan4_kernel: tiles of 512 outputs per band.  chan4x2_kernel (ratio 2): 1024
@@ -392,40 +353,20 @@ static void set_form(sxfir_plan *p, const PlanForm *f)
     p->occ = f->occ;
 }
 
-// The plan's kernels, from its kind and its form
+// The plan's kernels, from its kind and its form: the generic kernel every plan has, and the form's tiled instance(s)
 static void resolve_kernels(sxfir_plan *p)
 {
     KernelTable &k = p->k;
     k = KernelTable{};
-    const bool os = p->oversample == 2;
-    const int geom = p->form ? p->form->geom : GEOM_GENERIC;
-    if (p->kind == KIND_CHANNELIZER) {      // every band plan has its own generic kernel INSTEAD of `generic`
-        k.generic_name = os ? "chan4x2_generic_kernel" : "chan_generic_kernel";
-        if (os) k.chan4x2_generic = chan4x2_generic_kernel_for(p->fmt);
-        else k.chan_generic = chan_generic_kernel_for(p->fmt);
-        if (geom == GEOM_CHAN4) k.chan4 = sxfir::chan4_kernel;
-        if (geom == GEOM_CHAN4X2) k.chan4x2 = sxfir::chan4x2_kernel;
-        return;
-    }
-    if (p->kind == KIND_RATIONAL) {
-        k.generic_name = "resample_generic_kernel";
-        k.rat_generic = p->fmt == SXFIR_CF16 ? sxfir::resample_generic_kernel<sxfir::CF16, sxfir::CF16> : sxfir::resample_generic_kernel<sxfir::CF32, sxfir::CF32>;
-        if (geom == GEOM_RAT45) k.rat45 = sxfir::resample45_kernel;
-        return;
-    }
-    if (p->kind == KIND_SYNTHESIZER) {
-        k.generic_name = os ? "synthesis_os_generic_kernel" : "synthesis_generic_kernel";
-        if (os) k.syn4x2_generic = synthesis_os_generic_kernel_for(p->fmt);
-        else k.syn_generic = synthesis_generic_kernel_for(p->fmt);
-        if (geom == GEOM_SYN4) k.syn4 = sxfir::synthesis4_kernel;
-        if (geom == GEOM_SYN4X2) k.syn4x2 = sxfir::synthesis4x2_kernel;
-        return;
-    }
-    const bool cx = p->kind == KIND_COMPLEX;
-    if (p->mode == SXFIR_DECIMATE) k.generic_name = cx ? "decim_cx_generic_kernel" : "decim_generic_kernel";
-    else k.generic_name = cx ? "interp_cx_generic_kernel" : "interp_generic_kernel";
-    k.generic = generic_kernel(p->mode, p->fmt, cx);
-    switch (geom) {
+    const GenericKernel g = generic_kernel(p->kind, p->oversample, p->mode, p->fmt);
+    k.generic_name = g.name;
+    k.generic = g.fn;
+    switch (p->form ? p->form->geom : GEOM_GENERIC) {
+    case GEOM_CHAN4: k.chan4 = sxfir::chan4_kernel; break;
+    case GEOM_CHAN4X2: k.chan4x2 = sxfir::chan4x2_kernel; break;
+    case GEOM_SYN4: k.syn4 = sxfir::synthesis4_kernel; break;
+    case GEOM_SYN4X2: k.syn4x2 = sxfir::synthesis4x2_kernel; break;
+    case GEOM_RAT45: k.rat45 = sxfir::resample45_kernel; break;
     case GEOM_CX: k.cx = sxfir::decim4_cx_kernel; break;
     case GEOM_ICX: k.interp_cx = interp_cx_kernel(p->ratio); break;
     case GEOM_MULTI:

@@ -1,7 +1,7 @@
 // Rational (up / down) resamplers of the C ABI (include/sxfir_rational.h): plan creation and the streaming entry points.  The plan
 // is of KIND_RATIONAL: a x up interpolator (mode SXFIR_INTERPOLATE, ratio = up: its history, its contract) of which every down-th
 // output is computed, created through the frame of sxfir_plan.hip.h -- the kernel table gives it resample_generic_kernel and, at
-// 4/5 x 128 on CF32, resample45_kernel; rational_geom / launch_rational (sxfir_launch.hip.h) choose between the two per call;
+// 4/5 x 128 on CF32, resample45_kernel; rational_geom / launch_call (sxfir_launch.hip.h) choose between the two per call;
 // outputs_for and sxfir_set_position know its output count; the state entry points take it as it is; sxfir_interpolate and its kin
 // refuse it (check_io).  sxfir_resample is its own argument checks in front of stream_call.  Included by sxfir.hip last; not a
 // stand-alone translation unit.

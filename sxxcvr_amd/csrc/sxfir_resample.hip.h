@@ -37,30 +37,24 @@
 
 namespace sxfir {
 
-// the x up interpolator's GenericArgs (ratio = up) and what makes every down-th output of it
-struct ResampleGenericArgs {
-    GenericArgs g;
-    int down;
-    long long m_first;      // absolute index of the call's first output
-    long long consumed;     // absolute index of the call's first input
-};
-
 // One output per thread, any up / down / taps per phase / channel count / stride / start position: output m is phase m*down mod up
-// of input index floor(m*down / up) of the interpolator -- interp_generic_output, the statement of the contract.  The first output
+// of input index floor(m*down / up) of the interpolator -- interp_generic_output, the statement of the contract -- on the x up
+// interpolator's GenericArgs (ratio = up) with a.down, a.m_first (the absolute index of the call's first output) and a.consumed
+// (that of its first input).  The first output
 // of a call has floor(m*down / up) >= consumed, so the chain reaches at most T - 1 samples into the history.
 template <typename F, typename FO = F>
-__global__ __launch_bounds__(256) void resample_generic_kernel(const ResampleGenericArgs a)
+__global__ __launch_bounds__(256) void resample_generic_kernel(const GenericArgs a)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.g.n_out) return;
+    if (i >= a.n_out) return;
     const int ch = blockIdx.y;
-    const char *in = (const char *)a.g.in + sizeof(typename F::storage) * a.g.in_stride * ch;
-    const char *hist = (const char *)a.g.hist + sizeof(typename F::storage) * a.g.hist_stride * ch;
-    char *out = (char *)a.g.out + sizeof(typename FO::storage) * a.g.out_stride * ch;
+    const char *in = (const char *)a.in + sizeof(typename F::storage) * a.in_stride * ch;
+    const char *hist = (const char *)a.hist + sizeof(typename F::storage) * a.hist_stride * ch;
+    char *out = (char *)a.out + sizeof(typename FO::storage) * a.out_stride * ch;
     const long long n = (a.m_first + i) * a.down;           // index on the x up raster (64-bit: past 2^31 at 2^26 inputs and more)
-    const long long q = n / a.g.ratio;
-    const int r = (int)(n - q * a.g.ratio);
-    FO::store(out, i, interp_generic_output<F>(a.g, a.g.taps, in, hist, q - a.consumed, r), a.g.thr2);
+    const long long q = n / a.ratio;
+    const int r = (int)(n - q * a.ratio);
+    FO::store(out, i, interp_generic_output<F>(a, a.taps, in, hist, q - a.consumed, r), a.thr2);
 }
 
 struct Resample45 {
@@ -109,15 +103,6 @@ __device__ __forceinline__ void rat45_half(std::integer_sequence<int, Ws...>, co
 #pragma unroll
     for (int w = 0; w < (int)sizeof...(Ws); ++w) x[w] = win[w];
     (rat45_step<Ws>(x[Ws], hs, acc), ...);
-}
-
-// taps 64 `half` .. 64 `half` + 63 as 32 SGPR pairs.  tp is an opaque scalar (the caller launders it per pass) so that the loads
-// stay inside the tile loop: hoisted, the two sets would need 128 SGPRs at once.
-__device__ __forceinline__ void load_rat45_taps(unsigned long long tp, int half, f32x2 (&hs)[32])
-{
-    const __attribute__((address_space(4))) f32x2 *tq = (const __attribute__((address_space(4))) f32x2 *)tp;
-#pragma unroll
-    for (int m = 0; m < 32; ++m) hs[m] = tq[32 * half + m];
 }
 
 // HBM -> LDS for tile t: 11 LDS-DMA instructions into the linear image, 1..9 non-temporal
@@ -189,7 +174,7 @@ __global__ __launch_bounds__(64) void resample45_kernel(const DecimTileArgs a)
             f32x2 hs[32];
             unsigned long long tp = (unsigned long long)a.taps;
             asm volatile("" : "+s"(tp));
-            load_rat45_taps(tp, 1, hs);
+            load_tap_half(tp, 1, hs);
 #pragma unroll
             for (int k = 0; k < C::ROUNDS; ++k) rat45_half(std::make_integer_sequence<int, C::WIN>{}, win + C::ROUND_STEP * k, hs, a1[k]);
         }
@@ -198,7 +183,7 @@ __global__ __launch_bounds__(64) void resample45_kernel(const DecimTileArgs a)
             unsigned long long tp = (unsigned long long)a.taps;
             // (after pass 1: the second tap set is loaded when the first is dead)
             asm volatile("" : "+s"(tp) : "v"(a1[0][0]), "v"(a1[C::ROUNDS - 1][3]));
-            load_rat45_taps(tp, 0, hs);
+            load_tap_half(tp, 0, hs);
 #pragma unroll
             for (int k = 0; k < C::ROUNDS; ++k) rat45_half(std::make_integer_sequence<int, C::WIN>{}, win + C::ROUND_STEP * k + 16, hs, a0[k]);
         }
@@ -225,15 +210,7 @@ __global__ __launch_bounds__(64) void resample45_kernel(const DecimTileArgs a)
         } else {
             // the call's last tile: element by element, straight from the registers, nothing past n_out
 #pragma unroll
-            for (int k = 0; k < C::ROUNDS; ++k) {
-                const long long m = m0 + C::UP * (64 * k + lane);
-                float *dst = out + 2 * m;
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    if (m + 2 * e < a.n_out) { dst[4 * e] = y[k][e].x; dst[4 * e + 1] = y[k][e].y; }
-                    if (m + 2 * e + 1 < a.n_out) { dst[4 * e + 2] = y[k][e].z; dst[4 * e + 3] = y[k][e].w; }
-                }
-            }
+            for (int k = 0; k < C::ROUNDS; ++k) store_ragged_from(out, m0 + C::UP * (64 * k + lane), a.n_out, y[k]);
         }
         // the next tile's DMA overwrites the image only after these LDS reads have returned
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

@@ -74,32 +74,36 @@ struct Syn4 {
     static constexpr int NW = 18;                         // window chunks of a pass: image samples 4l .. 4l + 35
 };
 
-// One window chunk T (0..17) of pass r: samples w = 2T, 2T + 1 of the lane's window meet input qi at tap row j = 32 + qi - w (when
-// 0 <= j < 32); hs[j >> 1] holds the phase's taps pairwise; row half p = j >> 4 has its own chain, whose first tap is row 16p + 15.
-template <int T>
-__device__ __forceinline__ void syn4_step(const f32x4 &v, const f32x2 (&hs)[16], f32x2 (&acc)[2][4])
+// One window chunk T of a pass of either synthesizer kernel: samples w = 2T, 2T + 1 of the lane's window meet the lane's q-th
+// output of the pass (NQ of them) at tap row j = ROWS + STEP q + OFF - w (when 0 <= j < ROWS); hs[j >> 1] holds the pass's ROWS taps
+// pairwise; each row half j / (ROWS / 2) has its own chain, whose first tap is its last row.  synthesis4_kernel: <32, 1, 0, 4>
+// (pass = phase r, q = the lane's input qi); synthesis4x2_kernel: <64, 2, r >> 1, NQ> (pass = output residue r, q = output r + 4q
+// of the lane's sixteen).
+template <int T, int ROWS, int STEP, int OFF, int NQ>
+__device__ __forceinline__ void syn_step(const f32x4 &v, const f32x2 (&hs)[ROWS / 2], f32x2 (&acc)[2][NQ])
 {
+    constexpr int HALF = ROWS / 2;
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
         const int w = 2 * T + s;
         const f32x2 x = s ? __builtin_shufflevector(v, v, 2, 3) : __builtin_shufflevector(v, v, 0, 1);
 #pragma unroll
-        for (int qi = 0; qi < 4; ++qi) {
-            const int j = 32 + qi - w;
-            if (j >= 0 && j < 32) {
-                // (w ascends, j descends: row 15 of a half is its chain's first, from an inline +0)
-                if ((j & 15) == 15) pk_fma_s_hi_first(acc[j >> 4][qi], hs[j >> 1], x);
-                else if (j & 1) pk_fma_s_hi(acc[j >> 4][qi], hs[j >> 1], x);
-                else pk_fma_s_lo(acc[j >> 4][qi], hs[j >> 1], x);
+        for (int q = 0; q < NQ; ++q) {
+            const int j = ROWS + STEP * q + OFF - w;
+            if (j >= 0 && j < ROWS) {
+                // (w ascends, j descends: the last row of a half is its chain's first, from an inline +0)
+                if ((j & (HALF - 1)) == HALF - 1) pk_fma_s_hi_first(acc[j / HALF][q], hs[j >> 1], x);
+                else if (j & 1) pk_fma_s_hi(acc[j / HALF][q], hs[j >> 1], x);
+                else pk_fma_s_lo(acc[j / HALF][q], hs[j >> 1], x);
             }
         }
     }
 }
 
-template <int... Ts>
-__device__ __forceinline__ void syn4_steps(std::integer_sequence<int, Ts...>, const f32x4 (&win)[Syn4::NW], const f32x2 (&hs)[16], f32x2 (&acc)[2][4])
+template <int ROWS, int STEP, int OFF, int NQ, int NW, int... Ts>
+__device__ __forceinline__ void syn_steps(std::integer_sequence<int, Ts...>, const f32x4 (&win)[NW], const f32x2 (&hs)[ROWS / 2], f32x2 (&acc)[2][NQ])
 {
-    (syn4_step<Ts>(win[Ts], hs, acc), ...);
+    (syn_step<Ts, ROWS, STEP, OFF, NQ>(win[Ts], hs, acc), ...);
 }
 
 // The butterflies of one chunk (two samples) of the four band images of PITCH slots each, in place.
@@ -249,7 +253,7 @@ __global__ __launch_bounds__(64) void synthesis4_kernel(const SynTileArgs a)
             f32x2 hs[16];
             syn_load_tap_set(hs, tq0, r, r == 0, prev);      // (a set per pass)
             f32x2 acc[2][4];                                    // every chain's first FMA (rows 31 and 15) writes it
-            syn4_steps(std::make_integer_sequence<int, C::NW>{}, win, hs, acc);
+            syn_steps<32, 1, 0, 4>(std::make_integer_sequence<int, C::NW>{}, win, hs, acc);
             f32x2 y[4];
 #pragma unroll
             for (int qi = 0; qi < 4; ++qi) y[qi] = (f32x2){__fadd_rn(acc[0][qi].x, acc[1][qi].x), __fadd_rn(acc[0][qi].y, acc[1][qi].y)};
@@ -301,34 +305,32 @@ __global__ __launch_bounds__(64) void synthesis4_kernel(const SynTileArgs a)
 
 // ---- every other shape: one thread per input index, the butterflies once per (m - j), four chains in registers
 
-struct SynGenericArgs {
-    GenericArgs g;          // the stream fields of the generic kernels (ratio = 4; n_in = inputs per band; hist_len = a band's history;
-                            // hist: band k of a channel at k * hist_len, hist_stride = 4 * hist_len)
-    long long band_stride;  // samples between the bands of a channel
-};
+// Both synthesizer generic kernels read GenericArgs with ratio = 4 (2: oversampled), n_in = inputs per band, hist_len = a BAND's
+// history (band k of a channel at k * hist_len of its hist_stride = 4 * hist_len samples) and band_stride = samples between the
+// bands of a channel.
 
 // Outputs 4m .. 4m + 3: per tap row j (descending inside each of the jsplit ranges) the four bands' samples at m - j, their
 // butterflies, one FMA of each phase chain -- phases 0..3 by name, no per-thread array that an index could send to scratch.
 template <typename F, typename FO = F>
-__global__ __launch_bounds__(256) void synthesis_generic_kernel(const SynGenericArgs a)
+__global__ __launch_bounds__(256) void synthesis_generic_kernel(const GenericArgs a)
 {
     const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= a.g.n_in) return;
+    if (m >= a.n_in) return;
     const int ch = blockIdx.y;
     const long long sb = (long long)sizeof(typename F::storage);
-    const char *in = (const char *)a.g.in + sb * a.g.in_stride * ch;
-    const char *hist = (const char *)a.g.hist + sb * a.g.hist_stride * ch;
-    const long long bs = sb * a.band_stride, hs = sb * a.g.hist_len;
-    const int jl = a.g.ntaps / 4 / a.g.jsplit;
+    const char *in = (const char *)a.in + sb * a.in_stride * ch;
+    const char *hist = (const char *)a.hist + sb * a.hist_stride * ch;
+    const long long bs = sb * a.band_stride, hs = sb * a.hist_len;
+    const int jl = a.ntaps / 4 / a.jsplit;
     f32x2 y0 = {0.0f, 0.0f}, y1 = y0, y2 = y0, y3 = y0;
-    for (int p = 0; p < a.g.jsplit; ++p) {
+    for (int p = 0; p < a.jsplit; ++p) {
         f32x2 u0 = {0.0f, 0.0f}, u1 = u0, u2 = u0, u3 = u0;
         for (int j = (p + 1) * jl - 1; j >= p * jl; --j) {
-            const float2 x0 = sample_at<F>(a.g, in, hist, m - j), x1 = sample_at<F>(a.g, in + bs, hist + hs, m - j);
-            const float2 x2 = sample_at<F>(a.g, in + 2 * bs, hist + 2 * hs, m - j), x3 = sample_at<F>(a.g, in + 3 * bs, hist + 3 * hs, m - j);
+            const float2 x0 = sample_at<F>(a, in, hist, m - j), x1 = sample_at<F>(a, in + bs, hist + hs, m - j);
+            const float2 x2 = sample_at<F>(a, in + 2 * bs, hist + 2 * hs, m - j), x3 = sample_at<F>(a, in + 3 * bs, hist + 3 * hs, m - j);
             f32x2 v[4];
             chan4_butterfly((f32x2){x0.x, x0.y}, (f32x2){x1.x, x1.y}, (f32x2){x2.x, x2.y}, (f32x2){x3.x, x3.y}, v);
-            const float *t = a.g.taps + 4 * j;
+            const float *t = a.taps + 4 * j;
             u0 = (f32x2){__builtin_fmaf(t[0], v[0].x, u0.x), __builtin_fmaf(t[0], v[0].y, u0.y)};
             u1 = (f32x2){__builtin_fmaf(t[1], v[1].x, u1.x), __builtin_fmaf(t[1], v[1].y, u1.y)};
             u2 = (f32x2){__builtin_fmaf(t[2], v[2].x, u2.x), __builtin_fmaf(t[2], v[2].y, u2.y)};
@@ -345,11 +347,11 @@ __global__ __launch_bounds__(256) void synthesis_generic_kernel(const SynGeneric
         }
     }
     // FO::store rounds to half once for CF16 and makes the wire words for S32
-    char *out = (char *)a.g.out + sizeof(typename FO::storage) * a.g.out_stride * ch;
-    FO::store(out, 4 * m, make_float2(y0.x, y0.y), a.g.thr2);
-    FO::store(out, 4 * m + 1, make_float2(y1.x, y1.y), a.g.thr2);
-    FO::store(out, 4 * m + 2, make_float2(y2.x, y2.y), a.g.thr2);
-    FO::store(out, 4 * m + 3, make_float2(y3.x, y3.y), a.g.thr2);
+    char *out = (char *)a.out + sizeof(typename FO::storage) * a.out_stride * ch;
+    FO::store(out, 4 * m, make_float2(y0.x, y0.y), a.thr2);
+    FO::store(out, 4 * m + 1, make_float2(y1.x, y1.y), a.thr2);
+    FO::store(out, 4 * m + 2, make_float2(y2.x, y2.y), a.thr2);
+    FO::store(out, 4 * m + 3, make_float2(y3.x, y3.y), a.thr2);
 }
 
 // History carry-over of the generic path: band k's last hist_len samples of (hist_k ++ in_k), out of place as history_kernel.

@@ -38,7 +38,7 @@
 
 #include <utility>
 
-#include "sxfir_synthesis4.hip.h"       // SynTileArgs, SynGenericArgs, synthesis_history_kernel; through it chan4_butterfly, glds16, the packed FMAs
+#include "sxfir_synthesis4.hip.h"       // SynTileArgs, syn_step, synthesis_history_kernel; through it chan4_butterfly, glds16, the packed FMAs
 
 namespace sxfir {
 
@@ -64,35 +64,6 @@ struct Syn4x2 {
     static constexpr int NW = (QI + HIST) / 2;            // window chunks of a pass: image samples QI l .. QI l + QI + 63
     static constexpr int NBFLY = (CHUNKS + 63) / 64;      // butterfly chunks per lane (the last one on the lanes below CHUNKS % 64)
 };
-
-// One window chunk T (0..35) of a pass with RH = r >> 1: samples w = 2T, 2T + 1 of the lane's window meet output q (input 2q + RH of
-// the lane's eight) at tap row i = 64 + 2q + RH - w (when 0 <= i < 64); hs[i >> 1] holds the parity's taps pairwise; row half
-// i >> 5 has its own chain, whose first tap is row 32 (i >> 5) + 31.
-template <int T, int RH>
-__device__ __forceinline__ void syn4x2_step(const f32x4 &v, const f32x2 (&hs)[32], f32x2 (&acc)[2][Syn4x2::NQ])
-{
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        const int w = 2 * T + s;
-        const f32x2 x = s ? __builtin_shufflevector(v, v, 2, 3) : __builtin_shufflevector(v, v, 0, 1);
-#pragma unroll
-        for (int q = 0; q < Syn4x2::NQ; ++q) {
-            const int i = 64 + 2 * q + RH - w;
-            if (i >= 0 && i < 64) {
-                // (w ascends, i descends: row 31 of a half is its chain's first, from an inline +0)
-                if ((i & 31) == 31) pk_fma_s_hi_first(acc[i >> 5][q], hs[i >> 1], x);
-                else if (i & 1) pk_fma_s_hi(acc[i >> 5][q], hs[i >> 1], x);
-                else pk_fma_s_lo(acc[i >> 5][q], hs[i >> 1], x);
-            }
-        }
-    }
-}
-
-template <int RH, int... Ts>
-__device__ __forceinline__ void syn4x2_steps(std::integer_sequence<int, Ts...>, const f32x4 (&win)[Syn4x2::NW], const f32x2 (&hs)[32], f32x2 (&acc)[2][Syn4x2::NQ])
-{
-    (syn4x2_step<Ts, RH>(win[Ts], hs, acc), ...);
-}
 
 __global__ __launch_bounds__(64) void synthesis4x2_kernel(const SynOsTileArgs ao)
 {
@@ -213,8 +184,10 @@ __global__ __launch_bounds__(64) void synthesis4x2_kernel(const SynOsTileArgs ao
                 if (next < a.n_tiles) counted = stage_band(next, r ^ flip);
             }
             f32x2 acc[2][C::NQ];                                  // every chain's first FMA (rows 63 and 31) writes it
-            if (r < 2) syn4x2_steps<0>(std::make_integer_sequence<int, C::NW>{}, win, hs, acc);
-            else syn4x2_steps<1>(std::make_integer_sequence<int, C::NW>{}, win, hs, acc);
+            // syn_step (sxfir_synthesis4.hip.h): window sample w meets output q (input 2q + (r >> 1) of the lane's eight) at tap row
+            // i = 64 + 2q + (r >> 1) - w of the parity's 64
+            if (r < 2) syn_steps<64, 2, 0, C::NQ>(std::make_integer_sequence<int, C::NW>{}, win, hs, acc);
+            else syn_steps<64, 2, 1, C::NQ>(std::make_integer_sequence<int, C::NW>{}, win, hs, acc);
             f32x2 y[C::NQ];
 #pragma unroll
             for (int q = 0; q < C::NQ; ++q) y[q] = (f32x2){__fadd_rn(acc[0][q].x, acc[1][q].x), __fadd_rn(acc[0][q].y, acc[1][q].y)};
@@ -271,33 +244,27 @@ __global__ __launch_bounds__(64) void synthesis4x2_kernel(const SynOsTileArgs ao
 
 // ---- every other shape: one thread per input index, two chains in registers
 
-struct SynOsGenericArgs {
-    SynGenericArgs s;       // synthesis_generic_kernel's fields (ratio = 2; hist_len = a band's history, ntaps / 2)
-    long long m_first;      // absolute per-band index of the call's first input
-};
-
-// Outputs 2m and 2m + 1 (residues 2 (M & 1) and 2 (M & 1) + 1 for the absolute index M): per tap row i (descending inside each
+// Outputs 2m and 2m + 1 (residues 2 (M & 1) and 2 (M & 1) + 1 for the absolute per-band input index M = a.m_first + m): per tap row i (descending inside each
 // of the jsplit ranges) the four bands' samples at m - i, the two DFT outputs these residues name -- each the butterflies' own
 // expression of it -- and one FMA of each chain; the chains by name, no per-thread array that an index could send to scratch.
 template <typename F, typename FO = F>
-__global__ __launch_bounds__(256) void synthesis_os_generic_kernel(const SynOsGenericArgs ao)
+__global__ __launch_bounds__(256) void synthesis_os_generic_kernel(const GenericArgs a)
 {
-    const SynGenericArgs &a = ao.s;
     const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= a.g.n_in) return;
+    if (m >= a.n_in) return;
     const int ch = blockIdx.y;
     const long long sb = (long long)sizeof(typename F::storage);
-    const char *in = (const char *)a.g.in + sb * a.g.in_stride * ch;
-    const char *hist = (const char *)a.g.hist + sb * a.g.hist_stride * ch;
-    const long long bs = sb * a.band_stride, hs = sb * a.g.hist_len;
-    const bool odd = ((ao.m_first + m) & 1) != 0;           // outputs of residues 2, 3: v_2 and v_3; else v_0 and v_1
-    const int jl = a.g.ntaps / 2 / a.g.jsplit;
+    const char *in = (const char *)a.in + sb * a.in_stride * ch;
+    const char *hist = (const char *)a.hist + sb * a.hist_stride * ch;
+    const long long bs = sb * a.band_stride, hs = sb * a.hist_len;
+    const bool odd = ((a.m_first + m) & 1) != 0;           // outputs of residues 2, 3: v_2 and v_3; else v_0 and v_1
+    const int jl = a.ntaps / 2 / a.jsplit;
     f32x2 y0 = {0.0f, 0.0f}, y1 = y0;
-    for (int p = 0; p < a.g.jsplit; ++p) {
+    for (int p = 0; p < a.jsplit; ++p) {
         f32x2 u0 = {0.0f, 0.0f}, u1 = u0;
         for (int i = (p + 1) * jl - 1; i >= p * jl; --i) {
-            const float2 x0 = sample_at<F>(a.g, in, hist, m - i), x1 = sample_at<F>(a.g, in + bs, hist + hs, m - i);
-            const float2 x2 = sample_at<F>(a.g, in + 2 * bs, hist + 2 * hs, m - i), x3 = sample_at<F>(a.g, in + 3 * bs, hist + 3 * hs, m - i);
+            const float2 x0 = sample_at<F>(a, in, hist, m - i), x1 = sample_at<F>(a, in + bs, hist + hs, m - i);
+            const float2 x2 = sample_at<F>(a, in + 2 * bs, hist + 2 * hs, m - i), x3 = sample_at<F>(a, in + 3 * bs, hist + 3 * hs, m - i);
             // chan4_butterfly's lines for v_0 / v_2 (from a0, b0) and v_1 / v_3 (from a1, b1)
             const f32x2 a0 = {__fadd_rn(x0.x, x2.x), __fadd_rn(x0.y, x2.y)}, b0 = {__fadd_rn(x1.x, x3.x), __fadd_rn(x1.y, x3.y)};
             const f32x2 a1 = {__fsub_rn(x0.x, x2.x), __fsub_rn(x0.y, x2.y)}, b1 = {__fsub_rn(x1.x, x3.x), __fsub_rn(x1.y, x3.y)};
@@ -309,7 +276,7 @@ __global__ __launch_bounds__(256) void synthesis_os_generic_kernel(const SynOsGe
                 va = (f32x2){__fadd_rn(a0.x, b0.x), __fadd_rn(a0.y, b0.y)};         // v_0
                 vb = (f32x2){__fsub_rn(a1.x, b1.y), __fadd_rn(a1.y, b1.x)};         // v_1
             }
-            const float *t = a.g.taps + 2 * i;
+            const float *t = a.taps + 2 * i;
             u0 = (f32x2){__builtin_fmaf(t[0], va.x, u0.x), __builtin_fmaf(t[0], va.y, u0.y)};
             u1 = (f32x2){__builtin_fmaf(t[1], vb.x, u1.x), __builtin_fmaf(t[1], vb.y, u1.y)};
         }
@@ -322,9 +289,9 @@ __global__ __launch_bounds__(256) void synthesis_os_generic_kernel(const SynOsGe
         }
     }
     // FO::store rounds to half once for CF16 and makes the wire words for S32
-    char *out = (char *)a.g.out + sizeof(typename FO::storage) * a.g.out_stride * ch;
-    FO::store(out, 2 * m, make_float2(y0.x, y0.y), a.g.thr2);
-    FO::store(out, 2 * m + 1, make_float2(y1.x, y1.y), a.g.thr2);
+    char *out = (char *)a.out + sizeof(typename FO::storage) * a.out_stride * ch;
+    FO::store(out, 2 * m, make_float2(y0.x, y0.y), a.thr2);
+    FO::store(out, 2 * m + 1, make_float2(y1.x, y1.y), a.thr2);
 }
 
 }  // namespace sxfir

@@ -1,6 +1,6 @@
 // The 4-band synthesizer of the C ABI (include/sxfir_synthesizer.h): plan creation and the streaming entry point.  The plan is
 // of KIND_SYNTHESIZER: a x4 interpolator in everything about the stream, created by create_band_plan (sxfir_plan.hip.h) -- the kernel
-// table gives it synthesis4_kernel and synthesis_generic_kernel, interp_geom / launch_synth (sxfir_launch.hip.h) choose between the
+// table gives it synthesis4_kernel and synthesis_generic_kernel, interp_geom / launch_call (sxfir_launch.hip.h) choose between the
 // two per call, the state entry points take it as it is; sxfir_interpolate and its kin refuse it (check_io).  sxfir_synthesize is
 // its own argument checks in front of stream_call.  Included by sxfir.hip last; not a stand-alone translation unit.
 #pragma once

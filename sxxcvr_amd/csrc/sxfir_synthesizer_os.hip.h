@@ -1,7 +1,7 @@
 // The 2x oversampled 4-band synthesizer of the C ABI (include/sxfir_synthesizer_os.h): plan creation.  The plan is of
 // KIND_SYNTHESIZER with ratio = nbands / oversample = 2 and bands = 4: a x2 interpolator in everything about the stream, created
 // by create_band_plan (sxfir_plan.hip.h) -- the kernel table gives it synthesis4x2_kernel and synthesis_os_generic_kernel,
-// interp_geom / launch_synth (sxfir_launch.hip.h) choose between the two per call, the state entry points take it as it is, and
+// interp_geom / launch_call (sxfir_launch.hip.h) choose between the two per call, the state entry points take it as it is, and
 // its calls come through sxfir_synthesize (sxfir_synthesizer.hip.h) unchanged.  Included by sxfir.hip last; not a stand-alone
 // translation unit.
 #pragma once

@@ -12,7 +12,7 @@ import pytest
 import sxxcvr_amd
 from sxxcvr_amd import design_lowpass
 from sxxcvr_amd.resampler import DECIMATE, KERNEL_GENERIC, KERNEL_TILED
-from gpu_util import OUT_FILL, assert_bands, assert_bit_exact, band_proto, chan_ref, random_taps, run, to_cpu, to_gpu, wideband_source
+from gpu_util import OUT_FILL, assert_bands, assert_bit_exact, band_proto, chan_os_ref, chan_ref, random_taps, run, to_cpu, to_gpu, wideband_source
 
 pytestmark = pytest.mark.gpu
 
@@ -165,6 +165,31 @@ def test_generic_tap_counts(oracle, ntaps):
         plan.set_kernel(KERNEL_TILED)
     assert ei.value.code == -4
     assert_bands(run(plan, xg), chan_ref(oracle, h, xs), "generic 4 x %d" % ntaps)
+
+
+@pytest.mark.parametrize("oversample", [1, 2])
+def test_generic_start_parity(oracle, oversample):
+    """6. Calls that start at an odd absolute output index, on both generic channelizer kernels: 32 taps (no tiled form), three
+    calls of 5, 6 and 3 outputs per band -- the second starts at output 5, the third at output 11.  The oversampled plan shifts
+    the butterflies' operands by the parity of the ABSOLUTE output index; the critically sampled plan never does."""
+    import torch
+    h = random_taps(32)
+    ratio = 4 // oversample
+    blocks = [ratio * m for m in (5, 6, 3)]
+    xg, xs = source(oracle, 10, sum(blocks))
+    plan = sxxcvr_amd.Channelizer(h, oversample=oversample)
+    name = GENERIC if oversample == 1 else "chan4x2_generic_kernel"
+    outs, pos = [], 0
+    for b in blocks:
+        g = plan.geometry(b)
+        assert not g["tiled"] and g["kernel"] == name, g
+        outs.append(plan.process(xg[pos:pos + b].clone()))
+        pos += b
+    torch.cuda.synchronize()
+    assert [o.shape[1] for o in outs] == [5, 6, 3]
+    ref = chan_ref(oracle, h, xs) if oversample == 1 else chan_os_ref(oracle, h, xs)
+    assert_bands(np.concatenate([to_cpu(o) for o in outs], axis=1), ref, "generic, oversample %d, calls of 5, 6, 3 outputs" % oversample)
+    assert plan.position == (sum(blocks), 14)
 
 
 def test_generic_cf16(oracle, proto):
