@@ -151,6 +151,11 @@ def load_sxfir(profiling=False):
         "sxfir_resample": (ci, [vp, vp, sz, sz, vp, sz, P(sz), vp]),
         "sxfir_time_resample": (ci, [vp, vp, sz, sz, vp, sz, ci, vp, P(C.c_float)]),
         "sxfir_plan_rational": (ci, [vp, P(ci), P(ci)]),
+        # include/sxfir_translate.h: frequency-translating decimators
+        "sxfir_translate_abi_version": (ci, []),
+        "sxfir_design_rotator": (ci, [ci, vp]),
+        "sxfir_create_translating": (ci, [P(vp), vp, ci, ci, ci, ci, ci, ci, ci]),
+        "sxfir_plan_translation": (ci, [vp, P(ci), P(ci)]),
     }
     if profiling:
         sig["sxfir_debug_clock"] = (ci, [vp, P(dbl)])

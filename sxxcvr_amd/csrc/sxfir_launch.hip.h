@@ -375,6 +375,39 @@ static sxfir::InterpTileArgs interp_tile_args(const sxfir_plan *p, const CallIO 
     return t;
 }
 
+// translating plans (include/sxfir_translate.h).  The call's first output has the absolute index `produced`: its table index, in
+// 64 bits, and for the tiled kernel the steps between lanes, tiles and a wave's tiles, so that its tile loop has no division
+static sxfir::Mixer mixer_of(const sxfir_plan *p)
+{
+    sxfir::Mixer m{};
+    m.w = p->mix_dev;
+    m.den = (unsigned)p->mix_den;
+    m.s = (unsigned)p->mix_s;
+    m.phase = (unsigned)((p->produced % p->mix_den) * p->mix_s % p->mix_den);
+    return m;
+}
+
+static sxfir::MixGenericArgs mix_generic_args(const sxfir_plan *p, const CallIO &c, long long first)
+{
+    sxfir::MixGenericArgs a{};
+    a.g = generic_args(p, c, first);
+    a.g.m_first = p->produced;
+    a.mix = mixer_of(p);
+    return a;
+}
+
+static sxfir::MixTileArgs mix_tile_args(const sxfir_plan *p, const CallIO &c, const LaunchGeom &geom)
+{
+    sxfir::MixTileArgs a{};
+    a.t = decim_tile_args(p, c, geom);
+    a.mix = mixer_of(p);
+    const long long den = p->mix_den, s = p->mix_s;
+    a.lane_step = (unsigned)(8 * s % den);
+    a.tile_step = (unsigned)(p->tile * s % den);
+    a.stride_step = (unsigned)((long long)a.t.n_waves % den * a.tile_step % den);
+    return a;
+}
+
 // ---- the tiled launches of the families that have checks of their own, called from launch_call's switch
 
 // /8 .. /96 (GEOM_MULTI): decim_dense_kernel or decim_blocks_kernel
@@ -480,7 +513,8 @@ static int launch_call(sxfir_plan *p, const CallIO &c, bool *history_done, const
     if (geom.kind == GEOM_GENERIC) {
         if (p->kernel == SXFIR_KERNEL_TILED) return refuse_tiled(p);
         const long long first = p->mode == SXFIR_DECIMATE ? first_offset(p) : 0;        // (a rational plan is an interpolator)
-        if (int rc = launch(p->k.generic, grid, 256, c.st, generic_args(p, c, first))) return rc;
+        if (int rc = p->mix_den ? launch(p->k.mix_generic, grid, 256, c.st, mix_generic_args(p, c, first))
+                                : launch(p->k.generic, grid, 256, c.st, generic_args(p, c, first))) return rc;
         if (key && key->hi > key->lo && key_pending) *key_pending = true;    // counted by the caller once the call is certain to commit
         return SXFIR_OK;
     }
@@ -498,6 +532,7 @@ static int launch_call(sxfir_plan *p, const CallIO &c, bool *history_done, const
     // resample45_kernel stands on the /4 kernels' argument struct and schedule (decim_tile_args: XCD-blocked strided passes, the
     // last tile's wave carries the history over)
     case GEOM_RAT45: return launch(p->k.rat45, grid, threads, c.st, decim_tile_args(p, c, geom));
+    case GEOM_MIX: return launch(p->k.mix, grid, threads, c.st, mix_tile_args(p, c, geom));
     case GEOM_IPASS:
     case GEOM_ITILE:
     case GEOM_ICX: return launch_interp_tiled(p, c, geom, grid, key, key_pending);

@@ -13,7 +13,8 @@
 // (sxfir_channelizer.hip.h), sxfir_create_synthesizer (sxfir_synthesizer.hip.h), sxfir_create_channelizer_os
 // (sxfir_channelizer_os.hip.h: KIND_CHANNELIZER with ratio = bands / oversample), sxfir_create_synthesizer_os
 // (sxfir_synthesizer_os.hip.h: KIND_SYNTHESIZER with ratio = bands / oversample).  A complex-tap plan is a decimator whose taps_dev
-// holds a[0, ntaps) then b[0, ntaps); the band kinds are a /ratio decimator and a x ratio interpolator in everything about the stream.
+// holds a[0, ntaps) then b[0, ntaps) -- sxfir_create_translating (sxfir_translate.hip.h) makes one that carries a mixer (mix_dev,
+// mix_den, mix_s: its outputs turned by a table entry each, kernels and argument structs of their own); the band kinds are a /ratio decimator and a x ratio interpolator in everything about the stream.
 // sxfir_create_rational (sxfir_rational.hip.h): KIND_RATIONAL, a x ratio interpolator (ratio = up) of which every down-th output is
 // computed -- an interpolator's history and contract, positions and output counts of its own (rational_produced).
 enum PlanKind { KIND_REAL = 0, KIND_COMPLEX = 1, KIND_CHANNELIZER = 2, KIND_SYNTHESIZER = 3, KIND_RATIONAL = 4 };
@@ -30,7 +31,7 @@ enum PlanKind { KIND_REAL = 0, KIND_COMPLEX = 1, KIND_CHANNELIZER = 2, KIND_SYNT
 enum TapTable { TAPS_SCALED = 0, TAPS_SUBSET8 = 1, TAPS_PASS8 = 2, TAPS_BLOCKS16 = 3, TAPS_PHASED = 4, TAPS_NONE = 5, TAPS_PASS8_CX = 6 };
 
 // Which kernel family a call launches (LaunchGeom::kind, sxfir_launch.hip.h)
-enum { GEOM_GENERIC = 0, GEOM_MULTI = 1, GEOM_WIDE = 2, GEOM_TILE = 3, GEOM_IPASS = 4, GEOM_ITILE = 5, GEOM_CX = 6, GEOM_CHAN4 = 7, GEOM_SYN4 = 8, GEOM_CHAN4X2 = 9, GEOM_SYN4X2 = 10, GEOM_ICX = 11, GEOM_RAT45 = 12 };
+enum { GEOM_GENERIC = 0, GEOM_MULTI = 1, GEOM_WIDE = 2, GEOM_TILE = 3, GEOM_IPASS = 4, GEOM_ITILE = 5, GEOM_CX = 6, GEOM_CHAN4 = 7, GEOM_SYN4 = 8, GEOM_CHAN4X2 = 9, GEOM_SYN4X2 = 10, GEOM_ICX = 11, GEOM_RAT45 = 12, GEOM_MIX = 13 };
 
 // One typed kernel pointer per launch-argument family, and a plan's kernels: resolved once by the plan's creator
 // (resolve_kernels below), read by the occupancy query there and by the launches (sxfir_launch.hip.h).
@@ -42,6 +43,8 @@ typedef void (*InterpTileFn)(sxfir::InterpTileArgs);
 typedef void (*ChanTileFn)(sxfir::ChanTileArgs);
 typedef void (*SynTileFn)(sxfir::SynTileArgs);
 typedef void (*SynOsTileFn)(sxfir::SynOsTileArgs);
+typedef void (*MixGenericFn)(sxfir::MixGenericArgs);
+typedef void (*MixTileFn)(sxfir::MixTileArgs);
 struct KernelTable {
     const char *generic_name;    // the plan's generic kernel, as sxfir_launch_geometry reports it, and the instance: every plan of every
     GenericFn generic;           // kind has exactly one (generic_kernel below), the kernel of every call its form does not take
@@ -55,6 +58,8 @@ struct KernelTable {
     SynTileFn syn4;              // synthesizer plans (include/sxfir_synthesizer.h): synthesis4_kernel (4 bands x 128 taps, CF32)
     SynOsTileFn syn4x2;          // 2x oversampled synthesizer plans (include/sxfir_synthesizer_os.h): synthesis4x2_kernel (4 bands x 128 taps, CF32)
     DecimTileFn rat45;           // rational plans (include/sxfir_rational.h): resample45_kernel (4/5 x 128 taps, CF32)
+    MixGenericFn mix_generic;    // translating plans (include/sxfir_translate.h): decim_mix_generic_kernel, in the place of `generic`
+    MixTileFn mix;               // ... and decim4_mix_kernel (/4 x 128 complex taps, CF32)
 };
 
 // What the geometry and launch code needs to know of a tiled kernel family (FORM_* below).  A plan has at most one, settled at
@@ -109,6 +114,9 @@ struct sxfir_plan {
     float taps_k[64];         // the first 64 taps (times 2^-31 for S32 plans) for kernels that take them by value
     void *hist_dev;        // current history: nchan * hist_len samples
     void *hist_alt;        // the tiled kernels write the next history here, then the two swap
+    float *mix_dev;        // translating plans (include/sxfir_translate.h): the rotation table, mix_den (re, im) pairs; else null
+    int mix_den, mix_num;  // ... its length (0: the plan has no mixer) and num mod den of the band centre num / den
+    int mix_s;             // ... (num * ratio) mod den: table entries per output
     KernelTable k;         // the instances this plan launches (null: none in this build for that family)
     ProfKnobs prof;        // written and read by the profiling build's hooks alone
     long long consumed, produced;
@@ -152,6 +160,13 @@ static GenericKernel generic_kernel(int kind, int oversample, int mode, int fmt)
     SXFIR_GENERIC(interp_generic_kernel, CF32, S32);
 }
 #undef SXFIR_GENERIC
+
+// Translating plans (include/sxfir_translate.h): decim_mix_generic_kernel on MixGenericArgs, the three instances of an RX kind
+static MixGenericFn mix_generic_kernel(int fmt)
+{
+    using namespace sxfir;
+    return fmt == SXFIR_CF32 ? decim_mix_generic_kernel<CF32> : fmt == SXFIR_CF16 ? decim_mix_generic_kernel<CF16> : decim_mix_generic_kernel<S32, CF32>;
+}
 
 // /8, /16, /32 with 32 taps per phase: decim_dense_kernel, non-temporal staging loads for the image rows no other tile reads
 // (NTLD = 2: both halos stay plain loads; round 4, profiles/round4h_kbench_both_halos_plain.txt: whole kernel -0.9 % at /32,
@@ -293,6 +308,9 @@ static const PlanForm FORM_ITILE = {"interp_tile_kernel", GEOM_ITILE, TILE_ITILE
 static const PlanForm FORM_ITILE_BLOCKS = {"interp_tile_kernel", GEOM_ITILE, TILE_ITILE, 64, 1, 2, false, 2, 16, TAPS_SCALED};
 // decim4_cx_kernel: complex taps, /4 x 128 on CF32, on the wide kernel's frame
 static const PlanForm FORM_CX = {"decim4_cx_kernel", GEOM_CX, 512, 64, 1, 2, true, 16, 8, TAPS_NONE};
+// decim4_mix_kernel: translating plans, /4 x 128 complex taps on CF32: decim4_cx_kernel's tile, threads, start rule (an output
+// boundary, which at /4 is a stream position that is a multiple of 4: decim_geom), store rule and generations
+static const PlanForm FORM_MIX = {"decim4_mix_kernel", GEOM_MIX, 512, 64, 1, 2, true, 16, 8, TAPS_NONE};
 // interp_cx_pass_kernel: complex taps, x4 x 128 and x8 x 256 on CF32, on the pass kernel's frame and with its tiles and generations;
 // a small call keeps four tiles per workgroup as the other complex-tap and band kernels' do (a tile is twice the pass kernel's work)
 static const PlanForm FORM_ICX = {"interp_cx_pass_kernel", GEOM_ICX, TILE_IPASS, 64, 1, 2, true, 8, 8, TAPS_PASS8_CX};
@@ -361,6 +379,11 @@ static void resolve_kernels(sxfir_plan *p)
     const GenericKernel g = generic_kernel(p->kind, p->oversample, p->mode, p->fmt);
     k.generic_name = g.name;
     k.generic = g.fn;
+    if (p->mix_den) {           // a translating plan's generic kernel has an argument struct of its own
+        k.generic_name = "decim_mix_generic_kernel";
+        k.generic = nullptr;
+        k.mix_generic = mix_generic_kernel(p->fmt);
+    }
     switch (p->form ? p->form->geom : GEOM_GENERIC) {
     case GEOM_CHAN4: k.chan4 = sxfir::chan4_kernel; break;
     case GEOM_CHAN4X2: k.chan4x2 = sxfir::chan4x2_kernel; break;
@@ -368,6 +391,7 @@ static void resolve_kernels(sxfir_plan *p)
     case GEOM_SYN4X2: k.syn4x2 = sxfir::synthesis4x2_kernel; break;
     case GEOM_RAT45: k.rat45 = sxfir::resample45_kernel; break;
     case GEOM_CX: k.cx = sxfir::decim4_cx_kernel; break;
+    case GEOM_MIX: k.mix = sxfir::decim4_mix_kernel; break;
     case GEOM_ICX: k.interp_cx = interp_cx_kernel(p->ratio); break;
     case GEOM_MULTI:
         if (!p->blocks) k.dense = dense_kernel(p->ratio, p->fmt);
@@ -394,6 +418,7 @@ static const void *occupancy_instance(const sxfir_plan *p)
     case GEOM_TILE: return (const void *)tile_kernel(p->ntaps, SXFIR_CF32);
     case GEOM_IPASS: return (const void *)interp_kernel(p->ratio < 16 ? p->ratio : 16, SXFIR_CF32, false, false);
     case GEOM_CX: return (const void *)k.cx;
+    case GEOM_MIX: return (const void *)k.mix;
     case GEOM_ICX: return (const void *)k.interp_cx;
     case GEOM_CHAN4: return (const void *)k.chan4;
     case GEOM_CHAN4X2: return (const void *)k.chan4x2;
@@ -521,6 +546,7 @@ static void free_plan(sxfir_plan *p)
     (void)hipFree(p->taps_scaled_dev);
     (void)hipFree(p->hist_dev);
     (void)hipFree(p->hist_alt);
+    (void)hipFree(p->mix_dev);
     (void)hipFree(p->join_partials);
     (void)hipFree(p->join_arrived);
     prof_free(p);
@@ -629,6 +655,11 @@ static int plan_to_device(sxfir_plan **out, sxfir_plan *p, const float *taps, si
     if (e == hipSuccess) e = hipMalloc(&p->hist_dev, hist_bytes);
     if (e == hipSuccess) e = hipMalloc(&p->hist_alt, hist_bytes);
     if (e == hipSuccess) e = hipMemset(p->hist_dev, 0, hist_bytes);
+    if (e == hipSuccess && p->mix_den) {                // a translating plan's rotation table
+        std::vector<float> w(2 * (size_t)p->mix_den);
+        (void)sxfir_design_rotator(p->mix_den, w.data());
+        e = upload(&p->mix_dev, w.data(), w.size());
+    }
     if (e == hipSuccess && p->blocks) {
         if (!p->join_tiles) p->join_tiles = 8LL * p->compute_units * p->occ;
         e = hipMalloc(&p->join_partials, (size_t)p->join_tiles * (size_t)p->blocks * 4096);

@@ -1,4 +1,4 @@
-"""Python face of the C ABI in include/sxfir.h, include/sxfir_complex.h, include/sxfir_complex_tx.h, include/sxfir_channelizer.h, include/sxfir_synthesizer.h and include/sxfir_rational.h.
+"""Python face of the C ABI in include/sxfir.h, include/sxfir_complex.h, include/sxfir_complex_tx.h, include/sxfir_channelizer.h, include/sxfir_synthesizer.h, include/sxfir_rational.h and include/sxfir_translate.h.
 
 Device memory comes either from torch (complex64 / int32 CUDA tensors, the
 current torch stream is used) or from the library's own sxfir_malloc for
@@ -63,6 +63,15 @@ def design_bandpass(ntaps, ratio, num, den, beta=8.0, gain=1.0):
     taps = np.empty(ntaps, dtype=np.complex64)
     check(lib.sxfir_design_bandpass(ntaps, ratio, beta, gain, int(num), int(den), taps.ctypes.data_as(C.c_void_p)))
     return taps
+
+
+def design_rotator(den):
+    """The rotation table of TranslatingDecimator (sxfir_design_rotator): complex64 [den], w[i] = exp(-2j pi i / den), each component
+    computed in fp64 from the integer i and rounded to float32 once."""
+    lib = load_sxfir()
+    w = np.empty(max(int(den), 0), dtype=np.complex64)
+    check(lib.sxfir_design_rotator(int(den), w.ctypes.data_as(C.c_void_p)), lib)
+    return w
 
 
 def design_rational(up, down, taps_per_phase=32, beta=8.0):
@@ -373,6 +382,36 @@ class ComplexInterpolator(Resampler):
         self.mode, self.ratio, self.nchan, self.fmt, self.ntaps = INTERPOLATE, int(ratio), int(nchan), _FMT[fmt], taps.size
         self._ck(self._lib.sxfir_create_complex_interpolator(C.byref(self._plan), taps.ctypes.data_as(C.c_void_p), taps.size,
                                                              int(ratio), int(nchan), self.fmt, int(device)))
+
+
+class TranslatingDecimator(Resampler):
+    """A frequency-translating decimator (include/sxfir_translate.h): the complex-tap decimator Resampler(DECIMATE, taps, ratio) with
+    output m turned by exp(-2j pi (m * s mod den) / den), s = num * ratio mod den, m the absolute output index -- the band centred at
+    num / den cycles per input sample (taps = design_bandpass(ntaps, ratio, num, den)) lands at 0 Hz of the output in one pass, on or
+    off the output raster.  The plan is a decimator plan with complex taps in everything else: the same methods as Resampler."""
+
+    def __init__(self, taps, ratio, num, den, nchan=1, fmt="CF32", device=-1, profiling=False):
+        self._lib = load_sxfir(profiling)
+        self.profiling = bool(profiling)
+        self._plan = C.c_void_p()
+        taps = np.ascontiguousarray(taps, dtype=np.complex64)
+        self.mode, self.ratio, self.nchan, self.fmt, self.ntaps = DECIMATE, int(ratio), int(nchan), _FMT[fmt], taps.size
+        self._ck(self._lib.sxfir_create_translating(C.byref(self._plan), taps.ctypes.data_as(C.c_void_p), taps.size, int(ratio),
+                                                    int(num), int(den), int(nchan), self.fmt, int(device)))
+
+    def _translation(self):
+        n, d = C.c_int(), C.c_int()
+        self._ck(self._lib.sxfir_plan_translation(self._plan, C.byref(n), C.byref(d)))
+        return n.value, d.value
+
+    @property
+    def num(self):
+        """The band centre's numerator, reduced into [0, den)."""
+        return self._translation()[0]
+
+    @property
+    def den(self):
+        return self._translation()[1]
 
 
 class RationalResampler(Resampler):

@@ -2,6 +2,7 @@
 
     python3 tools/cxbench.py [rx] [--log2n 28] [--iters 20] [--rounds 3]
     python3 tools/cxbench.py tx [--log2n 28] [--iters 20] [--rounds 3]
+    python3 tools/cxbench.py mix [--log2n 28] [--iters 20] [--rounds 3] [--num 123 --den 1000]
 
 2^28 resident CF32 samples, sxfir_time_decimate (HIP events around back-to-back launches).  The complex /4 x 128 plan
 (decim4_cx_kernel) and the real /4 x 128 plan (decim4_wide_kernel) are alternated on the same box, three alternations.  Per
@@ -15,6 +16,12 @@ samples, sxfir_time_interpolate; the complex plan (interp_cx_pass_kernel) and th
 (interp8_pass_kernel) alternated three times on the same box.  Per run: ms, algorithmic bytes (8 + 8 / ratio per output sample),
 TFLOP/s (real: 128 flop per output sample = 32 taps x 2 components x 2 flop; complex: 256), and per round the ratio complex / real
 -- 2.0 is "two real passes", without the combining pass those would still need.  profiles/cx_interp.txt keeps the output.
+
+`mix`: the translating /4 x 128 plan (include/sxfir_translate.h, decim4_mix_kernel) against the route it replaces at that route's
+lower bound -- per round (a) the translating plan, (b) the complex plan of the same taps (decim4_cx_kernel), (c) a device-to-device
+copy of the n / 4 output samples: 8 B read and 8 B written per output, the traffic floor of any separate rotation pass.  The
+condition is (a) < (b) + (c) in every round; (a) / (b) per round and its median say what the fused rotation costs.
+profiles/cx_mix.txt keeps the output.
 """
 import argparse
 import ctypes as C
@@ -60,12 +67,51 @@ def tx(args, n):
         del x, plans
 
 
+def mix(args, n):
+    """/4 x 128 on n resident inputs: translating plan, complex plan of the same taps, and a copy of the output."""
+    x = torch.empty(n, dtype=torch.complex64, device="cuda")
+    sxxcvr_amd.synth_fill(x, 0x51255, 0, 0)
+    y = torch.empty(n // 4, dtype=torch.complex64, device="cuda")
+    y2 = torch.empty_like(y)
+    taps = sxxcvr_amd.design_bandpass(128, 4, args.num, args.den)
+    plans = {"mix": sxxcvr_amd.TranslatingDecimator(taps, 4, args.num, args.den), "complex": sxxcvr_amd.Resampler(DECIMATE, taps, 4)}
+    for k, p in plans.items():
+        p.set_kernel(KERNEL_TILED)
+        print("%-8s %s" % (k, p.geometry(n)))
+        p.time_decimate_ptr(x.data_ptr(), n, n, y.data_ptr(), n // 4, 3)          # warm-up
+    print("band centre %d / %d: %d table entries per output" % (plans["mix"].num, plans["mix"].den, plans["mix"].num * 4 % plans["mix"].den))
+
+    def copy_ms(iters):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            y2.copy_(y)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / iters
+
+    copy_ms(3)
+    torch.cuda.synchronize()
+    ratios, ok = [], True
+    for r in range(args.rounds):
+        a = plans["mix"].time_decimate_ptr(x.data_ptr(), n, n, y.data_ptr(), n // 4, args.iters)
+        b = plans["complex"].time_decimate_ptr(x.data_ptr(), n, n, y.data_ptr(), n // 4, args.iters)
+        c = copy_ms(args.iters)
+        ratios.append(a / b)
+        ok = ok and a < b + c
+        print("round %d (a) mix %.4f ms  (b) complex %.4f ms  (c) copy of the output %.4f ms (%.3f of 8 TB/s)  (b) + (c) %.4f ms  (a) / (b) %.3f  (a) < (b) + (c): %s" % (
+            r, a, b, c, 16.0 * (n // 4) / (c * 1e-3) / 8e12, b + c, a / b, a < b + c))
+    print("median (a) / (b) %.3f; (a) < (b) + (c) in every round: %s" % (statistics.median(ratios), ok))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", nargs="?", default="rx", choices=["rx", "tx"])
+    ap.add_argument("mode", nargs="?", default="rx", choices=["rx", "tx", "mix"])
     ap.add_argument("--log2n", type=int, default=28)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--num", type=int, default=123)
+    ap.add_argument("--den", type=int, default=1000)
     args = ap.parse_args()
     n = 1 << args.log2n
     lib = sxxcvr_amd.load_sxfir()
@@ -75,6 +121,8 @@ def main():
     print("box: %s %s %s host %s" % (name.value.decode(), arch.value.decode(), bdf.value.decode(), os.uname().nodename))
     if args.mode == "tx":
         return tx(args, n)
+    if args.mode == "mix":
+        return mix(args, n)
     x = torch.empty(n, dtype=torch.complex64, device="cuda")
     sxxcvr_amd.synth_fill(x, 0x51255, 0, 0)
     y = torch.empty(n // 4, dtype=torch.complex64, device="cuda")
