@@ -120,14 +120,15 @@ def _layout(rng, nchan, n, banded, chan_mode, band_mode, nesting):
     return chan, _stride(rng, (nchan - 1) * chan + n, band_mode)
 
 
-def _make_call(rng, kind, ratio, nchan, consumed, n, request, perturb, nesting):
+def _make_call(rng, kind, ratio, nchan, consumed, n, request, perturb, nesting, n_out=None):
     """One call of n inputs.  perturb: None (an aligned output, even strides on the output side), "offset" (the output starts one
     sample in), "out_stride" / "band_stride" (that stride odd) or "any" (every placement drawn).  The input side is always drawn: a
     view `skew` samples into its buffer, strides padded by nothing, to an even or to an odd figure -- no header asks more of the
     input than one sample's alignment (sxfir_channelizer.hip.h / sxfir_synthesizer.hip.h: "buffers must be aligned to one complex
-    sample"; sxfir_synthesizer.h: "an odd in_stride or band_stride stays with the tiled kernel")."""
-    K = KINDS[kind]
-    n_out = outputs_for(kind, ratio, consumed, n)
+    sample"; sxfir_synthesizer.h: "an odd in_stride or band_stride stays with the tiled kernel").  n_out: the call's outputs where
+    the kind is not one of KINDS (tests/rate_cases.py: `kind` is then a Kind of its own, without bands on either side)."""
+    K = KINDS[kind] if n_out is None else kind
+    n_out = outputs_for(kind, ratio, consumed, n) if n_out is None else n_out
     modes = ("tight", "even", "odd")
     out_off = 0
     chan_mode, band_mode = "even", "even"

@@ -231,6 +231,105 @@ def test_odd_stride_and_offset_output(oracle):
     same(rig.call(plan, 4 * 50 + 1, n - 4 * 50 - 1, GENERIC), ref[:, k1:], "the call after the refused one")
 
 
+# ---- more tiles than waves: the tile loop's second iteration ----------------------------------------------------------------------
+WALK_SEED = 0x3A1C
+
+
+def _walk(oracle, num, den, nchan=1, where=0):
+    """One tiled call of 3 tiles and 140 samples more than the grid has waves (per channel), so that four waves walk on to a second
+    tile -- `tile_ph += stride_step` and its wrap, the next tile's staging over an image the stores have just read -- and the wave
+    that carries the history over owns two tiles.  FORM_MIX has the heavy prologue: a call this small is dealt as one generation,
+    the grid per channel is resident / nchan.  The whole call is compared on the GPU with the plan's generic kernel over the same
+    input (the sweep holds that one to the oracle); five windows of 200 outputs and the whole of a second tiled call of TILE + 8
+    samples are compared with the oracle's reference, from inputs regenerated for each window alone.  Returns the first call's
+    geometry and size."""
+    import torch
+    lead = 256 if where else 0                                  # (a placed plan: the samples in front are its history)
+    assert where % 4 == 0 and lead % 4 == 0
+    plans = [plan4(H4, num, den, k, nchan) for k in (KERNEL_TILED, KERNEL_GENERIC)]
+    contract = plans[0].contract
+    per = plans[0].geometry(TILE)["resident"] // nchan
+    n, n2 = (per + 3) * TILE + 140, TILE + 8
+    x = torch.empty((nchan, lead + n + n2), dtype=torch.complex64, device="cuda")
+    sxxcvr_amd.synth_fill(x, WALK_SEED, 40, 0)
+    stream = torch.cuda.current_stream().cuda_stream
+    for plan in plans:
+        if where:
+            plan.set_history_ptr(x.data_ptr(), lead, x.stride(0), stream)
+            plan.set_position(where)
+        assert plan.position == (where, where // 4)
+    g = plans[0].geometry(n)
+    G = g["workgroups"] // nchan                                # waves per channel: the first tile a wave reaches in its second iteration
+    assert g["kernel"] == TILED and g["tiled"] and g["tile_samples"] == TILE and g["n_tiles"] == per + 4, g
+    assert G < g["n_tiles"] and G == per, "no wave walks to a second tile: %r" % (g,)
+    assert plans[1].geometry(n)["kernel"] == GENERIC
+
+    def call(plan, pos, count):
+        """sxfir_decimate over inputs [pos, pos + count) of the stream, between guards of fill: the rows as int32 [nchan, row, 2]"""
+        n_out = count // 4
+        row = 2 * GUARD + n_out + n_out % 2
+        buf = torch.full((nchan, row, 2), _i32(FILL), dtype=torch.int32, device="cuda")
+        c0, p0 = plan.position
+        assert plan.outputs_for(count) == n_out
+        assert plan.process_ptr(x.data_ptr() + 8 * (lead + pos), count, x.stride(0), buf.data_ptr() + 8 * GUARD, row, stream) == n_out
+        assert plan.position == (c0 + count, p0 + n_out)
+        assert bool((buf[:, :GUARD] == _i32(FILL)).all()) and bool((buf[:, GUARD + n_out:] == _i32(FILL)).all()), "the guard around the outputs was written"
+        return buf, n_out
+
+    def window(c, m0, cnt):
+        """[cnt, 2] words of outputs [m0, m0 + cnt) of the stream (its first output: the absolute where / 4), channel c"""
+        pre = min(128, lead + 4 * m0)                           # samples in front of the window: the filter's reach, or all there are
+        assert pre == 128 or (pre == 4 * m0 and lead == 0)
+        xw = oracle.synth_iq(WALK_SEED, 40 + c, lead + 4 * m0 - pre, pre + 4 * cnt)
+        return mix_ref(oracle, H4, 4, xw, contract, num, den, where // 4 + m0 - pre // 4)[pre // 4:].view(np.uint32).reshape(cnt, 2)
+
+    got, n_out = call(plans[0], 0, n)
+    other, _ = call(plans[1], 0, n)
+    torch.cuda.synchronize()
+    assert torch.equal(got, other), "the tiled and the generic kernel differ: first at output %d of channel %d" % (
+        int((got != other).any(dim=2).nonzero()[0, 1]) - GUARD, int((got != other).any(dim=2).nonzero()[0, 0]))
+    starts = {"the stream's start": 0, "the first tile of a second iteration": G * 512, "the seam in front of it": G * 512 - 100,
+              "the middle": n_out // 2 + 3, "the last, ragged tile": n_out - 200}
+    assert n_out % 512 == 35
+    for what, m0 in starts.items():
+        for c in range(nchan):
+            same(got[c, GUARD + m0:GUARD + m0 + 200].cpu().numpy().view(np.uint32), window(c, m0, 200), "%s, channel %d" % (what, c))
+    # the history was carried over by a wave that owned more than one tile
+    assert (g["n_tiles"] - 1) % G < g["n_tiles"] - G
+    assert plans[0].geometry(n2)["kernel"] == TILED
+    second, n_out2 = call(plans[0], n, n2)
+    torch.cuda.synchronize()
+    for c in range(nchan):
+        same(second[c, GUARD:GUARD + n_out2].cpu().numpy().view(np.uint32), window(c, n_out, n_out2), "the call after it, channel %d" % c)
+    print("%d/%d x %d ch from %d: resident %d, grid %d per channel, %d tiles, %d samples" % (num, den, nchan, where, g["resident"], G, g["n_tiles"], n))
+    return g, n
+
+
+@pytest.mark.parametrize("num,den,s", [(3, 7, 5), (65535, 65536, 65532), (65534, 65535, 65531), (1, 3, 1)])
+def test_more_tiles_than_resident_workgroups(oracle, num, den, s):
+    """One channel: the grid is the chip's resident waves, a multiple of 8 -- the XCD-blocked dealing (w8 != 0).  (3, 7) and (1, 3):
+    more tiles than table entries, so `tile % den` wraps for an s that is not 0, and a lane's index wraps inside its eight reads;
+    (65535, 65536) and (65534, 65535): s at the top of the table (the largest /4 allows; den - 4 on the odd den)."""
+    assert step(num, den, 4) == s
+    g, n = _walk(oracle, num, den)
+    assert g["workgroups"] == g["resident"] and g["resident"] % 8 == 0, g
+    assert den > 8 or g["n_tiles"] > den
+
+
+def test_more_tiles_than_workgroups_three_channels(oracle):
+    """Three channels (or the count in 2..5 that does it): the grid per channel is no multiple of 8, so the tiles are dealt plainly
+    strided (w8 = 0)."""
+    resident = plan4(H4, 123, 1000).geometry(TILE)["resident"]
+    nchan = next(c for c in (3, 2, 4, 5) if (resident // c) % 8 and (resident // c * c) % 8)
+    g, n = _walk(oracle, 123, 1000, nchan=nchan)
+    assert (g["workgroups"] // nchan) % 8 != 0 and g["workgroups"] % 8 != 0, g
+
+
+def test_more_tiles_than_resident_workgroups_far(oracle):
+    """The same many-tile call on a plan placed at input 2^40 + 20: the call's phase comes from a 64-bit position."""
+    _walk(oracle, 12345, 65536, where=(1 << 40) + 20)
+
+
 # ---- the generic kernel at the shapes and formats without a tiled one ----------------------------------------------------------
 @pytest.mark.parametrize("ntaps,D,fmt,contract", [(256, 8, "CF32", (2, 4, 0)), (35, 5, "CF32", (1, 5, 0)), (1536, 48, "CF32", (2, 4, 1)),
                                                   (128, 4, "CF16", (2, 4, 0)), (128, 4, "S32", (2, 4, 0))])

@@ -224,6 +224,107 @@ def test_tiled_odd_output_stride(oracle):
     same(rig.call(plan, 0, n, TILED), ref, "the call after the refused one")
 
 
+# ---- 6b. more tiles than waves: the tile loop's second iteration -------------------------------------------------------------
+WALK_SEED = 0x45A7
+
+
+def _walk(oracle, nchan=1, where=0):
+    """One tiled call of 3 tiles and 35 samples more than the grid has waves (per channel), so that four waves walk on to a second
+    tile -- the next tile's staging lands on an image the transposed stores have just read -- and the wave that carries the history
+    over owns two tiles.  FORM_RAT45 has no heavy prologue: the grid is the plan's generations of resident waves, shared among the
+    channels, whatever the call's size; geometry() of a very long call tells it.  The whole call is compared on the GPU with
+    the plan's generic kernel over the same input (the sweep holds that one to the oracle); five windows of 200 outputs and the
+    whole of a second tiled call of TILE + 8 samples are compared with the oracle's reference, from inputs regenerated for each
+    window alone.  Returns the first call's geometry and size."""
+    import torch
+    h = rational_taps(4, 32)
+    lead = 40 if where else 0                                   # (a placed plan: the samples in front are its history)
+    assert where % 5 == 0 and lead % 5 == 0
+    plans = [plan45(h, k, nchan) for k in (KERNEL_TILED, KERNEL_GENERIC)]
+    per = plans[0].geometry(TILE << 20)["workgroups"] // nchan
+    n, n2 = (per + 3) * TILE + 35, TILE + 8
+    x = torch.empty((nchan, lead + n + n2), dtype=torch.complex64, device="cuda")
+    sxxcvr_amd.synth_fill(x, WALK_SEED, 50, 0)
+    stream = torch.cuda.current_stream().cuda_stream
+    for plan in plans:
+        if where:
+            plan.set_history_ptr(x.data_ptr(), lead, x.stride(0), stream)
+            plan.set_position(where)
+        assert plan.position == (where, where // 5 * 4)
+    g = plans[0].geometry(n)
+    G = g["workgroups"] // nchan                                # waves per channel: the first tile a wave reaches in its second iteration
+    assert g["kernel"] == TILED and g["tiled"] and g["tile_samples"] == TILE and g["n_tiles"] == per + 4, g
+    assert G < g["n_tiles"] and G == per, "no wave walks to a second tile: %r" % (g,)
+    assert plans[1].geometry(n)["kernel"] == GENERIC
+
+    def call(plan, pos, count):
+        """sxfir_resample over inputs [pos, pos + count) of the stream (pos a multiple of 5), between guards of fill: the rows as
+        int32 [nchan, row, 2]"""
+        n_out = n_out_for(count, 4, 5)
+        row = 2 * GUARD + n_out + n_out % 2
+        buf = torch.full((nchan, row, 2), _i32(FILL), dtype=torch.int32, device="cuda")
+        c0, p0 = plan.position
+        assert plan.outputs_for(count) == n_out
+        assert plan.process_ptr(x.data_ptr() + 8 * (lead + pos), count, x.stride(0), buf.data_ptr() + 8 * GUARD, row, stream) == n_out
+        assert plan.position == (c0 + count, p0 + n_out)
+        assert bool((buf[:, :GUARD] == _i32(FILL)).all()) and bool((buf[:, GUARD + n_out:] == _i32(FILL)).all()), "the guard around the outputs was written"
+        return buf, n_out
+
+    def window(c, m0, cnt):
+        """[cnt, 2] words of outputs [m0, m0 + cnt) of the stream, m0 a multiple of 4 (a period's first), channel c: output 4 q + p
+        reads inputs 5 q + p - 31 .. 5 q + p"""
+        assert m0 % 4 == 0
+        at = 5 * (m0 // 4)
+        pre = min(35, lead + at)                                # whole periods in front of the window: the filter's reach, or all there are
+        assert pre == 35 or (pre == at and lead == 0)
+        count = min(5 * (cnt + 3) // 4 + 2, n + n2 - at)
+        xw = oracle.synth_iq(WALK_SEED, 50 + c, lead + at - pre, pre + count)
+        skip = pre // 5 * 4
+        ref = rational_ref(oracle, h, 4, 5, xw, 2)[skip:skip + cnt]
+        assert ref.size == cnt
+        return ref.view(np.uint32).reshape(cnt, 2)
+
+    got, n_out = call(plans[0], 0, n)
+    other, _ = call(plans[1], 0, n)
+    torch.cuda.synchronize()
+    assert torch.equal(got, other), "the tiled and the generic kernel differ: first at output %d of channel %d" % (
+        int((got != other).any(dim=2).nonzero()[0, 1]) - GUARD, int((got != other).any(dim=2).nonzero()[0, 0]))
+    assert n_out == (per + 3) * 1024 + 28
+    starts = {"the stream's start": 0, "the first tile of a second iteration": G * 1024, "the seam in front of it": G * 1024 - 100,
+              "the middle": n_out // 2 // 4 * 4 + 4, "the last, ragged tile": n_out - 200}
+    for what, m0 in starts.items():
+        for c in range(nchan):
+            same(got[c, GUARD + m0:GUARD + m0 + 200].cpu().numpy().view(np.uint32), window(c, m0, 200), "%s, channel %d" % (what, c))
+    # the history was carried over by a wave that owned more than one tile
+    assert (g["n_tiles"] - 1) % G < g["n_tiles"] - G
+    assert plans[0].geometry(n2)["kernel"] == TILED
+    second, n_out2 = call(plans[0], n, n2)
+    torch.cuda.synchronize()
+    for c in range(nchan):
+        same(second[c, GUARD:GUARD + n_out2].cpu().numpy().view(np.uint32), window(c, n_out, n_out2), "the call after it, channel %d" % c)
+    print("4/5 x %d ch from %d: resident %d, grid %d per channel, %d tiles, %d samples" % (nchan, where, g["resident"], G, g["n_tiles"], n))
+    return g, n
+
+
+def test_more_tiles_than_resident_workgroups(oracle):
+    """One channel: the grid, whole generations of the chip's resident waves, is a multiple of 8 -- the XCD-blocked dealing."""
+    g, n = _walk(oracle)
+    assert g["workgroups"] % g["resident"] == 0 and g["workgroups"] % 8 == 0, g
+
+
+def test_more_tiles_than_workgroups_plainly_strided(oracle):
+    """The smallest channel count above one whose share of the grid is no multiple of 8: the tiles are dealt plainly strided."""
+    grid = plan45(rational_taps(4, 32)).geometry(TILE << 20)["workgroups"]
+    nchan = next(c for c in range(2, 64) if (grid // c) % 8)
+    g, n = _walk(oracle, nchan=nchan)
+    assert (g["workgroups"] // nchan) % 8 != 0, g
+
+
+def test_more_tiles_than_resident_workgroups_far(oracle):
+    """The same many-tile call on a plan placed at input 5 (2^40 + 3): a start on the period that is no small multiple of 5."""
+    _walk(oracle, where=5 * ((1 << 40) + 3))
+
+
 # ---- 7. without the oracle: every down-th output of the interpolator plan --------------------------------------------------
 @pytest.mark.parametrize("fmt", ["CF32", "CF16"])
 @pytest.mark.parametrize("up,down,T", [(4, 5, 32), (3, 4, 8)])

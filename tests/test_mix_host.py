@@ -150,6 +150,73 @@ def test_reference_against_fp64(oracle, ntaps, ratio, num, den):
                           rotate_f32(z, design_rotator(den), 0, step(num, den, ratio), den).view(np.uint32))
 
 
+def tile_walk_model(num, den, n_waves, w8, n_tiles, phase=0):
+    """decim4_mix_kernel's table indices, every step as the code takes it, all waves of a grid side by side (int64 arrays, one row
+    per wave): mix_tile_args' three steps (sxfir_launch.hip.h), then per wave the first tile's phase -- the kernel's two divisions
+    --, the lane's offset, and the add-and-subtract walk over (tile, lane, i).  Returns the indices [n_tiles, 512] and the largest
+    intermediate value met; asserts that every value a 32-bit register holds stays below 2^32, every index below den, and that
+    every tile is one wave's."""
+    s = step(num, den, 4)
+    lane_step = 8 * s % den
+    tile_step = 512 * s % den
+    stride_step = n_waves % den * tile_step % den
+    top = 0
+
+    def u32(v):
+        nonlocal top
+        assert v.min() >= 0 and v.max() < 2 ** 32, int(v.max())
+        top = max(top, int(v.max()))
+        return v
+
+    def wrap(v):                                                # if (v >= den) v -= den
+        return v - den * (v >= den)
+
+    b = np.arange(n_waves, dtype=np.int64)
+    tile = (b & 7) * w8 + (b >> 3) if w8 else b.copy()          # wide_first_tile: XCD-blocked, or plain strided dealing
+    lane = np.arange(64, dtype=np.int64)
+    lane_ph = u32(lane * lane_step) % den
+    tile_ph = wrap(u32(phase + u32(u32(tile % den) * tile_step) % den))
+    out = np.full((n_tiles, 512), -1, dtype=np.int64)
+    while (tile < n_tiles).any():
+        live = tile < n_tiles                                   # (a wave past the last tile has left the loop)
+        assert (out[tile[live]] == -1).all(), "two waves own one tile"
+        idx = wrap(u32(tile_ph[:, None] + lane_ph[None, :]))
+        for i in range(8):
+            assert idx[live].max() < den
+            out[tile[live][:, None], (8 * lane + i)[None, :]] = idx[live]
+            idx = wrap(u32(idx + s))
+        tile = tile + n_waves
+        tile_ph = wrap(u32(tile_ph + stride_step))
+    assert (out >= 0).all(), "a tile is no wave's"
+    return out, top
+
+
+def test_the_tile_walk_arithmetic_stays_in_32_bits_and_hits_the_table_index():
+    """The three steps mix_tile_args hands decim4_mix_kernel and the kernel's walk, modelled step by step (tile_walk_model), against
+    mix_cases.table_index for every mixer of the sweep's menu at /4: grids of 1, 3, 8 and 512 waves, XCD-blocked (w8 = waves / 8)
+    and plainly strided (w8 = 0), over 3 waves + 3 tiles, so that every wave walks to a third tile and three to a fourth, from a first
+    output at 0, at den - 1 and near 2^40.  What the kernel's comments claim -- "no sum reaches 2^17", "65535^2 < 2^32" -- holds: no
+    intermediate value leaves 32 bits, no index reaches den."""
+    import rate_cases as rc
+    worst = 0
+    for cls, den, num in rc.MIXERS + (("tile walk", 7, 3), ("tile walk", 3, 1)):
+        num = rc.mixer_num(cls, den, num, 4)
+        s = step(num, den, 4)
+        for n_waves in (1, 3, 8, 512):
+            for w8 in sorted({0, n_waves // 8 if n_waves % 8 == 0 else 0}):
+                n_tiles = 3 * n_waves + 3
+                for m_first in (0, den - 1, (1 << 40) + 77):
+                    phase = m_first % den * s % den                             # mixer_of (sxfir_launch.hip.h)
+                    got, top = tile_walk_model(num, den, n_waves, w8, n_tiles, phase)
+                    worst = max(worst, top)
+                    want = table_index(m_first, 512 * n_tiles, s, den).reshape(n_tiles, 512)
+                    bad = np.nonzero((got != want).any(axis=1))[0]
+                    assert bad.size == 0, "den %d num %d, %d waves, w8 %d, from %d: tile %d" % (den, num, n_waves, w8, m_first, bad[0])
+    print("largest intermediate value: %d (2^32 = %d)" % (worst, 2 ** 32))
+    # the one product the grids above keep small, (tile mod den) tile_step of a wave's first tile, at its largest: den - 1 each
+    assert worst < 2 ** 32 and 65535 * 65535 < 2 ** 32 and 63 * 65535 < 2 ** 32
+
+
 def test_shipped_code_object_of_the_mix_kernels():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import shipped_isa

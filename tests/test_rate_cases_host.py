@@ -1,0 +1,223 @@
+"""tests/rate_cases.py on the CPU: the generator covers what the GPU sweep (tests/test_gpu_rate_sweep.py) is there for, its draws
+are calls the entry points accept, the predictor says what the headers say, and the reference of a PLACED stream is the fp64
+definition at the true 64-bit position, numerically, before any kernel runs."""
+import collections
+import math
+
+import numpy as np
+import pytest
+
+import rate_cases as rc
+from band_cases import AUTO, CX_RATIOS, GENERIC, TILED, Call
+from mix_cases import bound as mix_bound, mix_f64, step
+from rate_cases import KINDS, SWEEP_COUNT, SWEEP_SEED
+from rational_cases import bound as rational_bound, n_out_for, rational_f64
+
+
+def _labels(kind, case):
+    return [rc.expected_kernel(kind, case, i) for i in range(len(case.calls))]
+
+
+def coverage(kind, cases):
+    """The counts the conditions below are about: cases, unless the name says calls."""
+    c = collections.Counter()
+    for case in cases:
+        labels = _labels(kind, case)
+        form = rc.has_form(kind, case)
+        produced = [x for x in labels if x != "history only"]
+        c["calls"] += len(labels)
+        for x in ("tiled", "generic", "history only", "refused"):
+            c["%s calls" % x] += labels.count(x)
+        c[case.fmt] += 1
+        c["%d ch" % case.nchan] += 1
+        if case.style == "seam":
+            c["seam by %s" % case.how] += any(produced[i:i + 3] == ["tiled", "generic", "tiled"] for i in range(len(produced) - 2))
+        c["CF16 placed"] += case.fmt == "CF16" and case.place != "start"
+        c["3 ch with a seam"] += case.nchan == 3 and case.style == "seam"
+        c["refused in mid-stream on an odd stride"] += any(x == "refused" and form and 0 < i and call.out_stride % 2 == 1 and case.nchan > 1
+                                                           for i, (x, call) in enumerate(zip(labels, case.calls)))
+        if case.place != "start":
+            c["placed"] += 1
+            c["place %s" % case.place] += 1
+            if form:
+                c["placed, start rule %s" % ("kept" if case.c0 % KINDS[kind].start_multiple == 0 else "broken")] += 1
+        for index, log2, i in rc.crossings(case):
+            c["%s passes 2^%d" % (index, log2)] += 1
+            c["%s passes 2^%d in a %s call" % (index, log2, labels[i])] += 1
+        if kind == "translate":
+            c["den %d" % case.den] += 1
+            for cls in rc.s_classes(case):
+                c[cls] += 1
+            c["den below 8 on the tiled kernel"] += case.den < 8 and "tiled" in labels
+        else:
+            c["pair %d/%d" % (case.up, case.down)] += 1
+            c["odd taps per phase"] += rc.hist_of(case) % 2 == 1
+    return c
+
+
+def needed(kind):
+    """What must occur in at least one case (for "... calls": in one call)."""
+    need = ["tiled calls", "generic calls", "history only calls", "refused calls", "1 ch", "2 ch", "3 ch", "CF16 placed", "3 ch with a seam",
+            "refused in mid-stream on an odd stride", "placed, start rule kept", "placed, start rule broken"]
+    need += sorted(set(KINDS[kind].formats)) + ["seam by %s" % how for how in rc.SEAMS] + ["place %s" % p for p in rc.PLACES[kind]]
+    need += ["%s passes 2^%s" % tuple(p.split()) for p in rc.PLACES[kind] if p != "far"]
+    if kind == "translate":
+        need += ["den %d" % d for d in rc.DENS]
+        need += ["s = den - gcd, den 65535", "s = den - gcd, den 65536", "s = 1", "s = 0", "negative num", "num above den", "den below 8 on the tiled kernel"]
+    else:
+        need += ["pair %d/%d" % p for p in rc.RATIONAL_PAIRS] + ["odd taps per phase"]
+    return need
+
+
+@pytest.mark.parametrize("kind", list(KINDS))
+def test_the_sweep_covers_what_it_is_for(kind):
+    cases = rc.cases(kind, SWEEP_SEED, SWEEP_COUNT)
+    assert len(cases) == SWEEP_COUNT and len({c.ident for c in cases}) == SWEEP_COUNT
+    assert cases == rc.cases(kind, SWEEP_SEED, SWEEP_COUNT), "the generator is a function of its seed"
+    c = coverage(kind, cases)
+    print("%s, seed %d: %s" % (kind, SWEEP_SEED, ", ".join("%s %d" % (k, c[k]) for k in sorted(c))))
+    missing = [what for what in needed(kind) if c[what] < 1]
+    assert not missing, missing
+    # band_cases' deck
+    assert c["CF32"] == 22 and c["placed"] == 12 and sum(rc.has_form(kind, x) for x in cases) == 11, c
+    assert sum(x.style == "seam" for x in cases) == 4 and sum(x.style == "clean" for x in cases) == 7, c
+    assert c["placed, start rule kept"] == 2 and c["placed, start rule broken"] == 2, c
+    # at most a quarter of all calls compute nothing
+    assert 4 * (c["refused calls"] + c["history only calls"]) <= c["calls"], c
+    if kind == "translate":
+        # the mixer at its limits: num 65535 at /4 on den 65536 has s = 65532, as the tiled kernel's comments count on
+        assert rc.mixer_num("max", 65536, None, 4) == 65535 and step(65535, 65536, 4) == 65532
+        assert step(rc.mixer_num("max", 65535, None, 4), 65535, 4) == 65534 and step(rc.mixer_num("one", 65535, None, 4), 65535, 4) == 1
+        for x in cases:
+            assert 0 <= step(x.num, x.den, x.down) < x.den <= 65536, x.ident
+
+
+@pytest.mark.parametrize("kind", list(KINDS))
+def test_every_draw_is_a_call_the_entry_point_accepts(kind):
+    """The argument checks of sxfir_create_translating / sxfir_create_rational and of sxfir_decimate / sxfir_resample (check_buffers),
+    restated: legal shapes and formats, a stream of six tiles at the most, strides that hold the block, a position that
+    sxfir_set_position takes and whose product with `up` stays below 2^62, a lead that sxfir_set_history takes."""
+    K = KINDS[kind]
+    for case in rc.cases(kind, SWEEP_SEED, SWEEP_COUNT):
+        assert case.fmt in K.formats and case.nchan in (1, 2, 3) and 1 <= len(case.calls) <= 6, case.ident
+        if kind == "translate":
+            assert case.up == 1 and case.down in CX_RATIOS and 4 <= case.ntaps <= 300 and 1 <= case.den <= 65536, case.ident
+            assert -2 ** 31 <= case.num < 2 ** 31, case.ident
+        else:
+            assert case.fmt != "S32" and (case.num, case.den) == (0, 0), case.ident
+            assert 2 <= case.up <= 4096 and 2 <= case.down <= 4096 and math.gcd(case.up, case.down) == 1, case.ident
+            assert case.ntaps % case.up == 0 and 1 <= case.ntaps // case.up <= 40, case.ident
+            assert ((case.up, case.down) in rc.RATIONAL_PAIRS), case.ident
+        assert 0 < sum(call.n for call in case.calls) <= 6 * K.tile, case.ident
+        assert 0 <= case.c0 and (case.c0 + 6 * K.tile) * case.up < 2 ** 62, case.ident
+        assert (case.c0 == 0) == (case.place == "start"), case.ident
+        lead = rc.lead_of(case)
+        assert (lead == 0 and case.c0 == 0) or (rc.hist_len(case) <= lead <= case.c0 and (case.c0 - lead) % case.down == 0), case.ident
+        assert rc.hist_len(case) >= rc.hist_of(case) >= 1
+        pos = case.c0
+        for call in case.calls:
+            n_out = n_out_for(call.n, case.up, case.down, pos)
+            pos += call.n
+            assert call.request in (AUTO, TILED, GENERIC) and call.out_off in (0, 1) and call.skew >= 0 and call.band_stride == 0, case.ident
+            assert call.in_stride >= call.n and call.out_stride >= n_out, (case.ident, call)
+
+
+def test_the_predictor_on_hand_made_calls():
+    """The headers' rules on calls written out by hand: every reason to leave the tiled kernel, both start rules, from the stream's
+    start and from a placed position."""
+    def case(kind, calls, fmt="CF32", nchan=2, c0=0, shape=None):
+        ntaps, up, down = shape or KINDS[kind].tiled_shape
+        return rc.Case("hand", ntaps, up, down, 3, 7, 0, nchan, fmt, 0, "hand", None, "start" if c0 == 0 else "far", c0, tuple(calls))
+
+    def call(n, request=AUTO, out_off=0, out_stride=4096):
+        return Call(n, request, out_off, out_stride, 0, 4096, 0, "bands inside channels")
+
+    for kind in KINDS:
+        q = KINDS[kind].start_multiple
+        one = lambda *a, **kw: rc.expected_kernel(kind, case(kind, [call(*a, **kw)]), 0)                          # noqa: E731
+        assert one(640) == "tiled"                                                                                  # 1
+        assert one(640, GENERIC) == "generic"                                                                       # 2
+        assert one(640, out_off=1) == "generic" and one(640, TILED, out_off=1) == "refused"                         # 3, 4
+        assert rc.expected_kernel(kind, case(kind, [call(640, TILED, out_off=1)]), 0, request=AUTO) == "generic"    # 5
+        assert rc.expected_kernel(kind, case(kind, [call(640, TILED, out_off=1)]), 0, assume_aligned=True) == "tiled"           # 6
+        assert one(640, out_stride=4097) == "generic"                                                               # 7
+        assert rc.expected_kernel(kind, case(kind, [call(640, out_stride=4097)], nchan=1), 0) == "tiled"            # 8
+        assert rc.expected_kernel(kind, case(kind, [call(640)], fmt="CF16"), 0) == "generic"                        # 9
+        assert rc.expected_kernel(kind, case(kind, [call(640, TILED)], fmt="CF16"), 0) == "refused"                 # 10
+        assert one(0, TILED) == "history only"                                                                      # 11
+        # a placed stream: the rule is about the ABSOLUTE position
+        for c0, want in ((q * (2 ** 40 + 3), "tiled"), (q * 2 ** 40 + 1, "generic"), (2 ** 31, "tiled" if 2 ** 31 % q == 0 else "generic")):
+            assert rc.expected_kernel(kind, case(kind, [call(640)], c0=c0), 0) == want, (kind, c0)                   # 12, 13, 14
+        assert rc.expected_kernel(kind, case(kind, [call(640, TILED)], c0=q * 2 ** 40 + 1), 0) == "refused"         # 15
+    # translate, /4: 5 samples make 2 outputs and leave the stream one past a boundary; 2 more complete none; 1 brings it back
+    c = case("translate", [call(5), call(2), call(2, TILED), call(3), call(512, TILED)])
+    assert [rc.expected_kernel("translate", c, i) for i in range(5)] == ["tiled", "history only", "refused", "history only", "tiled"]
+    # rational, 4/5: ceil(4 c / 5) outputs exist after c inputs -- 5, 8, 12, 12, 13, 525, 528, 529 after 6, 10, 14, 15, 16, 656, 660,
+    # 661: the fifth input of every period (14) completes none, and the calls at 10, 15 and 660 start on the period
+    c = case("rational", [call(6), call(4, TILED), call(4), call(1, TILED), call(1), call(640, TILED), call(4), call(1)])
+    assert [n_out_for(x.n, 4, 5, rc.position_before(c, i)) for i, x in enumerate(c.calls)] == [5, 3, 4, 0, 1, 512, 3, 1]
+    assert [rc.expected_kernel("rational", c, i) for i in range(8)] == ["tiled", "refused", "tiled", "history only", "tiled", "refused", "generic", "tiled"]
+    # a shape without a tiled kernel
+    assert rc.expected_kernel("translate", case("translate", [call(640, TILED)], shape=(64, 1, 4)), 0) == "refused"
+    assert rc.expected_kernel("rational", case("rational", [call(640)], shape=(64, 4, 5)), 0) == "generic"
+    assert rc.expected_kernel("rational", case("rational", [call(1)], shape=(24, 3, 8), c0=1), 0) == "history only"
+
+
+def test_crossings_on_hand_made_streams():
+    def case(up, down, c0, sizes):
+        calls = tuple(Call(n, AUTO, 0, 4096, 0, 4096, 0, "bands inside channels") for n in sizes)
+        return rc.Case("hand", 128, up, down, 0, 0, 0, 1, "CF32", 0, "hand", None, "far", c0, calls)
+
+    assert rc.crossings(case(1, 4, 2 ** 31 - 10, [10, 10])) == set()                       # the mark lies between two calls
+    assert rc.crossings(case(1, 4, 2 ** 31 - 10, [5, 10])) == {("input", 31, 1)}
+    assert rc.crossings(case(1, 4, 4 * 2 ** 32 - 4, [4, 8])) == set()                      # output 2^32 - 1 in one call, 2^32 in the next
+    assert rc.crossings(case(1, 4, 4 * 2 ** 32 - 8, [4, 8])) == {("output", 32, 1)}       # outputs 2^32 - 1 (input 2^34 - 4) and 2^32
+    assert rc.crossings(case(1, 4, 4 * 2 ** 32, [8])) == set()
+    # 4/5: output m belongs to input floor(5 m / 4); m = ceil(2^31 / 5) = 429496730 is the first with 5 m >= 2^31, its input 536870912
+    assert rc.crossings(case(4, 5, 536870911, [2])) == {("raster", 31, 0)}
+    assert rc.crossings(case(4, 5, 536870912, [2])) == set()
+
+
+@pytest.mark.parametrize("kind", list(KINDS))
+def test_the_placed_reference_is_the_plain_one_at_the_lead(oracle, kind):
+    """At c0 = lead the placed stream IS the tail of one pass from zero history: the same bits, the lead's outputs dropped."""
+    for case in [c for c in rc.cases(kind, SWEEP_SEED, SWEEP_COUNT) if c.place != "start"][:4]:
+        lead = rc.lead_of(case)
+        near = case._replace(c0=lead)
+        assert rc.lead_of(near) == lead
+        h = rc.taps_of(kind, case)
+        raw, xs = rc.stream_input(kind, case, oracle)
+        whole = rc.plain_reference(kind, oracle, case, h, xs[0])
+        got = rc.reference(kind, oracle, near, h, xs[0])
+        assert got.size == n_out_for(xs.shape[1] - lead, case.up, case.down, lead) and got.size == whole.size - n_out_for(lead, case.up, case.down)
+        assert np.array_equal(got.view(np.uint32), whole[whole.size - got.size:].view(np.uint32)), case.ident
+        if kind == "translate" and (case.c0 - lead) // case.down * step(case.num, case.den, case.down) % case.den:
+            far = rc.reference(kind, oracle, case, h, xs[0])
+            assert far.shape == got.shape and not np.array_equal(far.view(np.uint32), got.view(np.uint32)), "the far phase is not the near one"
+
+
+@pytest.mark.parametrize("kind", list(KINDS))
+def test_the_placed_reference_is_the_fp64_definition(oracle, kind):
+    """Three placed cases per kind, channel 0: the float32 reference the GPU is compared with bit for bit against the header's formula
+    in fp64 with the TRUE absolute index of the first output -- mix_cases.mix_f64 / rational_cases.rational_f64 over the lead and the
+    stream, the lead's outputs dropped -- within the project's bounds (mix_cases.bound, rational_cases.bound)."""
+    placed = [c for c in rc.cases(kind, SWEEP_SEED, SWEEP_COUNT) if c.place != "start"]
+    assert len(placed) >= 3
+    for case in placed[:3]:
+        lead = rc.lead_of(case)
+        h = rc.taps_of(kind, case)
+        raw, xs = rc.stream_input(kind, case, oracle)
+        x = xs[0]
+        got = rc.reference(kind, oracle, case, h, x).astype(np.complex128)
+        skip = n_out_for(lead, case.up, case.down)
+        if kind == "translate":
+            m_true = -(-case.c0 // case.down)                                   # ceil(c0 / ratio): sxfir_set_position's `produced`
+            want = mix_f64(h, case.down, case.num, case.den, x, m_true - skip)[skip:]
+            b = mix_bound(h, x, want)
+        else:
+            want = rational_f64(h, case.up, case.down, x)[skip:]
+            b = np.full(want.shape, rational_bound(h, x))
+        assert got.shape == want.shape and got.size > 0, case.ident
+        err = np.maximum(np.abs(got.real - want.real), np.abs(got.imag - want.imag)) if kind == "translate" else np.abs(got - want)
+        print("%s %s from %d: worst error %.3g, bound there %.3g" % (kind, case.ident, case.c0, err.max(), b[err.argmax()]))
+        assert np.all(err <= b), case.ident
