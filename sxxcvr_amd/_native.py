@@ -156,6 +156,10 @@ def load_sxfir(profiling=False):
         "sxfir_design_rotator": (ci, [ci, vp]),
         "sxfir_create_translating": (ci, [P(vp), vp, ci, ci, ci, ci, ci, ci, ci]),
         "sxfir_plan_translation": (ci, [vp, P(ci), P(ci)]),
+        # include/sxfir_translate_tx.h: frequency-translating interpolators
+        "sxfir_translate_tx_abi_version": (ci, []),
+        "sxfir_create_translating_interpolator": (ci, [P(vp), vp, ci, ci, ci, ci, ci, ci, ci]),
+        "sxfir_plan_translation_tx": (ci, [vp, P(ci), P(ci)]),
     }
     if profiling:
         sig["sxfir_debug_clock"] = (ci, [vp, P(dbl)])

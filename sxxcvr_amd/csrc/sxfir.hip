@@ -9,6 +9,7 @@
 #include "../../include/sxfir_synthesizer_os.h"
 #include "../../include/sxfir_rational.h"
 #include "../../include/sxfir_translate.h"
+#include "../../include/sxfir_translate_tx.h"
 
 #include <hip/hip_runtime.h>
 
@@ -86,6 +87,7 @@
 #include "sxfir_interp_cx.hip.h"                // x4 x 128, x8 x 256 complex taps (include/sxfir_complex_tx.h)
 #include "sxfir_resample.hip.h"                 // rational up / down: the generic kernel and 4/5 x 128 (include/sxfir_rational.h)
 #include "sxfir_decim_mix.hip.h"                // translating decimators: the generic kernel and /4 x 128 (include/sxfir_translate.h)
+#include "sxfir_interp_mix.hip.h"               // translating interpolators: the generic kernel, x4 x 128 and x8 x 256 (include/sxfir_translate_tx.h)
 
 namespace {
 
@@ -127,3 +129,4 @@ inline size_t sample_bytes(int fmt) { return fmt == SXFIR_CF16 ? 4 : 8; }   // C
 #include "sxfir_synthesizer_os.hip.h"   // sxfir_create_synthesizer_os, sxfir_plan_synthesis_oversampling (include/sxfir_synthesizer_os.h)
 #include "sxfir_rational.hip.h"   // sxfir_create_rational, sxfir_resample, sxfir_time_resample, sxfir_plan_rational (include/sxfir_rational.h)
 #include "sxfir_translate.hip.h"   // sxfir_design_rotator, sxfir_create_translating, sxfir_plan_translation (include/sxfir_translate.h)
+#include "sxfir_translate_tx.hip.h"   // sxfir_create_translating_interpolator, sxfir_plan_translation_tx (include/sxfir_translate_tx.h)

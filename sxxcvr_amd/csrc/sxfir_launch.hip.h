@@ -361,7 +361,7 @@ static sxfir::InterpTileArgs interp_tile_args(const sxfir_plan *p, const CallIO 
     t.hist = (const float *)p->hist_dev;
     t.hist_out = (float *)p->hist_alt;
     t.out = (float *)c.out;
-    t.taps = geom.kind == GEOM_IPASS || geom.kind == GEOM_ICX ? p->taps_scaled_dev : p->taps_dev;      // the pass-major table(s)
+    t.taps = geom.kind == GEOM_IPASS || geom.kind == GEOM_ICX || geom.kind == GEOM_IMIX ? p->taps_scaled_dev : p->taps_dev;      // the pass-major table(s)
     t.n_in = (long long)c.n_in;
     t.in_stride = (long long)c.in_stride;
     t.out_stride = (long long)c.out_stride;
@@ -405,6 +405,42 @@ static sxfir::MixTileArgs mix_tile_args(const sxfir_plan *p, const CallIO &c, co
     a.lane_step = (unsigned)(8 * s % den);
     a.tile_step = (unsigned)(p->tile * s % den);
     a.stride_step = (unsigned)((long long)a.t.n_waves % den * a.tile_step % den);
+    return a;
+}
+
+// translating interpolators (include/sxfir_translate_tx.h).  Input m of the stream is turned by table entry (m t) mod den,
+// t = (den - mix_s) mod den; the call's input 0 has the absolute index `consumed` (64 bits; `back` samples in front of it, the
+// tiled kernel's halo, reach below 0 at the stream's start: the mathematical modulo).  For the tiled kernel also the steps between
+// the chunks of two lanes, a lane's chunks, tiles and a wave's tiles, so that its tile loop has no division
+static sxfir::TxMixer tx_mixer_of(const sxfir_plan *p, long long back)
+{
+    sxfir::TxMixer m{};
+    const long long den = p->mix_den;
+    m.w = p->mix_dev;
+    m.den = (unsigned)den;
+    m.t = (unsigned)((den - p->mix_s) % den);
+    m.phase = (unsigned)((((p->consumed - back) % den + den) % den) * m.t % den);
+    return m;
+}
+
+static sxfir::InterpMixGenericArgs imix_generic_args(const sxfir_plan *p, const CallIO &c)
+{
+    sxfir::InterpMixGenericArgs a{};
+    a.g = generic_args(p, c, 0);
+    a.mix = tx_mixer_of(p, 0);
+    return a;
+}
+
+static sxfir::InterpMixTileArgs imix_tile_args(const sxfir_plan *p, const CallIO &c, const LaunchGeom &geom)
+{
+    sxfir::InterpMixTileArgs a{};
+    a.t = interp_tile_args(p, c, geom, nullptr);
+    a.mix = tx_mixer_of(p, 32);                     // (the image of tile 0 starts InterpPass8::HIST samples in front of the call)
+    const long long den = p->mix_den, t = a.mix.t;
+    a.lane_step = (unsigned)(2 * t % den);
+    a.instr_step = (unsigned)(128 * t % den);
+    a.tile_step = (unsigned)(p->tile * t % den);
+    a.stride_step = (unsigned)((long long)a.t.n_groups % den * a.tile_step % den);
     return a;
 }
 
@@ -453,7 +489,7 @@ static int launch_decim4(sxfir_plan *p, const CallIO &c, const LaunchGeom &geom,
 
 extern "C" {
 
-// The interpolators (GEOM_IPASS, GEOM_ITILE, GEOM_ICX)
+// The interpolators (GEOM_IPASS, GEOM_ITILE, GEOM_ICX, GEOM_IMIX)
 static int launch_interp_tiled(sxfir_plan *p, const CallIO &c, const LaunchGeom &geom, dim3 grid, const KeyedRange *key, bool *key_pending)
 {
     const unsigned threads = (unsigned)p->form->threads;
@@ -464,6 +500,13 @@ static int launch_interp_tiled(sxfir_plan *p, const CallIO &c, const LaunchGeom 
         // complex taps: no keyed instance -- the count depends on the input alone and runs as the generic path's pass of its own
         if (int rc = need_tap_table(p, TAPS_PASS8_CX, "interp_cx_pass_kernel")) return rc;
         if (int rc = launch(p->k.interp_cx, grid, threads, c.st, interp_tile_args(p, c, geom, nullptr))) return rc;
+        if (key && key->hi > key->lo && key_pending) *key_pending = true;
+        return SXFIR_OK;
+    }
+    if (geom.kind == GEOM_IMIX) {
+        // translating plans: as the complex taps' -- the keying count is taken on the raw input, as a pass of its own
+        if (int rc = need_tap_table(p, TAPS_PASS8_CX, "interp_mix_pass_kernel")) return rc;
+        if (int rc = launch(p->k.imix, grid, threads, c.st, imix_tile_args(p, c, geom))) return rc;
         if (key && key->hi > key->lo && key_pending) *key_pending = true;
         return SXFIR_OK;
     }
@@ -513,8 +556,9 @@ static int launch_call(sxfir_plan *p, const CallIO &c, bool *history_done, const
     if (geom.kind == GEOM_GENERIC) {
         if (p->kernel == SXFIR_KERNEL_TILED) return refuse_tiled(p);
         const long long first = p->mode == SXFIR_DECIMATE ? first_offset(p) : 0;        // (a rational plan is an interpolator)
-        if (int rc = p->mix_den ? launch(p->k.mix_generic, grid, 256, c.st, mix_generic_args(p, c, first))
-                                : launch(p->k.generic, grid, 256, c.st, generic_args(p, c, first))) return rc;
+        if (int rc = !p->mix_den ? launch(p->k.generic, grid, 256, c.st, generic_args(p, c, first))
+                     : p->mode == SXFIR_DECIMATE ? launch(p->k.mix_generic, grid, 256, c.st, mix_generic_args(p, c, first))
+                                                 : launch(p->k.imix_generic, grid, 256, c.st, imix_generic_args(p, c))) return rc;
         if (key && key->hi > key->lo && key_pending) *key_pending = true;    // counted by the caller once the call is certain to commit
         return SXFIR_OK;
     }
@@ -535,7 +579,8 @@ static int launch_call(sxfir_plan *p, const CallIO &c, bool *history_done, const
     case GEOM_MIX: return launch(p->k.mix, grid, threads, c.st, mix_tile_args(p, c, geom));
     case GEOM_IPASS:
     case GEOM_ITILE:
-    case GEOM_ICX: return launch_interp_tiled(p, c, geom, grid, key, key_pending);
+    case GEOM_ICX:
+    case GEOM_IMIX: return launch_interp_tiled(p, c, geom, grid, key, key_pending);
     case GEOM_MULTI: return launch_decim_multi(p, c, geom, grid);
     }
     return launch_decim4(p, c, geom, grid);

@@ -31,7 +31,7 @@ enum PlanKind { KIND_REAL = 0, KIND_COMPLEX = 1, KIND_CHANNELIZER = 2, KIND_SYNT
 enum TapTable { TAPS_SCALED = 0, TAPS_SUBSET8 = 1, TAPS_PASS8 = 2, TAPS_BLOCKS16 = 3, TAPS_PHASED = 4, TAPS_NONE = 5, TAPS_PASS8_CX = 6 };
 
 // Which kernel family a call launches (LaunchGeom::kind, sxfir_launch.hip.h)
-enum { GEOM_GENERIC = 0, GEOM_MULTI = 1, GEOM_WIDE = 2, GEOM_TILE = 3, GEOM_IPASS = 4, GEOM_ITILE = 5, GEOM_CX = 6, GEOM_CHAN4 = 7, GEOM_SYN4 = 8, GEOM_CHAN4X2 = 9, GEOM_SYN4X2 = 10, GEOM_ICX = 11, GEOM_RAT45 = 12, GEOM_MIX = 13 };
+enum { GEOM_GENERIC = 0, GEOM_MULTI = 1, GEOM_WIDE = 2, GEOM_TILE = 3, GEOM_IPASS = 4, GEOM_ITILE = 5, GEOM_CX = 6, GEOM_CHAN4 = 7, GEOM_SYN4 = 8, GEOM_CHAN4X2 = 9, GEOM_SYN4X2 = 10, GEOM_ICX = 11, GEOM_RAT45 = 12, GEOM_MIX = 13, GEOM_IMIX = 14 };
 
 // One typed kernel pointer per launch-argument family, and a plan's kernels: resolved once by the plan's creator
 // (resolve_kernels below), read by the occupancy query there and by the launches (sxfir_launch.hip.h).
@@ -45,6 +45,8 @@ typedef void (*SynTileFn)(sxfir::SynTileArgs);
 typedef void (*SynOsTileFn)(sxfir::SynOsTileArgs);
 typedef void (*MixGenericFn)(sxfir::MixGenericArgs);
 typedef void (*MixTileFn)(sxfir::MixTileArgs);
+typedef void (*InterpMixGenericFn)(sxfir::InterpMixGenericArgs);
+typedef void (*InterpMixTileFn)(sxfir::InterpMixTileArgs);
 struct KernelTable {
     const char *generic_name;    // the plan's generic kernel, as sxfir_launch_geometry reports it, and the instance: every plan of every
     GenericFn generic;           // kind has exactly one (generic_kernel below), the kernel of every call its form does not take
@@ -60,6 +62,8 @@ struct KernelTable {
     DecimTileFn rat45;           // rational plans (include/sxfir_rational.h): resample45_kernel (4/5 x 128 taps, CF32)
     MixGenericFn mix_generic;    // translating plans (include/sxfir_translate.h): decim_mix_generic_kernel, in the place of `generic`
     MixTileFn mix;               // ... and decim4_mix_kernel (/4 x 128 complex taps, CF32)
+    InterpMixGenericFn imix_generic;   // translating interpolators (include/sxfir_translate_tx.h): interp_mix_generic_kernel, in the place of `generic`
+    InterpMixTileFn imix;        // ... and interp_mix_pass_kernel (x4 x 128, x8 x 256 complex taps, CF32)
 };
 
 // What the geometry and launch code needs to know of a tiled kernel family (FORM_* below).  A plan has at most one, settled at
@@ -116,7 +120,8 @@ struct sxfir_plan {
     void *hist_alt;        // the tiled kernels write the next history here, then the two swap
     float *mix_dev;        // translating plans (include/sxfir_translate.h): the rotation table, mix_den (re, im) pairs; else null
     int mix_den, mix_num;  // ... its length (0: the plan has no mixer) and num mod den of the band centre num / den
-    int mix_s;             // ... (num * ratio) mod den: table entries per output
+    int mix_s;             // ... (num * ratio) mod den: table entries per output.  A translating INTERPOLATOR (include/sxfir_translate_tx.h:
+                           // mode SXFIR_INTERPOLATE tells the two apart) carries the same three: its inputs are turned, by den - mix_s entries each
     KernelTable k;         // the instances this plan launches (null: none in this build for that family)
     ProfKnobs prof;        // written and read by the profiling build's hooks alone
     long long consumed, produced;
@@ -166,6 +171,20 @@ static MixGenericFn mix_generic_kernel(int fmt)
 {
     using namespace sxfir;
     return fmt == SXFIR_CF32 ? decim_mix_generic_kernel<CF32> : fmt == SXFIR_CF16 ? decim_mix_generic_kernel<CF16> : decim_mix_generic_kernel<S32, CF32>;
+}
+
+// Translating interpolators (include/sxfir_translate_tx.h): interp_mix_generic_kernel on InterpMixGenericArgs, the three instances
+// of a TX kind, and interp_mix_pass_kernel<QI, LL> on the complex-tap interpolators' shapes (sxfir_interp_mix.hip.h)
+static InterpMixGenericFn imix_generic_kernel(int fmt)
+{
+    using namespace sxfir;
+    return fmt == SXFIR_CF32 ? interp_mix_generic_kernel<CF32> : fmt == SXFIR_CF16 ? interp_mix_generic_kernel<CF16> : interp_mix_generic_kernel<CF32, S32>;
+}
+static InterpMixTileFn imix_kernel(int ratio)
+{
+    if (ratio == 4) return sxfir::interp_mix_pass_kernel<4, 4>;
+    if (ratio == 8) return sxfir::interp_mix_pass_kernel<2, 8>;
+    return nullptr;
 }
 
 // /8, /16, /32 with 32 taps per phase: decim_dense_kernel, non-temporal staging loads for the image rows no other tile reads
@@ -314,6 +333,9 @@ static const PlanForm FORM_MIX = {"decim4_mix_kernel", GEOM_MIX, 512, 64, 1, 2, 
 // interp_cx_pass_kernel: complex taps, x4 x 128 and x8 x 256 on CF32, on the pass kernel's frame and with its tiles and generations;
 // a small call keeps four tiles per workgroup as the other complex-tap and band kernels' do (a tile is twice the pass kernel's work)
 static const PlanForm FORM_ICX = {"interp_cx_pass_kernel", GEOM_ICX, TILE_IPASS, 64, 1, 2, true, 8, 8, TAPS_PASS8_CX};
+// interp_mix_pass_kernel: translating interpolators, x4 x 128 and x8 x 256 complex taps on CF32: interp_cx_pass_kernel's tile, threads,
+// start rule (any start), store rule, generations and tap tables
+static const PlanForm FORM_IMIX = {"interp_mix_pass_kernel", GEOM_IMIX, TILE_IPASS, 64, 1, 2, true, 8, 8, TAPS_PASS8_CX};
 
 // resample45_kernel: rational 4/5 x 128 on CF32, tiles of Resample45::TILE_IN = 1280 inputs (256 periods of five), one wave per tile; a
 // call starts on a period (a stream position that is a multiple of 5).  Its prologue is light (the taps are re-loaded per tile), so a
@@ -380,9 +402,11 @@ static void resolve_kernels(sxfir_plan *p)
     k.generic_name = g.name;
     k.generic = g.fn;
     if (p->mix_den) {           // a translating plan's generic kernel has an argument struct of its own
-        k.generic_name = "decim_mix_generic_kernel";
+        const bool rx = p->mode == SXFIR_DECIMATE;
+        k.generic_name = rx ? "decim_mix_generic_kernel" : "interp_mix_generic_kernel";
         k.generic = nullptr;
-        k.mix_generic = mix_generic_kernel(p->fmt);
+        if (rx) k.mix_generic = mix_generic_kernel(p->fmt);
+        else k.imix_generic = imix_generic_kernel(p->fmt);
     }
     switch (p->form ? p->form->geom : GEOM_GENERIC) {
     case GEOM_CHAN4: k.chan4 = sxfir::chan4_kernel; break;
@@ -393,6 +417,7 @@ static void resolve_kernels(sxfir_plan *p)
     case GEOM_CX: k.cx = sxfir::decim4_cx_kernel; break;
     case GEOM_MIX: k.mix = sxfir::decim4_mix_kernel; break;
     case GEOM_ICX: k.interp_cx = interp_cx_kernel(p->ratio); break;
+    case GEOM_IMIX: k.imix = imix_kernel(p->ratio); break;
     case GEOM_MULTI:
         if (!p->blocks) k.dense = dense_kernel(p->ratio, p->fmt);
         for (int split = 0; split < 2; ++split) k.blocks[split] = blocks_kernel(p->blocks, p->fmt, split != 0);
@@ -420,6 +445,7 @@ static const void *occupancy_instance(const sxfir_plan *p)
     case GEOM_CX: return (const void *)k.cx;
     case GEOM_MIX: return (const void *)k.mix;
     case GEOM_ICX: return (const void *)k.interp_cx;
+    case GEOM_IMIX: return (const void *)k.imix;
     case GEOM_CHAN4: return (const void *)k.chan4;
     case GEOM_CHAN4X2: return (const void *)k.chan4x2;
     case GEOM_SYN4: return (const void *)k.syn4;

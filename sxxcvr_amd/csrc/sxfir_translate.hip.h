@@ -57,8 +57,10 @@ int sxfir_create_translating(sxfir_plan **out, const float *taps_iq, int ntaps, 
 int sxfir_plan_translation(const sxfir_plan *p, int *num, int *den)
 {
     if (!p || !num || !den) return fail(SXFIR_EINVAL, "NULL argument");
-    *num = p->mix_den ? p->mix_num : 0;
-    *den = p->mix_den;
+    // (a translating interpolator carries a mixer too: include/sxfir_translate_tx.h, sxfir_plan_translation_tx)
+    const bool mine = p->mix_den && p->mode == SXFIR_DECIMATE;
+    *num = mine ? p->mix_num : 0;
+    *den = mine ? p->mix_den : 0;
     return SXFIR_OK;
 }
 

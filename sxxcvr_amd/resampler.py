@@ -1,4 +1,4 @@
-"""Python face of the C ABI in include/sxfir.h, include/sxfir_complex.h, include/sxfir_complex_tx.h, include/sxfir_channelizer.h, include/sxfir_synthesizer.h, include/sxfir_rational.h and include/sxfir_translate.h.
+"""Python face of the C ABI in include/sxfir.h, include/sxfir_complex.h, include/sxfir_complex_tx.h, include/sxfir_channelizer.h, include/sxfir_synthesizer.h, include/sxfir_rational.h, include/sxfir_translate.h and include/sxfir_translate_tx.h.
 
 Device memory comes either from torch (complex64 / int32 CUDA tensors, the
 current torch stream is used) or from the library's own sxfir_malloc for
@@ -402,6 +402,37 @@ class TranslatingDecimator(Resampler):
     def _translation(self):
         n, d = C.c_int(), C.c_int()
         self._ck(self._lib.sxfir_plan_translation(self._plan, C.byref(n), C.byref(d)))
+        return n.value, d.value
+
+    @property
+    def num(self):
+        """The band centre's numerator, reduced into [0, den)."""
+        return self._translation()[0]
+
+    @property
+    def den(self):
+        return self._translation()[1]
+
+
+class TranslatingInterpolator(Resampler):
+    """A frequency-translating interpolator (include/sxfir_translate_tx.h), the way back from TranslatingDecimator: the complex-tap
+    interpolator ComplexInterpolator(taps, ratio) with input m turned by exp(+2j pi (m * s mod den) / den), s = num * ratio mod den, m
+    the absolute input index, where it is read -- a base-band stream lands centred at num / den cycles per output sample
+    (taps = design_bandpass(ntaps, ratio, num, den, gain=ratio)) in one pass, on or off the x ratio raster.  History is raw samples.
+    The plan is an interpolator plan with complex taps in everything else: the same methods as Resampler."""
+
+    def __init__(self, taps, ratio, num, den, nchan=1, fmt="CF32", device=-1, profiling=False):
+        self._lib = load_sxfir(profiling)
+        self.profiling = bool(profiling)
+        self._plan = C.c_void_p()
+        taps = np.ascontiguousarray(taps, dtype=np.complex64)
+        self.mode, self.ratio, self.nchan, self.fmt, self.ntaps = INTERPOLATE, int(ratio), int(nchan), _FMT[fmt], taps.size
+        self._ck(self._lib.sxfir_create_translating_interpolator(C.byref(self._plan), taps.ctypes.data_as(C.c_void_p), taps.size,
+                                                                 int(ratio), int(num), int(den), int(nchan), self.fmt, int(device)))
+
+    def _translation(self):
+        n, d = C.c_int(), C.c_int()
+        self._ck(self._lib.sxfir_plan_translation_tx(self._plan, C.byref(n), C.byref(d)))
         return n.value, d.value
 
     @property

@@ -3,6 +3,7 @@
     python3 tools/cxbench.py [rx] [--log2n 28] [--iters 20] [--rounds 3]
     python3 tools/cxbench.py tx [--log2n 28] [--iters 20] [--rounds 3]
     python3 tools/cxbench.py mix [--log2n 28] [--iters 20] [--rounds 3] [--num 123 --den 1000]
+    python3 tools/cxbench.py mixtx [--log2n 28] [--iters 20] [--rounds 3] [--num 123 --den 1000]
 
 2^28 resident CF32 samples, sxfir_time_decimate (HIP events around back-to-back launches).  The complex /4 x 128 plan
 (decim4_cx_kernel) and the real /4 x 128 plan (decim4_wide_kernel) are alternated on the same box, three alternations.  Per
@@ -22,6 +23,12 @@ lower bound -- per round (a) the translating plan, (b) the complex plan of the s
 copy of the n / 4 output samples: 8 B read and 8 B written per output, the traffic floor of any separate rotation pass.  The
 condition is (a) < (b) + (c) in every round; (a) / (b) per round and its median say what the fused rotation costs.
 profiles/cx_mix.txt keeps the output.
+
+`mixtx`: the translating interpolators (include/sxfir_translate_tx.h, interp_mix_pass_kernel) the same way -- x4 x 128 and x8 x 256,
+n CF32 OUTPUT samples, sxfir_time_interpolate, per round (a) the translating plan, (b) the ComplexInterpolator plan of the same taps
+(interp_cx_pass_kernel), (c) a device-to-device copy of the call's n / ratio INPUT samples: the traffic floor of the separate
+rotation pass the old route needs in front of (b).  The condition is (a) < (b) + (c) in every round.  profiles/cx_mix_tx.txt keeps
+the output.
 """
 import argparse
 import ctypes as C
@@ -104,9 +111,49 @@ def mix(args, n):
     print("median (a) / (b) %.3f; (a) < (b) + (c) in every round: %s" % (statistics.median(ratios), ok))
 
 
+def mixtx(args, n):
+    """x4 x 128 and x8 x 256 on n resident outputs: translating plan, complex plan of the same taps, and a copy of the input."""
+    y = torch.empty(n, dtype=torch.complex64, device="cuda")
+    for L in (4, 8):
+        n_in = n // L
+        x = torch.empty(n_in, dtype=torch.complex64, device="cuda")
+        sxxcvr_amd.synth_fill(x, 0x51255, 0, 0)
+        x2 = torch.empty_like(x)
+        taps = sxxcvr_amd.design_bandpass(32 * L, L, args.num, args.den, gain=L)
+        plans = {"mix": sxxcvr_amd.TranslatingInterpolator(taps, L, args.num, args.den), "complex": sxxcvr_amd.ComplexInterpolator(taps, L)}
+        for k, p in plans.items():
+            p.set_kernel(KERNEL_TILED)
+            print("x%d %-8s %s" % (L, k, p.geometry(n_in)))
+            p.time_passes_ptr(x.data_ptr(), n_in, n_in, y.data_ptr(), n, 3)          # warm-up
+        print("x%d band centre %d / %d: %d table entries per input" % (L, plans["mix"].num, plans["mix"].den, plans["mix"].num * L % plans["mix"].den))
+
+        def copy_ms(iters):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                x2.copy_(x)
+            e1.record()
+            e1.synchronize()
+            return e0.elapsed_time(e1) / iters
+
+        copy_ms(3)
+        torch.cuda.synchronize()
+        ratios, ok = [], True
+        for r in range(args.rounds):
+            a = plans["mix"].time_passes_ptr(x.data_ptr(), n_in, n_in, y.data_ptr(), n, args.iters)
+            b = plans["complex"].time_passes_ptr(x.data_ptr(), n_in, n_in, y.data_ptr(), n, args.iters)
+            c = copy_ms(args.iters)
+            ratios.append(a / b)
+            ok = ok and a < b + c
+            print("x%d round %d (a) mix %.4f ms  (b) complex %.4f ms  (c) copy of the input %.4f ms (%.3f of 8 TB/s)  (b) + (c) %.4f ms  (a) / (b) %.3f  (a) < (b) + (c): %s" % (
+                L, r, a, b, c, 16.0 * n_in / (c * 1e-3) / 8e12, b + c, a / b, a < b + c))
+        print("x%d median (a) / (b) %.3f; (a) < (b) + (c) in every round: %s" % (L, statistics.median(ratios), ok))
+        del x, x2, plans
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", nargs="?", default="rx", choices=["rx", "tx", "mix"])
+    ap.add_argument("mode", nargs="?", default="rx", choices=["rx", "tx", "mix", "mixtx"])
     ap.add_argument("--log2n", type=int, default=28)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=3)
@@ -123,6 +170,8 @@ def main():
         return tx(args, n)
     if args.mode == "mix":
         return mix(args, n)
+    if args.mode == "mixtx":
+        return mixtx(args, n)
     x = torch.empty(n, dtype=torch.complex64, device="cuda")
     sxxcvr_amd.synth_fill(x, 0x51255, 0, 0)
     y = torch.empty(n // 4, dtype=torch.complex64, device="cuda")
