@@ -70,7 +70,7 @@
 #include "sxfir_interp_tile.hip.h"
 #include "sxfir_interp_pass.hip.h"
 #include "sxfir_decim_wide.hip.h"               // /4, 128 symmetric taps: the shipped form since round 4
-#include "sxfir_decim_cx.hip.h"                 // /4, 128 complex taps (include/sxfir_complex.h)
+#include "sxfir_decim_cx.hip.h"                 // /4, 128 complex taps, with or without a mixer (include/sxfir_complex.h, include/sxfir_translate.h)
 #ifdef SXFIR_PROFILING
 #include "sxfir_decim_tile2.hip.h"              // round 3's /4 form and its variants: A/B partners of the wide kernel, no instance in the production library since round 4
 #include "experiments/sxfir_decim_pair.hip.h"   // measured variant, not shipped (LABBOOK.md 5.1)
@@ -84,10 +84,8 @@
 #include "sxfir_synthesis4.hip.h"               // the 4-band synthesizer (include/sxfir_synthesizer.h)
 #include "sxfir_chan4x2.hip.h"                  // the 2x oversampled 4-band channelizer (include/sxfir_channelizer_os.h)
 #include "sxfir_synthesis4x2.hip.h"             // the 2x oversampled 4-band synthesizer (include/sxfir_synthesizer_os.h)
-#include "sxfir_interp_cx.hip.h"                // x4 x 128, x8 x 256 complex taps (include/sxfir_complex_tx.h)
+#include "sxfir_interp_cx.hip.h"                // x4 x 128, x8 x 256 complex taps, with or without a mixer (include/sxfir_complex_tx.h, include/sxfir_translate_tx.h)
 #include "sxfir_resample.hip.h"                 // rational up / down: the generic kernel and 4/5 x 128 (include/sxfir_rational.h)
-#include "sxfir_decim_mix.hip.h"                // translating decimators: the generic kernel and /4 x 128 (include/sxfir_translate.h)
-#include "sxfir_interp_mix.hip.h"               // translating interpolators: the generic kernel, x4 x 128 and x8 x 256 (include/sxfir_translate_tx.h)
 
 namespace {
 
@@ -121,12 +119,10 @@ inline size_t sample_bytes(int fmt) { return fmt == SXFIR_CF16 ? 4 : 8; }   // C
 #include "sxfir_timing.hip.h"    // sxfir_time_*, sxfir_clock_probe_*
 #include "sxfir_runtime.hip.h"   // synthetic source, converters, time arithmetic, tap design, memory / stream / event helpers
 #include "sxfir_comm.hip.h"      // sxfir_comm_*: the RCCL gather
-#include "sxfir_complex.hip.h"   // sxfir_create_complex, sxfir_design_bandpass (include/sxfir_complex.h)
-#include "sxfir_complex_tx.hip.h"   // sxfir_create_complex_interpolator (include/sxfir_complex_tx.h)
+#include "sxfir_complex.hip.h"   // create_complex_plan, sxfir_create_complex, sxfir_create_complex_interpolator, sxfir_design_bandpass (include/sxfir_complex.h, include/sxfir_complex_tx.h)
 #include "sxfir_channelizer.hip.h"   // sxfir_create_channelizer, sxfir_channelize (include/sxfir_channelizer.h)
 #include "sxfir_synthesizer.hip.h"   // sxfir_create_synthesizer, sxfir_synthesize (include/sxfir_synthesizer.h)
 #include "sxfir_channelizer_os.hip.h"   // sxfir_create_channelizer_os, sxfir_plan_oversampling (include/sxfir_channelizer_os.h)
 #include "sxfir_synthesizer_os.hip.h"   // sxfir_create_synthesizer_os, sxfir_plan_synthesis_oversampling (include/sxfir_synthesizer_os.h)
 #include "sxfir_rational.hip.h"   // sxfir_create_rational, sxfir_resample, sxfir_time_resample, sxfir_plan_rational (include/sxfir_rational.h)
-#include "sxfir_translate.hip.h"   // sxfir_design_rotator, sxfir_create_translating, sxfir_plan_translation (include/sxfir_translate.h)
-#include "sxfir_translate_tx.hip.h"   // sxfir_create_translating_interpolator, sxfir_plan_translation_tx (include/sxfir_translate_tx.h)
+#include "sxfir_translate.hip.h"   // sxfir_design_rotator, sxfir_create_translating, sxfir_create_translating_interpolator, sxfir_plan_translation, sxfir_plan_translation_tx (include/sxfir_translate.h, include/sxfir_translate_tx.h)

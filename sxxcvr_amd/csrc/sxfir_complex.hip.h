@@ -1,32 +1,62 @@
-// Complex-tap (band-pass) decimators of the C ABI (include/sxfir_complex.h): plan creation and the band-pass designer.  The plan
-// is of KIND_COMPLEX: a decimator under the real-tap contract of its shape, created through the frame of sxfir_plan.hip.h -- the
-// kernel table gives it decim4_cx_kernel and decim_cx_generic_kernel, decim_geom / launch_call (sxfir_launch.hip.h) choose between
-// the two per call, every other entry point takes it as a decimator.  Included by sxfir.hip last; not a stand-alone translation unit.
+// Complex-tap (band-pass) plans of the C ABI, both directions (include/sxfir_complex.h, include/sxfir_complex_tx.h): plan creation
+// and the band-pass designer.  The plan is of KIND_COMPLEX: a decimator or an interpolator under the real-tap contract of its shape,
+// created through the frame of sxfir_plan.hip.h -- the kernel table gives it decim4_cx_kernel and decim_cx_generic_kernel, or
+// interp_cx_pass_kernel and interp_cx_generic_kernel; decim_geom / interp_geom and launch_call (sxfir_launch.hip.h) choose between
+// the two per call, every other entry point takes it as the decimator or interpolator it is.  create_complex_plan is also the
+// translating plans' creation path (sxfir_translate.hip.h): the same plan with a mixer.  Included by sxfir.hip; not a stand-alone
+// translation unit.
 #pragma once
 
-extern "C" {
-
-int sxfir_complex_abi_version(void) { return SXFIR_COMPLEX_ABI_VERSION; }
-
-int sxfir_create_complex(sxfir_plan **out, int mode, const float *taps_iq, int ntaps, int ratio, int nchan, int fmt, int device)
+// The one creation path of the KIND_COMPLEX plans, behind the creator's own argument checks: the history of the plan's direction, the
+// real-tap contract, the mixer (den 0: none; else the band centre num / den: mix_den, mix_num, mix_s, and plan_to_device makes the
+// rotation table), the form of the shapes the tiled kernels take with its tap layout, the taps planar on the device.
+static int create_complex_plan(sxfir_plan **out, int mode, const float *taps_iq, int ntaps, int ratio, int num, int den, int nchan,
+                               int fmt, int device)
 {
-    if (int rc = check_create_args(out, taps_iq, mode, ntaps, "ratio", ratio, nchan, fmt)) return rc;
-    if (mode == SXFIR_INTERPOLATE)
-        return fail(SXFIR_EUNSUPPORTED, "complex taps: decimators only (no complex-tap interpolator kernel exists)");
+    const bool tx = mode == SXFIR_INTERPOLATE;
     sxfir_plan *p = nullptr;
     if (int rc = new_plan(&p, KIND_COMPLEX, mode, ntaps, ratio, nchan, fmt, device)) return rc;
-    p->hist_len = (ntaps + 1) & ~1;
+    p->hist_len = ((tx ? ntaps / ratio : ntaps) + 1) & ~1;
     real_tap_contract(p);
-    set_form(p, fmt == SXFIR_CF32 && ratio == 4 && ntaps == 128 ? &FORM_CX : nullptr);
+    if (den) {
+        p->mix_den = den;
+        p->mix_num = (int)((((long long)num % den) + den) % den);
+        p->mix_s = (int)((long long)p->mix_num * ratio % den);
+    }
+    const bool x4 = ratio == 4 && ntaps == 128, x8 = ratio == 8 && ntaps == 256;
+    const PlanForm *form = tx ? (den ? &FORM_IMIX : &FORM_ICX) : (den ? &FORM_MIX : &FORM_CX);
+    set_form(p, fmt == SXFIR_CF32 && (x4 || (tx && x8)) ? form : nullptr);
+    // an interpolator's two pass-major tables, for the shapes the tiled kernel takes; a decimator has no second tap table
+    p->tap_table = p->form ? p->form->taps : TAPS_NONE;
     resolve_form(p);
 
-    // planar on the device: a[0, ntaps) then b[0, ntaps); no second tap table (TAPS_NONE, new_plan)
+    // planar on the device: a[0, ntaps) then b[0, ntaps)
     std::vector<float> planar(2 * (size_t)ntaps);
     for (int k = 0; k < ntaps; ++k) {
         planar[(size_t)k] = taps_iq[2 * k];
         planar[(size_t)ntaps + (size_t)k] = taps_iq[2 * k + 1];
     }
     return plan_to_device(out, p, planar.data(), planar.size());
+}
+
+extern "C" {
+
+int sxfir_complex_abi_version(void) { return SXFIR_COMPLEX_ABI_VERSION; }
+int sxfir_complex_tx_abi_version(void) { return SXFIR_COMPLEX_TX_ABI_VERSION; }
+
+int sxfir_create_complex(sxfir_plan **out, int mode, const float *taps_iq, int ntaps, int ratio, int nchan, int fmt, int device)
+{
+    if (int rc = check_create_args(out, taps_iq, mode, ntaps, "ratio", ratio, nchan, fmt)) return rc;
+    if (mode == SXFIR_INTERPOLATE)
+        return fail(SXFIR_EUNSUPPORTED, "complex taps: decimators only (no complex-tap interpolator kernel exists)");
+    return create_complex_plan(out, mode, taps_iq, ntaps, ratio, 0, 0, nchan, fmt, device);
+}
+
+int sxfir_create_complex_interpolator(sxfir_plan **out, const float *taps_iq, int ntaps, int ratio, int nchan, int fmt, int device)
+{
+    if (int rc = check_create_args(out, taps_iq, SXFIR_INTERPOLATE, ntaps, "ratio", ratio, nchan, fmt)) return rc;
+    if (ntaps % ratio) return fail(SXFIR_EINVAL, "interpolator needs ntaps %% ratio == 0 (%d, %d)", ntaps, ratio);
+    return create_complex_plan(out, SXFIR_INTERPOLATE, taps_iq, ntaps, ratio, 0, 0, nchan, fmt, device);
 }
 
 int sxfir_taps_are_complex(const sxfir_plan *p, int *is_complex)

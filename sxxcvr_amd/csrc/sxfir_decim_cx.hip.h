@@ -22,15 +22,21 @@
 // Per tile of 512 outputs: 2048 v_pk_fma_f32 (2 chains x 8 outputs x 128 taps per lane; half of them with a scalar tap
 // operand) = twice a real-tap tile's 1024; 94 window ds_read_b128 (47 per pass) + 4 of the output transposition: 23.5 window
 // reads per 512 FMAs (the wide kernel: 39.5).  LDS 18 496 B per wave -> 8 waves per CU (2 per SIMD, 256 VGPRs each).
-// Registers and spills of the shipped instance: DESIGN.md 5.9 (tools/shipped_isa.py decim4_cx).
+// Registers and spills of the shipped instances: DESIGN.md 5.5, 5.12 (tools/shipped_isa.py decim4_cx).
+//
+// One kernel, two instances by argument struct: the complex-tap decimators' (DecimTileArgs) and the translating decimators'
+// (MixTileArgs: the same tile with every output turned by a table entry, sxfir_mixer.hip.h); what the mixer adds sits under
+// `if constexpr (MIX)`, and the plain instance's text is what it was before the mixer came.
 //
 // New code: the reference decimates inside the SX1255, whose base-band decimator is fixed and low-pass (SoapySX.cpp:180-208
 // only programs the divider); a band other than the one around 0 Hz has no counterpart there.
 #pragma once
 
+#include <type_traits>
 #include <utility>
 
 #include "sxfir_decim_wide.hip.h"       // DecimWide and the wide tile's frame: schedule, staging, carry-over, stores
+#include "sxfir_mixer.hip.h"            // Mixer, mix_rotate: the translating decimators' instance
 
 namespace sxfir {
 
@@ -97,13 +103,32 @@ __device__ __forceinline__ void load_cx_taps(unsigned long long tp, int half, f3
     for (int m = 0; m < 32; ++m) hs[m] = tq[32 * half + m];
 }
 
-__global__ __launch_bounds__(64) void decim4_cx_kernel(const DecimTileArgs a)
+// The argument struct of the translating decimators' instance (include/sxfir_translate.h): the plain struct plus the mixer and
+// the three steps of the tile walk, worked out by the host (mix_tile_args, sxfir_launch.hip.h) so that the tile loop holds no division
+struct MixTileArgs : DecimTileArgs {
+    Mixer mix;
+    unsigned lane_step;     // (8 s) mod den: between the first outputs of two lanes
+    unsigned tile_step;     // (512 s) mod den: between two tiles
+    unsigned stride_step;   // (n_waves * 512 s) mod den: between two tiles of one wave
+};
+
+// Args = DecimTileArgs: the complex-tap decimators' kernel.  Args = MixTileArgs: the translating decimators' (the launch geometry
+// calls that instance decim4_mix_kernel) -- the same tile with output m turned by w[(m s) mod den], m the ABSOLUTE output index.
+// Lane l owns outputs 8l..8l+7 of the tile: its first table index is (tile's phase + l (8 s mod den)) mod den, the next seven follow
+// by adding s and taking den off on overflow, all in 32 bits.  The tile's phase starts at (call's phase + (tile mod den)(512 s mod
+// den)) mod den and moves by (n_waves 512 s) mod den per stride of the tile loop.  The eight table reads (8 bytes each, a table of
+// at most 512 KiB that lives in L2) are issued between the two passes, behind the 1024 packed FMAs of pass 0; the rotation sits
+// between the combine and the transposition writes, so the full and the ragged store path both see rotated values.
+template <typename Args>
+__global__ __launch_bounds__(64) void decim4_cx_kernel(const Args ka)
 {
     using C = DecimWide;
+    constexpr bool MIX = std::is_same_v<Args, MixTileArgs>;
     static_assert(C::CHUNKS % 16 == 0, "whole 16-chunk rows");
     static_assert(DecimCx::P0FROM + DecimCx::PCH == C::WCH, "the two passes cover the window");
     __shared__ __attribute__((aligned(16))) f32x4 img[C::SLOTS];
 
+    const DecimTileArgs &a = ka;
     const int lane = threadIdx.x;
     const int ch = blockIdx.y;
     const float *in = a.in + 2 * a.in_stride * ch;
@@ -128,6 +153,15 @@ __global__ __launch_bounds__(64) void decim4_cx_kernel(const DecimTileArgs a)
 
     if (b == a.hist_wave) carry_history<8, C::HIST>(lane, in, hist, a.hist_out + 2 * a.hist_stride * ch, a.n_in);
 
+    // the mixer's phases, 32 bits: the lane's offset into a tile and the first tile's phase (the only divisions of the kernel)
+    unsigned den = 0, s = 0, lane_ph = 0, tile_ph = 0;
+    if constexpr (MIX) {
+        den = ka.mix.den, s = ka.mix.step;
+        lane_ph = (unsigned)lane * ka.lane_step % den;                                          // (63 * 65535 < 2^32)
+        tile_ph = ka.mix.phase + ((unsigned)tile % den) * ka.tile_step % den;                  // (65535^2 < 2^32)
+        if (tile_ph >= den) tile_ph -= den;
+    }
+
     // lane l: outputs 8l..8l+7 of the tile; window from chunk 16l (lane stride 17 slots: conflict free)
     const f32x4 *win = img + 17 * lane;
     const int swz_w = (lane & 1) ^ ((lane >> 1) & 3), swz_r = ((lane >> 2) & 1) ^ ((lane >> 3) & 3);   // the output transposition's swizzles
@@ -143,6 +177,21 @@ __global__ __launch_bounds__(64) void decim4_cx_kernel(const DecimTileArgs a)
             load_cx_taps(tp, 1, hs, hv);
             fir_cx_pass<DecimCx::NB>(std::make_integer_sequence<int, DecimCx::PCH>{}, win, hs, hv, a1a, a1b);
         }
+        // the lane's eight table entries, read behind pass 1 (its tap registers are dead) and in front of pass 0's FMAs
+        f32x2 wv[MIX ? 8 : 1];
+        if constexpr (MIX) {
+            unsigned long long wp = (unsigned long long)ka.mix.w;
+            asm volatile("" : "+s"(wp) : "v"(a1a[0]), "v"(a1a[7]), "v"(a1b[0]), "v"(a1b[7]));
+            const __attribute__((address_space(1))) f32x2 *wt = (const __attribute__((address_space(1))) f32x2 *)wp;      // (global, not flat, loads)
+            unsigned idx = tile_ph + lane_ph;
+            if (idx >= den) idx -= den;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                wv[i] = wt[idx];
+                idx += s;
+                if (idx >= den) idx -= den;
+            }
+        }
         {
             f32x2 hs[32], hv[32];
             unsigned long long tp = (unsigned long long)a.taps;
@@ -154,14 +203,20 @@ __global__ __launch_bounds__(64) void decim4_cx_kernel(const DecimTileArgs a)
         f32x4 y[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            // A = P0 + P1 and B = P0 + P1 (the real-tap contract's last addition), then y = A + j B: one rounding each
+            // A = P0 + P1 and B = P0 + P1 (the real-tap contract's last addition), then y = A + j B: one rounding each; then the
+            // mixer's rotation
             f32x2 yy[2];
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
                 const int i = 2 * k + e;
                 const float are = __fadd_rn(a0a[i].x, a1a[i].x), aim = __fadd_rn(a0a[i].y, a1a[i].y);
                 const float bre = __fadd_rn(a0b[i].x, a1b[i].x), bim = __fadd_rn(a0b[i].y, a1b[i].y);
-                yy[e] = (f32x2){__fsub_rn(are, bim), __fadd_rn(aim, bre)};
+                if constexpr (MIX) {
+                    const float2 r = mix_rotate(make_float2(__fsub_rn(are, bim), __fadd_rn(aim, bre)), make_float2(wv[i].x, wv[i].y));
+                    yy[e] = (f32x2){r.x, r.y};
+                } else {
+                    yy[e] = (f32x2){__fsub_rn(are, bim), __fadd_rn(aim, bre)};
+                }
             }
             y[k] = (f32x4){yy[0].x, yy[0].y, yy[1].x, yy[1].y};
         }
@@ -178,6 +233,10 @@ __global__ __launch_bounds__(64) void decim4_cx_kernel(const DecimTileArgs a)
         }
         // the next tile's DMA overwrites the image only after these LDS reads have returned
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        if constexpr (MIX) {
+            tile_ph += ka.stride_step;
+            if (tile_ph >= den) tile_ph -= den;
+        }
     }
 }
 

@@ -24,28 +24,59 @@
 // The output path keeps the compiler's addressing at both ratios (the real x8 instance's hand-written store offsets are not
 // carried over).  Eight stores per tile at both ratios (CPL = QI L / 2 = 8): the counted wait is s_waitcnt vmcnt(8).
 //
+// One kernel, two instances per ratio by argument struct: the complex-tap interpolators' (InterpTileArgs) and the translating
+// interpolators' (InterpMixTileArgs, sxfir_mixer.hip.h); what the mixer adds sits under `if constexpr (MIX)`.  Between the staged
+// image landing and the window read the wave rotates the image IN PLACE in LDS: all TILE_IN + 32 samples, the halo included, lane l
+// the chunks l, 64 + l (and 128 + l) below CHUNKS -- 2.25 chunks of two samples per lane at x4, 1.25 at x8 -- so the passes read
+// rotated samples and what is carried to the next call's history, read from HBM, stays raw.  The table entries of a tile (two 8-byte
+// reads per chunk, a table of at most 512 KiB that lives in L2) are fetched one tile ahead, in front of that tile's DMAs, and held in
+// 2 NLOAD register pairs through the arithmetic.  The wave's prologue holds the only divisions (the lane's offset, the first tile's
+// phase); the steps per chunk, per DMA instruction, per tile and per stride of the tile loop come from the host.
+//
+// The counted wait.  s_waitcnt vmcnt(8) at the loop head presumes that at least eight VMEM instructions were issued behind the next
+// tile's DMAs (the tile's eight stores: vmcnt counts loads and stores together, in issue order) -- "at most 8 outstanding" then
+// means the DMAs have landed.  The mixer's table reads are issued in FRONT of the DMAs, so the sequence behind the DMAs is eight
+// stores and nothing else in both instances, and the same wait covers the table reads.  They are written as inline instructions
+// (an ordinary load's result, used while an LDS-DMA is in flight, makes the compiler wait with vmcnt(0) and drain the stores);
+// behind the wait their registers pass through an empty statement, so no use of them can be placed in front of it.
+//
 // New code: in the reference the SX1255 interpolates what snd_pcm_writei hands it (SoapySX.cpp:1093), the one band around 0 Hz.
 #pragma once
 
+#include <type_traits>
 #include <utility>
 
 #include "sxfir_interp_pass.hip.h"      // InterpPass8, interp_pass_steps, InterpTileArgs
+#include "sxfir_mixer.hip.h"            // Mixer, mix_rotate: the translating interpolators' instances
 #include "sxfir_synthesis4.hip.h"       // syn_first_tile, syn_load_tap_set
 
 namespace sxfir {
 
-template <int QI, int LL>
-__global__ __launch_bounds__(64) void interp_cx_pass_kernel(const InterpTileArgs a)
+// The argument struct of the translating interpolators' instances (include/sxfir_translate_tx.h): the plain struct plus the mixer and
+// the steps of the image walk, worked out by the host in 64 bits (imix_tile_args, sxfir_launch.hip.h)
+struct InterpMixTileArgs : InterpTileArgs {
+    Mixer mix;
+    unsigned lane_step;     // (2 t) mod den: between the chunks of two lanes
+    unsigned instr_step;    // (128 t) mod den: between a lane's chunks (64 chunks apart)
+    unsigned tile_step;     // (TILE_IN t) mod den: between two tiles
+    unsigned stride_step;   // (n_groups TILE_IN t) mod den: between two tiles of one wave
+};
+
+template <int QI, int LL, typename Args>
+__global__ __launch_bounds__(64) void interp_cx_pass_kernel(const Args ka)
 {
     using C = InterpPass8<QI, LL>;
+    constexpr bool MIX = std::is_same_v<Args, InterpMixTileArgs>;
     static_assert((QI == 4 && LL == 4) || (QI == 2 && LL == 8), "x4 with four inputs per lane, x8 with two");
     static_assert(C::CPL == 8, "eight stores per tile behind the next tile's DMAs");
     static_assert(C::TILE_IN >= C::HIST && (C::TILE_IN & (C::TILE_IN - 1)) == 0, "tile 0 is the only one that reaches into the history");
     static_assert((QI / 2) * 63 + C::NWU <= C::CHUNKS, "the last lane's window ends inside the image");
+    static_assert(!MIX || C::CHUNKS <= C::IMG, "slot = chunk: the rotation reads every slot of the image, writes those below CHUNKS");
     constexpr int NSETS = C::L / 2;               // tap sets (passes) of one table: (c, p) at 2c + p; b's follow a's
     __shared__ __attribute__((aligned(16))) f32x4 lds[C::IMG + C::OBUF];
     f32x4 *obuf = lds + C::IMG;
 
+    const InterpTileArgs &a = ka;
     const int lane = threadIdx.x;
     const int ch = blockIdx.y;
     const float *in = a.in + 2 * a.in_stride * ch;
@@ -57,11 +88,63 @@ __global__ __launch_bounds__(64) void interp_cx_pass_kernel(const InterpTileArgs
     const int G = a.n_groups;
     const int first_tile = syn_first_tile(blockIdx.x, G);
     if (first_tile >= a.n_tiles) return;
+    // the next call's history: raw samples, from HBM
     if (first_tile == (a.n_tiles - 1) % G && lane < C::HIST) {
         const long long s = a.n_in - C::HIST + lane;
         const float2 v = s >= 0 ? reinterpret_cast<const float2 *>(in)[s] : reinterpret_cast<const float2 *>(hist)[s + C::HIST];
         reinterpret_cast<float2 *>(a.hist_out + 2 * a.hist_stride * ch)[lane] = v;
     }
+
+    // the mixer's phases, 32 bits: the lane's chunks in a tile's image and the first tile's phase (the only divisions of the kernel)
+    unsigned den = 0, tstep = 0, tile_ph = 0;
+    unsigned lane_ph[C::NLOAD] = {};
+    unsigned long long wbase = 0;
+    if constexpr (MIX) {
+        den = ka.mix.den, tstep = ka.mix.step;
+        lane_ph[0] = (unsigned)lane * ka.lane_step % den;                                          // (63 * 65535 < 2^32)
+#pragma unroll
+        for (int i = 1; i < C::NLOAD; ++i) {
+            lane_ph[i] = lane_ph[i - 1] + ka.instr_step;
+            if (lane_ph[i] >= den) lane_ph[i] -= den;
+        }
+        tile_ph = ka.mix.phase + ((unsigned)first_tile % den) * ka.tile_step % den;                // (65535^2 < 2^32)
+        if (tile_ph >= den) tile_ph -= den;
+        wbase = (unsigned long long)ka.mix.w;
+    }
+
+    // a tile's table entries: the two samples of the lane's chunk 64 i + lane.  Every index is below den, so the lanes whose chunk
+    // lies past the image's end read an entry too (and use it for nothing)
+    // The reads are written out as instructions of their own: beside an LDS-DMA in flight the compiler waits with vmcnt(0) for
+    // an ordinary load's result, which would drain the tile's stores at every loop head.  So nothing the compiler knows of is
+    // pending on these registers; wait_image at the loop head makes them usable.
+    f32x2 wt[MIX ? C::NLOAD : 1][2];
+    auto fetch = [&](unsigned ph) __attribute__((always_inline)) {
+        if constexpr (MIX) {
+#pragma unroll
+            for (int i = 0; i < C::NLOAD; ++i) {
+                unsigned i0 = ph + lane_ph[i];
+                if (i0 >= den) i0 -= den;
+                unsigned i1 = i0 + tstep;
+                if (i1 >= den) i1 -= den;
+                asm volatile("global_load_dwordx2 %0, %1, %2" : "=&v"(wt[i][0]) : "v"(8u * i0), "s"(wbase) : "memory");      // (8 * 65535 < 2^20)
+                asm volatile("global_load_dwordx2 %0, %1, %2" : "=&v"(wt[i][1]) : "v"(8u * i1), "s"(wbase) : "memory");
+            }
+        }
+    };
+    // the wait for a staged tile: its image and, with a mixer, its table entries.  s_waitcnt vmcnt counts loads and stores together,
+    // in issue order: with the next tile's table reads and DMAs issued BEFORE this tile's eight stores, "at most 8 outstanding" means
+    // both have landed; a tile staged through registers and a wave's first tile wait for everything.  BEHIND the wait the table
+    // registers pass through an empty statement: every use of them follows it, and a copy the compiler makes for it follows the
+    // wait too
+    auto wait_image = [&](bool counted) __attribute__((always_inline)) {
+        if (counted) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if constexpr (MIX) {
+            static_assert(C::NLOAD == 2 || C::NLOAD == 3, "the operand lists below");
+            if constexpr (C::NLOAD == 3) asm volatile("" : "+v"(wt[0][0]), "+v"(wt[0][1]), "+v"(wt[1][0]), "+v"(wt[1][1]), "+v"(wt[2][0]), "+v"(wt[2][1]) :: "memory");
+            else asm volatile("" : "+v"(wt[0][0]), "+v"(wt[0][1]), "+v"(wt[1][0]), "+v"(wt[1][1]) :: "memory");
+        }
+    };
 
     // HBM -> LDS for one tile: samples [q0 - 32, q0 + TILE_IN).  The first and the last 16 chunks are shared with the neighbouring
     // tiles (plain loads), those in between are this tile's alone (non-temporal).  Tiles below n_full have all their inputs (and
@@ -115,14 +198,27 @@ __global__ __launch_bounds__(64) void interp_cx_pass_kernel(const InterpTileArgs
     };
 
     int tile = first_tile;
+    fetch(tile_ph);
     stage(tile);
     bool counted = false;                                       // the staged tile's DMAs sit in front of CPL stores
     while (true) {
-        // s_waitcnt vmcnt counts loads and stores together, in issue order: with the next tile's DMAs issued BEFORE this tile's
-        // eight stores, "at most 8 outstanding" means the DMAs have landed
-        if (counted) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_image(counted);
         const long long q0 = (long long)tile * C::TILE_IN;
+
+        // ---- the mixer's rotation, in place: chunk 64 i + lane holds samples q0 - 32 + 2 (64 i + lane) and the one behind it.  (A
+        // slot past CHUNKS belongs to no sample: it is read, since every lane runs the instruction anyway, and not written.)
+        if constexpr (MIX) {
+#pragma unroll
+            for (int i = 0; i < C::NLOAD; ++i) {
+                const int slot = 64 * i + lane;
+                const f32x4 v = lds[slot];
+                const float2 r0 = mix_rotate(make_float2(v.x, v.y), make_float2(wt[i][0].x, wt[i][0].y));
+                const float2 r1 = mix_rotate(make_float2(v.z, v.w), make_float2(wt[i][1].x, wt[i][1].y));
+                if (64 * i + 63 < C::CHUNKS || slot < C::CHUNKS) lds[slot] = (f32x4){r0.x, r0.y, r1.x, r1.y};
+            }
+            // one wave: its LDS instructions complete in order; the window reads below follow the rotated writes
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        }
 
         // ---- the lane's window, once: samples q0 + QI g - 32 .. q0 + QI g + QI - 1  ->  image chunks (QI/2) g .. + NWU - 1
         // (row half p uses chunks 8 - 8p + t, t = 0 .. NW - 1, of these; both tap tables use the same)
@@ -133,9 +229,16 @@ __global__ __launch_bounds__(64) void interp_cx_pass_kernel(const InterpTileArgs
             for (int t = 0; t < C::NWU; ++t) win[t] = wp[t];
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        // the image is free: fetch the next tile behind the arithmetic of this one
+        // the image is free: fetch the next tile -- its table entries, then its image -- behind the arithmetic of this one
         const int next = tile + G;
         counted = false;
+        // (the table reads are issued on the wave's last tile too -- every index is a valid one --, so that the registers have one
+        // definition inside the loop and the compiler no reason to copy them while they are in flight)
+        if constexpr (MIX) {
+            tile_ph += ka.stride_step;
+            if (tile_ph >= den) tile_ph -= den;
+            fetch(tile_ph);
+        }
         if (next < a.n_tiles) counted = stage(next);
 
         // what the next tap set's loads wait for: a result of the pass before (the tile's first set: a window register)

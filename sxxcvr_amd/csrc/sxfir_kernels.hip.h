@@ -7,6 +7,10 @@
 #include <hip/hip_fp16.h>
 #include <stdint.h>
 
+#include <type_traits>
+
+#include "sxfir_mixer.hip.h"            // Mixer, mix_rotate: the translating plans' generic kernels
+
 namespace sxfir {
 
 // Sample access for the two IQ storage formats (arithmetic is always fp32).
@@ -102,6 +106,12 @@ struct GenericArgs {
     int down;               // rational plans: `down` of up / down (up is `ratio`)
 };
 
+// The translating plans' generic kernels (sxfir_mixer.hip.h): GenericArgs keeps its size.  m_first: a translating decimator's
+// absolute index of the call's first output.
+struct MixGenericArgs : GenericArgs {
+    Mixer mix;
+};
+
 template <typename F>
 __device__ __forceinline__ float2 sample_at(const GenericArgs &a, const void *in, const void *hist, long long idx)
 {
@@ -180,9 +190,13 @@ __global__ __launch_bounds__(256) void decim_generic_kernel(const GenericArgs a)
 // Complex taps h = a + j b (a.taps: a[0, ntaps) then b[0, ntaps)), one output per thread: A = a (*) x and B = b (*) x are two
 // real-tap outputs under the contract above, one after the other through the same code (one set of partial arrays); then
 // y.re = A.re - B.im, y.im = A.im + B.re, one rounding each, and FO::store rounds to half once for CF16.
-template <typename F, typename FO = F>
-__global__ __launch_bounds__(256) void decim_cx_generic_kernel(const GenericArgs a)
+// Args = MixGenericArgs: the translating decimators' instances (include/sxfir_translate.h; the launch geometry calls them
+// decim_mix_generic_kernel) -- output m_first + m turned by the table entry of ((m_first + m) mod den) s mod den, reduced exactly,
+// in integers.
+template <typename F, typename FO = F, typename Args = GenericArgs>
+__global__ __launch_bounds__(256) void decim_cx_generic_kernel(const Args ka)
 {
+    const GenericArgs &a = ka;
     const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= a.n_out) return;
     const int ch = blockIdx.y;
@@ -196,7 +210,15 @@ __global__ __launch_bounds__(256) void decim_cx_generic_kernel(const GenericArgs
         if (part == 0) ab[0] = v;
         else ab[1] = v;
     }
-    FO::store(out, m, make_float2(__fsub_rn(ab[0].x, ab[1].y), __fadd_rn(ab[0].y, ab[1].x)), a.thr2);
+    const float2 z = make_float2(__fsub_rn(ab[0].x, ab[1].y), __fadd_rn(ab[0].y, ab[1].x));
+    if constexpr (std::is_same_v<Args, MixGenericArgs>) {
+        const unsigned r = (unsigned)((unsigned long long)(a.m_first + m) % ka.mix.den);       // < 2^16
+        const unsigned idx = r * ka.mix.step % ka.mix.den;                                     // (65535^2 < 2^32)
+        const float2 w = reinterpret_cast<const float2 *>(ka.mix.w)[idx];
+        FO::store(out, m, mix_rotate(z, w), a.thr2);
+    } else {
+        FO::store(out, m, z, a.thr2);
+    }
 }
 
 // Interpolator, one output per thread: y[n] = sum_j h[j*L + n%L] x[n/L - j],
@@ -274,6 +296,56 @@ __global__ __launch_bounds__(256) void interp_cx_generic_kernel(const GenericArg
     const int r = (int)(n - q * a.ratio);
     const float2 A = interp_generic_output<F>(a, a.taps, in, hist, q, r);
     const float2 B = interp_generic_output<F>(a, a.taps + a.ntaps, in, hist, q, r);
+    FO::store(out, n, make_float2(__fsub_rn(A.x, B.y), __fadd_rn(A.y, B.x)), a.thr2);
+}
+
+// The translating interpolators' generic kernel (include/sxfir_translate_tx.h): interp_cx_generic_kernel's output over window samples
+// that are rotated as they are read.  Both chains (the a taps, the b taps) in one loop over the window, so a sample is rotated
+// once; each chain is the real-tap interpolator's (interp_generic_output), bit for bit.  One 64-bit modulo per thread (the input
+// index of the output), one 32-bit product and modulo per chain (its oldest sample), then the index moves by t per sample along
+// the descending j.
+// (The decimators' pair is one kernel; this one rotates inside the chain loop, which is another loop: it stays a kernel of its own.)
+template <typename F, typename FO = F>
+__global__ __launch_bounds__(256) void interp_mix_generic_kernel(const MixGenericArgs ma)
+{
+    const GenericArgs &a = ma;
+    const long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= a.n_out) return;
+    const int ch = blockIdx.y;
+    const char *in = (const char *)a.in + sizeof(typename F::storage) * a.in_stride * ch;
+    const char *hist = (const char *)a.hist + sizeof(typename F::storage) * a.hist_stride * ch;
+    char *out = (char *)a.out + sizeof(typename FO::storage) * a.out_stride * ch;
+    const int L = a.ratio;
+    const long long q = n / L;
+    const int r = (int)(n - q * L);
+    const int jl = a.ntaps / L / a.jsplit;
+    const float *ta = a.taps, *tb = a.taps + a.ntaps;
+
+    // the table index of input q: (phase + (q mod den) t) mod den                           ((65535^2 < 2^32))
+    const unsigned den = ma.mix.den, t = ma.mix.step;
+    unsigned iq = ma.mix.phase + (unsigned)((unsigned long long)q % den) * t % den;
+    if (iq >= den) iq -= den;
+    const float2 *w = reinterpret_cast<const float2 *>(ma.mix.w);
+
+    float2 A = make_float2(0.0f, 0.0f), B = make_float2(0.0f, 0.0f);
+    for (int p = 0; p < a.jsplit; ++p) {
+        const int j0 = (p + 1) * jl - 1;                                // the chain's oldest sample: q - j0
+        unsigned idx = iq + den - (unsigned)j0 * t % den;              // (j0 < 65536)
+        if (idx >= den) idx -= den;
+        float ai = 0.0f, aq = 0.0f, bi = 0.0f, bq = 0.0f;
+        for (int j = j0; j >= p * jl; --j) {
+            const float2 x = mix_rotate(sample_at<F>(a, in, hist, q - j), w[idx]);
+            const float ha = ta[j * L + r], hb = tb[j * L + r];
+            ai = __builtin_fmaf(ha, x.x, ai);
+            aq = __builtin_fmaf(ha, x.y, aq);
+            bi = __builtin_fmaf(hb, x.x, bi);
+            bq = __builtin_fmaf(hb, x.y, bq);
+            idx += t;
+            if (idx >= den) idx -= den;
+        }
+        A = p == 0 ? make_float2(ai, aq) : make_float2(__fadd_rn(A.x, ai), __fadd_rn(A.y, aq));
+        B = p == 0 ? make_float2(bi, bq) : make_float2(__fadd_rn(B.x, bi), __fadd_rn(B.y, bq));
+    }
     FO::store(out, n, make_float2(__fsub_rn(A.x, B.y), __fadd_rn(A.y, B.x)), a.thr2);
 }
 

@@ -375,72 +375,57 @@ static sxfir::InterpTileArgs interp_tile_args(const sxfir_plan *p, const CallIO 
     return t;
 }
 
-// translating plans (include/sxfir_translate.h).  The call's first output has the absolute index `produced`: its table index, in
-// 64 bits, and for the tiled kernel the steps between lanes, tiles and a wave's tiles, so that its tile loop has no division
-static sxfir::Mixer mixer_of(const sxfir_plan *p)
+// translating plans (include/sxfir_translate.h, include/sxfir_translate_tx.h).  Item m of the stream -- a decimator's output, an
+// interpolator's input -- is turned by table entry (m step) mod den, `step` entries per item: a decimator's mix_s, an interpolator's
+// (den - mix_s) mod den.  The call's first item has the absolute index `first` (64 bits); `halo` items in front of it (the tiled
+// interpolator's image) reach below 0 at the stream's start: the mathematical modulo.
+static sxfir::Mixer mixer_of(const sxfir_plan *p, long long step, long long first, long long halo)
 {
     sxfir::Mixer m{};
-    m.w = p->mix_dev;
-    m.den = (unsigned)p->mix_den;
-    m.s = (unsigned)p->mix_s;
-    m.phase = (unsigned)((p->produced % p->mix_den) * p->mix_s % p->mix_den);
-    return m;
-}
-
-static sxfir::MixGenericArgs mix_generic_args(const sxfir_plan *p, const CallIO &c, long long first)
-{
-    sxfir::MixGenericArgs a{};
-    a.g = generic_args(p, c, first);
-    a.g.m_first = p->produced;
-    a.mix = mixer_of(p);
-    return a;
-}
-
-static sxfir::MixTileArgs mix_tile_args(const sxfir_plan *p, const CallIO &c, const LaunchGeom &geom)
-{
-    sxfir::MixTileArgs a{};
-    a.t = decim_tile_args(p, c, geom);
-    a.mix = mixer_of(p);
-    const long long den = p->mix_den, s = p->mix_s;
-    a.lane_step = (unsigned)(8 * s % den);
-    a.tile_step = (unsigned)(p->tile * s % den);
-    a.stride_step = (unsigned)((long long)a.t.n_waves % den * a.tile_step % den);
-    return a;
-}
-
-// translating interpolators (include/sxfir_translate_tx.h).  Input m of the stream is turned by table entry (m t) mod den,
-// t = (den - mix_s) mod den; the call's input 0 has the absolute index `consumed` (64 bits; `back` samples in front of it, the
-// tiled kernel's halo, reach below 0 at the stream's start: the mathematical modulo).  For the tiled kernel also the steps between
-// the chunks of two lanes, a lane's chunks, tiles and a wave's tiles, so that its tile loop has no division
-static sxfir::TxMixer tx_mixer_of(const sxfir_plan *p, long long back)
-{
-    sxfir::TxMixer m{};
     const long long den = p->mix_den;
     m.w = p->mix_dev;
     m.den = (unsigned)den;
-    m.t = (unsigned)((den - p->mix_s) % den);
-    m.phase = (unsigned)((((p->consumed - back) % den + den) % den) * m.t % den);
+    m.step = (unsigned)step;
+    m.phase = (unsigned)((((first - halo) % den + den) % den) * step % den);
     return m;
 }
 
-static sxfir::InterpMixGenericArgs imix_generic_args(const sxfir_plan *p, const CallIO &c)
+// the translating plans' generic kernels: a decimator's outputs count from `produced`, an interpolator's inputs from `consumed`
+static sxfir::MixGenericArgs mix_generic_args(const sxfir_plan *p, const CallIO &c, long long first)
 {
-    sxfir::InterpMixGenericArgs a{};
-    a.g = generic_args(p, c, 0);
-    a.mix = tx_mixer_of(p, 0);
+    sxfir::MixGenericArgs a{generic_args(p, c, first)};             // (the plain struct is its base)
+    if (p->mode == SXFIR_DECIMATE) {
+        a.m_first = p->produced;
+        a.mix = mixer_of(p, p->mix_s, p->produced, 0);
+    } else {
+        a.mix = mixer_of(p, (p->mix_den - p->mix_s) % p->mix_den, p->consumed, 0);
+    }
     return a;
 }
 
+// ... and for the tiled kernels the steps between lanes, tiles and a wave's tiles, so that their tile loops have no division
+static sxfir::MixTileArgs mix_tile_args(const sxfir_plan *p, const CallIO &c, const LaunchGeom &geom)
+{
+    sxfir::MixTileArgs a{decim_tile_args(p, c, geom)};
+    a.mix = mixer_of(p, p->mix_s, p->produced, 0);
+    const long long den = p->mix_den, s = p->mix_s;
+    a.lane_step = (unsigned)(8 * s % den);
+    a.tile_step = (unsigned)(p->tile * s % den);
+    a.stride_step = (unsigned)((long long)a.n_waves % den * a.tile_step % den);
+    return a;
+}
+
+// the tiled translating interpolators: the steps between the chunks of two lanes, a lane's chunks, tiles and a wave's tiles
 static sxfir::InterpMixTileArgs imix_tile_args(const sxfir_plan *p, const CallIO &c, const LaunchGeom &geom)
 {
-    sxfir::InterpMixTileArgs a{};
-    a.t = interp_tile_args(p, c, geom, nullptr);
-    a.mix = tx_mixer_of(p, 32);                     // (the image of tile 0 starts InterpPass8::HIST samples in front of the call)
-    const long long den = p->mix_den, t = a.mix.t;
+    sxfir::InterpMixTileArgs a{interp_tile_args(p, c, geom, nullptr)};
+    // (the image of tile 0 starts InterpPass8::HIST samples in front of the call)
+    a.mix = mixer_of(p, (p->mix_den - p->mix_s) % p->mix_den, p->consumed, 32);
+    const long long den = p->mix_den, t = a.mix.step;
     a.lane_step = (unsigned)(2 * t % den);
     a.instr_step = (unsigned)(128 * t % den);
     a.tile_step = (unsigned)(p->tile * t % den);
-    a.stride_step = (unsigned)((long long)a.t.n_groups % den * a.tile_step % den);
+    a.stride_step = (unsigned)((long long)a.n_groups % den * a.tile_step % den);
     return a;
 }
 
@@ -496,17 +481,12 @@ static int launch_interp_tiled(sxfir_plan *p, const CallIO &c, const LaunchGeom 
     if (geom.kind == GEOM_IPASS)
         if (int rc = need_tap_table(p, TAPS_PASS8, "interp8_pass_kernel")) return rc;
     if (geom.n_tiles * geom.split > 0x7fffffffLL) return fail(SXFIR_EINVAL, "call too large");       // (PBSPLIT: items)
-    if (geom.kind == GEOM_ICX) {
-        // complex taps: no keyed instance -- the count depends on the input alone and runs as the generic path's pass of its own
-        if (int rc = need_tap_table(p, TAPS_PASS8_CX, "interp_cx_pass_kernel")) return rc;
-        if (int rc = launch(p->k.interp_cx, grid, threads, c.st, interp_tile_args(p, c, geom, nullptr))) return rc;
-        if (key && key->hi > key->lo && key_pending) *key_pending = true;
-        return SXFIR_OK;
-    }
-    if (geom.kind == GEOM_IMIX) {
-        // translating plans: as the complex taps' -- the keying count is taken on the raw input, as a pass of its own
-        if (int rc = need_tap_table(p, TAPS_PASS8_CX, "interp_mix_pass_kernel")) return rc;
-        if (int rc = launch(p->k.imix, grid, threads, c.st, imix_tile_args(p, c, geom))) return rc;
+    if (geom.kind == GEOM_ICX || geom.kind == GEOM_IMIX) {
+        // complex taps, with or without a mixer: no keyed instance -- the count depends on the raw input alone and runs as the
+        // generic path's pass of its own
+        if (int rc = need_tap_table(p, TAPS_PASS8_CX, p->form->tiled)) return rc;
+        if (int rc = geom.kind == GEOM_ICX ? launch(p->k.interp_cx, grid, threads, c.st, interp_tile_args(p, c, geom, nullptr))
+                                           : launch(p->k.imix, grid, threads, c.st, imix_tile_args(p, c, geom))) return rc;
         if (key && key->hi > key->lo && key_pending) *key_pending = true;
         return SXFIR_OK;
     }
@@ -557,8 +537,7 @@ static int launch_call(sxfir_plan *p, const CallIO &c, bool *history_done, const
         if (p->kernel == SXFIR_KERNEL_TILED) return refuse_tiled(p);
         const long long first = p->mode == SXFIR_DECIMATE ? first_offset(p) : 0;        // (a rational plan is an interpolator)
         if (int rc = !p->mix_den ? launch(p->k.generic, grid, 256, c.st, generic_args(p, c, first))
-                     : p->mode == SXFIR_DECIMATE ? launch(p->k.mix_generic, grid, 256, c.st, mix_generic_args(p, c, first))
-                                                 : launch(p->k.imix_generic, grid, 256, c.st, imix_generic_args(p, c))) return rc;
+                                 : launch(p->k.mix_generic, grid, 256, c.st, mix_generic_args(p, c, first))) return rc;
         if (key && key->hi > key->lo && key_pending) *key_pending = true;    // counted by the caller once the call is certain to commit
         return SXFIR_OK;
     }

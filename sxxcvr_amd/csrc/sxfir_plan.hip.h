@@ -14,7 +14,8 @@
 // (sxfir_channelizer_os.hip.h: KIND_CHANNELIZER with ratio = bands / oversample), sxfir_create_synthesizer_os
 // (sxfir_synthesizer_os.hip.h: KIND_SYNTHESIZER with ratio = bands / oversample).  A complex-tap plan is a decimator whose taps_dev
 // holds a[0, ntaps) then b[0, ntaps) -- sxfir_create_translating (sxfir_translate.hip.h) makes one that carries a mixer (mix_dev,
-// mix_den, mix_s: its outputs turned by a table entry each, kernels and argument structs of their own); the band kinds are a /ratio decimator and a x ratio interpolator in everything about the stream.
+// mix_den, mix_s: its outputs turned by a table entry each, the mixer instances of the complex-tap kernels on argument structs of
+// their own); the band kinds are a /ratio decimator and a x ratio interpolator in everything about the stream.
 // sxfir_create_rational (sxfir_rational.hip.h): KIND_RATIONAL, a x ratio interpolator (ratio = up) of which every down-th output is
 // computed -- an interpolator's history and contract, positions and output counts of its own (rational_produced).
 enum PlanKind { KIND_REAL = 0, KIND_COMPLEX = 1, KIND_CHANNELIZER = 2, KIND_SYNTHESIZER = 3, KIND_RATIONAL = 4 };
@@ -45,25 +46,24 @@ typedef void (*SynTileFn)(sxfir::SynTileArgs);
 typedef void (*SynOsTileFn)(sxfir::SynOsTileArgs);
 typedef void (*MixGenericFn)(sxfir::MixGenericArgs);
 typedef void (*MixTileFn)(sxfir::MixTileArgs);
-typedef void (*InterpMixGenericFn)(sxfir::InterpMixGenericArgs);
 typedef void (*InterpMixTileFn)(sxfir::InterpMixTileArgs);
 struct KernelTable {
     const char *generic_name;    // the plan's generic kernel, as sxfir_launch_geometry reports it, and the instance: every plan of every
     GenericFn generic;           // kind has exactly one (generic_kernel below), the kernel of every call its form does not take
     DecimMultiFn dense;          // decim_dense_kernel (/8, /16, /32)
     DecimBlocksFn blocks[2];     // decim_blocks_kernel (/48, /96): [0] the walking form, [1] SPLIT, (tile, block) items
-    DecimTileFn tile, wide, cx;  // /4: decim4_tile_kernel, decim4_wide_kernel, decim4_cx_kernel (complex taps)
+    DecimTileFn tile, wide, cx;  // /4: decim4_tile_kernel, decim4_wide_kernel, decim4_cx_kernel<DecimTileArgs> (complex taps)
     InterpTileFn interp[2][2];   // [keyed][split]: interp8_pass_kernel; interp_tile_kernel on CF16 storage ([0][0] alone)
-    InterpTileFn interp_cx;      // complex-tap interpolators (include/sxfir_complex_tx.h): interp_cx_pass_kernel (x4 x 128, x8 x 256, CF32)
+    InterpTileFn interp_cx;      // complex-tap interpolators (include/sxfir_complex_tx.h): interp_cx_pass_kernel<.., InterpTileArgs> (x4 x 128, x8 x 256, CF32)
     ChanTileFn chan4;            // channelizer plans (include/sxfir_channelizer.h): chan4_kernel (4 bands x 128 taps, CF32)
     ChanTileFn chan4x2;          // 2x oversampled channelizer plans (include/sxfir_channelizer_os.h): chan4x2_kernel (4 bands x 128 taps, CF32)
     SynTileFn syn4;              // synthesizer plans (include/sxfir_synthesizer.h): synthesis4_kernel (4 bands x 128 taps, CF32)
     SynOsTileFn syn4x2;          // 2x oversampled synthesizer plans (include/sxfir_synthesizer_os.h): synthesis4x2_kernel (4 bands x 128 taps, CF32)
     DecimTileFn rat45;           // rational plans (include/sxfir_rational.h): resample45_kernel (4/5 x 128 taps, CF32)
-    MixGenericFn mix_generic;    // translating plans (include/sxfir_translate.h): decim_mix_generic_kernel, in the place of `generic`
-    MixTileFn mix;               // ... and decim4_mix_kernel (/4 x 128 complex taps, CF32)
-    InterpMixGenericFn imix_generic;   // translating interpolators (include/sxfir_translate_tx.h): interp_mix_generic_kernel, in the place of `generic`
-    InterpMixTileFn imix;        // ... and interp_mix_pass_kernel (x4 x 128, x8 x 256 complex taps, CF32)
+    MixGenericFn mix_generic;    // translating plans (include/sxfir_translate.h, include/sxfir_translate_tx.h), in the place of `generic`:
+                                 // decim_cx_generic_kernel<.., MixGenericArgs> or interp_mix_generic_kernel
+    MixTileFn mix;               // translating decimators: decim4_cx_kernel<MixTileArgs> (/4 x 128 complex taps, CF32)
+    InterpMixTileFn imix;        // translating interpolators: interp_cx_pass_kernel<.., InterpMixTileArgs> (x4 x 128, x8 x 256 complex taps, CF32)
 };
 
 // What the geometry and launch code needs to know of a tiled kernel family (FORM_* below).  A plan has at most one, settled at
@@ -166,25 +166,17 @@ static GenericKernel generic_kernel(int kind, int oversample, int mode, int fmt)
 }
 #undef SXFIR_GENERIC
 
-// Translating plans (include/sxfir_translate.h): decim_mix_generic_kernel on MixGenericArgs, the three instances of an RX kind
-static MixGenericFn mix_generic_kernel(int fmt)
+// Translating plans (include/sxfir_translate.h, include/sxfir_translate_tx.h), on MixGenericArgs: the complex-tap decimators'
+// generic kernel with the mixer, the three instances of an RX kind (reported as decim_mix_generic_kernel); interp_mix_generic_kernel,
+// the three of a TX kind
+static MixGenericFn mix_generic_kernel(int mode, int fmt)
 {
     using namespace sxfir;
-    return fmt == SXFIR_CF32 ? decim_mix_generic_kernel<CF32> : fmt == SXFIR_CF16 ? decim_mix_generic_kernel<CF16> : decim_mix_generic_kernel<S32, CF32>;
-}
-
-// Translating interpolators (include/sxfir_translate_tx.h): interp_mix_generic_kernel on InterpMixGenericArgs, the three instances
-// of a TX kind, and interp_mix_pass_kernel<QI, LL> on the complex-tap interpolators' shapes (sxfir_interp_mix.hip.h)
-static InterpMixGenericFn imix_generic_kernel(int fmt)
-{
-    using namespace sxfir;
+    if (mode == SXFIR_DECIMATE)
+        return fmt == SXFIR_CF32   ? decim_cx_generic_kernel<CF32, CF32, MixGenericArgs>
+               : fmt == SXFIR_CF16 ? decim_cx_generic_kernel<CF16, CF16, MixGenericArgs>
+                                   : decim_cx_generic_kernel<S32, CF32, MixGenericArgs>;
     return fmt == SXFIR_CF32 ? interp_mix_generic_kernel<CF32> : fmt == SXFIR_CF16 ? interp_mix_generic_kernel<CF16> : interp_mix_generic_kernel<CF32, S32>;
-}
-static InterpMixTileFn imix_kernel(int ratio)
-{
-    if (ratio == 4) return sxfir::interp_mix_pass_kernel<4, 4>;
-    if (ratio == 8) return sxfir::interp_mix_pass_kernel<2, 8>;
-    return nullptr;
 }
 
 // /8, /16, /32 with 32 taps per phase: decim_dense_kernel, non-temporal staging loads for the image rows no other tile reads
@@ -277,12 +269,13 @@ static InterpTileFn interp_kernel(int ratio, int fmt, bool keyed, bool split)
     return nullptr;
 }
 
-// Complex-tap interpolators, 32 taps per phase on CF32: interp_cx_pass_kernel<QI, LL> on the pass kernel's frame -- x4 with four
-// inputs per lane, x8 with two (sxfir_interp_cx.hip.h)
-static InterpTileFn interp_cx_kernel(int ratio)
+// Complex-tap interpolators, 32 taps per phase on CF32: interp_cx_pass_kernel<QI, LL, Args> on the pass kernel's frame -- x4 with
+// four inputs per lane, x8 with two (sxfir_interp_cx.hip.h); Args = InterpMixTileArgs: the translating interpolators' instances
+template <typename Args>
+static auto interp_cx_kernel(int ratio) -> void (*)(Args)
 {
-    if (ratio == 4) return sxfir::interp_cx_pass_kernel<4, 4>;
-    if (ratio == 8) return sxfir::interp_cx_pass_kernel<2, 8>;
+    if (ratio == 4) return sxfir::interp_cx_pass_kernel<4, 4, Args>;
+    if (ratio == 8) return sxfir::interp_cx_pass_kernel<2, 8, Args>;
     return nullptr;
 }
 
@@ -325,15 +318,17 @@ static const PlanForm FORM_IPASS_BLOCKS = {"interp8_pass_kernel", GEOM_IPASS, TI
 static const PlanForm FORM_ITILE = {"interp_tile_kernel", GEOM_ITILE, TILE_ITILE, 64, 1, 2, false, 4, 16, TAPS_SCALED};
 // ... x48 as three phase blocks of its x16 form, x96 of its x32 form (two whole lines per input and block)
 static const PlanForm FORM_ITILE_BLOCKS = {"interp_tile_kernel", GEOM_ITILE, TILE_ITILE, 64, 1, 2, false, 2, 16, TAPS_SCALED};
+// (FORM_MIX, FORM_IMIX: the label names the mixer INSTANCE of the shared kernel -- decim4_cx_kernel<MixTileArgs>,
+// interp_cx_pass_kernel<QI, LL, InterpMixTileArgs> -- as sxfir_launch_geometry has reported it since the translating plans came)
 // decim4_cx_kernel: complex taps, /4 x 128 on CF32, on the wide kernel's frame
 static const PlanForm FORM_CX = {"decim4_cx_kernel", GEOM_CX, 512, 64, 1, 2, true, 16, 8, TAPS_NONE};
-// decim4_mix_kernel: translating plans, /4 x 128 complex taps on CF32: decim4_cx_kernel's tile, threads, start rule (an output
+// decim4_cx_kernel<MixTileArgs>: translating plans, /4 x 128 complex taps on CF32: the complex-tap instance's tile, threads, start rule (an output
 // boundary, which at /4 is a stream position that is a multiple of 4: decim_geom), store rule and generations
 static const PlanForm FORM_MIX = {"decim4_mix_kernel", GEOM_MIX, 512, 64, 1, 2, true, 16, 8, TAPS_NONE};
 // interp_cx_pass_kernel: complex taps, x4 x 128 and x8 x 256 on CF32, on the pass kernel's frame and with its tiles and generations;
 // a small call keeps four tiles per workgroup as the other complex-tap and band kernels' do (a tile is twice the pass kernel's work)
 static const PlanForm FORM_ICX = {"interp_cx_pass_kernel", GEOM_ICX, TILE_IPASS, 64, 1, 2, true, 8, 8, TAPS_PASS8_CX};
-// interp_mix_pass_kernel: translating interpolators, x4 x 128 and x8 x 256 complex taps on CF32: interp_cx_pass_kernel's tile, threads,
+// interp_cx_pass_kernel<.., InterpMixTileArgs>: translating interpolators, x4 x 128 and x8 x 256 complex taps on CF32: the complex-tap instances' tile, threads,
 // start rule (any start), store rule, generations and tap tables
 static const PlanForm FORM_IMIX = {"interp_mix_pass_kernel", GEOM_IMIX, TILE_IPASS, 64, 1, 2, true, 8, 8, TAPS_PASS8_CX};
 
@@ -402,11 +397,10 @@ static void resolve_kernels(sxfir_plan *p)
     k.generic_name = g.name;
     k.generic = g.fn;
     if (p->mix_den) {           // a translating plan's generic kernel has an argument struct of its own
-        const bool rx = p->mode == SXFIR_DECIMATE;
-        k.generic_name = rx ? "decim_mix_generic_kernel" : "interp_mix_generic_kernel";
+        // (RX: the label of decim_cx_generic_kernel's mixer instances)
+        k.generic_name = p->mode == SXFIR_DECIMATE ? "decim_mix_generic_kernel" : "interp_mix_generic_kernel";
         k.generic = nullptr;
-        if (rx) k.mix_generic = mix_generic_kernel(p->fmt);
-        else k.imix_generic = imix_generic_kernel(p->fmt);
+        k.mix_generic = mix_generic_kernel(p->mode, p->fmt);
     }
     switch (p->form ? p->form->geom : GEOM_GENERIC) {
     case GEOM_CHAN4: k.chan4 = sxfir::chan4_kernel; break;
@@ -414,10 +408,10 @@ static void resolve_kernels(sxfir_plan *p)
     case GEOM_SYN4: k.syn4 = sxfir::synthesis4_kernel; break;
     case GEOM_SYN4X2: k.syn4x2 = sxfir::synthesis4x2_kernel; break;
     case GEOM_RAT45: k.rat45 = sxfir::resample45_kernel; break;
-    case GEOM_CX: k.cx = sxfir::decim4_cx_kernel; break;
-    case GEOM_MIX: k.mix = sxfir::decim4_mix_kernel; break;
-    case GEOM_ICX: k.interp_cx = interp_cx_kernel(p->ratio); break;
-    case GEOM_IMIX: k.imix = imix_kernel(p->ratio); break;
+    case GEOM_CX: k.cx = sxfir::decim4_cx_kernel<sxfir::DecimTileArgs>; break;
+    case GEOM_MIX: k.mix = sxfir::decim4_cx_kernel<sxfir::MixTileArgs>; break;
+    case GEOM_ICX: k.interp_cx = interp_cx_kernel<sxfir::InterpTileArgs>(p->ratio); break;
+    case GEOM_IMIX: k.imix = interp_cx_kernel<sxfir::InterpMixTileArgs>(p->ratio); break;
     case GEOM_MULTI:
         if (!p->blocks) k.dense = dense_kernel(p->ratio, p->fmt);
         for (int split = 0; split < 2; ++split) k.blocks[split] = blocks_kernel(p->blocks, p->fmt, split != 0);

@@ -1,15 +1,28 @@
-// Frequency-translating decimators of the C ABI (include/sxfir_translate.h): the rotation table, plan creation and the plan query.
-// The plan is a KIND_COMPLEX decimator that carries a mixer (mix_dev, mix_den, mix_s: sxfir_plan.hip.h): created through the
-// frame of sxfir_plan.hip.h with the complex creator's history and contract, the kernel table gives it decim4_mix_kernel (FORM_MIX)
-// and decim_mix_generic_kernel, launch_call (sxfir_launch.hip.h) hands them the call's phase; every other entry point takes it as
-// the complex-tap decimator it is.  Included by sxfir.hip last; not a stand-alone translation unit.
+// Frequency-translating plans of the C ABI, both directions (include/sxfir_translate.h, include/sxfir_translate_tx.h): the rotation
+// table, plan creation and the plan queries.  The plan is a KIND_COMPLEX decimator or interpolator that carries a mixer (mix_dev,
+// mix_den, mix_s: sxfir_plan.hip.h; the plan's mode tells the two apart), created by create_complex_plan (sxfir_complex.hip.h): the
+// kernel table gives it the mixer instances of the complex-tap kernels (FORM_MIX, FORM_IMIX) and the translating generic kernels,
+// launch_call (sxfir_launch.hip.h) hands them the call's phase; every other entry point takes it as the complex-tap plan it is.
+// Included by sxfir.hip behind sxfir_complex.hip.h; not a stand-alone translation unit.
 #pragma once
 
 static const int MIX_DEN_MAX = 65536;          // the table at most 512 KiB; every index product of the kernels fits 32 bits
 
+// The band centre of a translating plan of direction `mode`; 0 / 0 for every other plan (the other direction's too: each query
+// answers for its own header's plans)
+static int plan_translation(const sxfir_plan *p, int mode, int *num, int *den)
+{
+    if (!p || !num || !den) return fail(SXFIR_EINVAL, "NULL argument");
+    const bool mine = p->mix_den && p->mode == mode;
+    *num = mine ? p->mix_num : 0;
+    *den = mine ? p->mix_den : 0;
+    return SXFIR_OK;
+}
+
 extern "C" {
 
 int sxfir_translate_abi_version(void) { return SXFIR_TRANSLATE_ABI_VERSION; }
+int sxfir_translate_tx_abi_version(void) { return SXFIR_TRANSLATE_TX_ABI_VERSION; }
 
 int sxfir_design_rotator(int den, float *w_iq)
 {
@@ -34,34 +47,19 @@ int sxfir_create_translating(sxfir_plan **out, const float *taps_iq, int ntaps, 
 {
     if (int rc = check_create_args(out, taps_iq, SXFIR_DECIMATE, ntaps, "ratio", ratio, nchan, fmt)) return rc;
     if (den < 1 || den > MIX_DEN_MAX) return fail(SXFIR_EINVAL, "den %d out of range (1 .. %d)", den, MIX_DEN_MAX);
-    sxfir_plan *p = nullptr;
-    if (int rc = new_plan(&p, KIND_COMPLEX, SXFIR_DECIMATE, ntaps, ratio, nchan, fmt, device)) return rc;
-    p->hist_len = (ntaps + 1) & ~1;
-    real_tap_contract(p);
-    p->mix_den = den;
-    p->mix_num = (int)((((long long)num % den) + den) % den);
-    p->mix_s = (int)((long long)p->mix_num * ratio % den);
-    set_form(p, fmt == SXFIR_CF32 && ratio == 4 && ntaps == 128 ? &FORM_MIX : nullptr);
-    resolve_form(p);
-
-    // planar on the device, as a complex-tap plan's: a[0, ntaps) then b[0, ntaps); the rotation table of mix_den entries is
-    // plan_to_device's (sxfir_design_rotator)
-    std::vector<float> planar(2 * (size_t)ntaps);
-    for (int k = 0; k < ntaps; ++k) {
-        planar[(size_t)k] = taps_iq[2 * k];
-        planar[(size_t)ntaps + (size_t)k] = taps_iq[2 * k + 1];
-    }
-    return plan_to_device(out, p, planar.data(), planar.size());
+    return create_complex_plan(out, SXFIR_DECIMATE, taps_iq, ntaps, ratio, num, den, nchan, fmt, device);
 }
 
-int sxfir_plan_translation(const sxfir_plan *p, int *num, int *den)
+int sxfir_create_translating_interpolator(sxfir_plan **out, const float *taps_iq, int ntaps, int ratio, int num, int den, int nchan,
+                                          int fmt, int device)
 {
-    if (!p || !num || !den) return fail(SXFIR_EINVAL, "NULL argument");
-    // (a translating interpolator carries a mixer too: include/sxfir_translate_tx.h, sxfir_plan_translation_tx)
-    const bool mine = p->mix_den && p->mode == SXFIR_DECIMATE;
-    *num = mine ? p->mix_num : 0;
-    *den = mine ? p->mix_den : 0;
-    return SXFIR_OK;
+    if (int rc = check_create_args(out, taps_iq, SXFIR_INTERPOLATE, ntaps, "ratio", ratio, nchan, fmt)) return rc;
+    if (ntaps % ratio) return fail(SXFIR_EINVAL, "interpolator needs ntaps %% ratio == 0 (%d, %d)", ntaps, ratio);
+    if (den < 1 || den > MIX_DEN_MAX) return fail(SXFIR_EINVAL, "den %d out of range (1 .. %d)", den, MIX_DEN_MAX);
+    return create_complex_plan(out, SXFIR_INTERPOLATE, taps_iq, ntaps, ratio, num, den, nchan, fmt, device);
 }
+
+int sxfir_plan_translation(const sxfir_plan *p, int *num, int *den) { return plan_translation(p, SXFIR_DECIMATE, num, den); }
+int sxfir_plan_translation_tx(const sxfir_plan *p, int *num, int *den) { return plan_translation(p, SXFIR_INTERPOLATE, num, den); }
 
 }  // extern "C"

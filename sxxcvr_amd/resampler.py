@@ -240,6 +240,16 @@ class Resampler(_Plan):
         self._ck(create(C.byref(self._plan), mode, taps.ctypes.data_as(C.c_void_p), taps.size,
                         int(ratio), int(nchan), self.fmt, int(device)))
 
+    def _create_complex(self, create, mode, taps, ratio, extra, nchan, fmt, device, profiling):
+        """The creators of the one-direction complex-tap plans: create(&plan, taps, ntaps, ratio, *extra, nchan, fmt, device)."""
+        self._lib = load_sxfir(profiling)
+        self.profiling = bool(profiling)
+        self._plan = C.c_void_p()
+        taps = np.ascontiguousarray(taps, dtype=np.complex64)
+        self.mode, self.ratio, self.nchan, self.fmt, self.ntaps = mode, int(ratio), int(nchan), _FMT[fmt], taps.size
+        self._ck(getattr(self._lib, create)(C.byref(self._plan), taps.ctypes.data_as(C.c_void_p), taps.size, int(ratio),
+                                            *[int(e) for e in extra], int(nchan), self.fmt, int(device)))
+
     @property
     def complex_taps(self):
         """True for a plan with complex taps (sxfir_taps_are_complex)."""
@@ -375,33 +385,15 @@ class ComplexInterpolator(Resampler):
     is an interpolator plan (mode INTERPOLATE) in everything else: the same methods as Resampler."""
 
     def __init__(self, taps, ratio, nchan=1, fmt="CF32", device=-1, profiling=False):
-        self._lib = load_sxfir(profiling)
-        self.profiling = bool(profiling)
-        self._plan = C.c_void_p()
-        taps = np.ascontiguousarray(taps, dtype=np.complex64)
-        self.mode, self.ratio, self.nchan, self.fmt, self.ntaps = INTERPOLATE, int(ratio), int(nchan), _FMT[fmt], taps.size
-        self._ck(self._lib.sxfir_create_complex_interpolator(C.byref(self._plan), taps.ctypes.data_as(C.c_void_p), taps.size,
-                                                             int(ratio), int(nchan), self.fmt, int(device)))
+        self._create_complex("sxfir_create_complex_interpolator", INTERPOLATE, taps, ratio, (), nchan, fmt, device, profiling)
 
 
-class TranslatingDecimator(Resampler):
-    """A frequency-translating decimator (include/sxfir_translate.h): the complex-tap decimator Resampler(DECIMATE, taps, ratio) with
-    output m turned by exp(-2j pi (m * s mod den) / den), s = num * ratio mod den, m the absolute output index -- the band centred at
-    num / den cycles per input sample (taps = design_bandpass(ntaps, ratio, num, den)) lands at 0 Hz of the output in one pass, on or
-    off the output raster.  The plan is a decimator plan with complex taps in everything else: the same methods as Resampler."""
-
-    def __init__(self, taps, ratio, num, den, nchan=1, fmt="CF32", device=-1, profiling=False):
-        self._lib = load_sxfir(profiling)
-        self.profiling = bool(profiling)
-        self._plan = C.c_void_p()
-        taps = np.ascontiguousarray(taps, dtype=np.complex64)
-        self.mode, self.ratio, self.nchan, self.fmt, self.ntaps = DECIMATE, int(ratio), int(nchan), _FMT[fmt], taps.size
-        self._ck(self._lib.sxfir_create_translating(C.byref(self._plan), taps.ctypes.data_as(C.c_void_p), taps.size, int(ratio),
-                                                    int(num), int(den), int(nchan), self.fmt, int(device)))
+class _Translating:
+    """What the two translating plans answer alike; `_query` names the plan query of the class's header."""
 
     def _translation(self):
         n, d = C.c_int(), C.c_int()
-        self._ck(self._lib.sxfir_plan_translation(self._plan, C.byref(n), C.byref(d)))
+        self._ck(getattr(self._lib, self._query)(self._plan, C.byref(n), C.byref(d)))
         return n.value, d.value
 
     @property
@@ -414,35 +406,30 @@ class TranslatingDecimator(Resampler):
         return self._translation()[1]
 
 
-class TranslatingInterpolator(Resampler):
+class TranslatingDecimator(Resampler, _Translating):
+    """A frequency-translating decimator (include/sxfir_translate.h): the complex-tap decimator Resampler(DECIMATE, taps, ratio) with
+    output m turned by exp(-2j pi (m * s mod den) / den), s = num * ratio mod den, m the absolute output index -- the band centred at
+    num / den cycles per input sample (taps = design_bandpass(ntaps, ratio, num, den)) lands at 0 Hz of the output in one pass, on or
+    off the output raster.  The plan is a decimator plan with complex taps in everything else: the same methods as Resampler."""
+
+    _query = "sxfir_plan_translation"
+
+    def __init__(self, taps, ratio, num, den, nchan=1, fmt="CF32", device=-1, profiling=False):
+        self._create_complex("sxfir_create_translating", DECIMATE, taps, ratio, (num, den), nchan, fmt, device, profiling)
+
+
+class TranslatingInterpolator(Resampler, _Translating):
     """A frequency-translating interpolator (include/sxfir_translate_tx.h), the way back from TranslatingDecimator: the complex-tap
     interpolator ComplexInterpolator(taps, ratio) with input m turned by exp(+2j pi (m * s mod den) / den), s = num * ratio mod den, m
     the absolute input index, where it is read -- a base-band stream lands centred at num / den cycles per output sample
     (taps = design_bandpass(ntaps, ratio, num, den, gain=ratio)) in one pass, on or off the x ratio raster.  History is raw samples.
     The plan is an interpolator plan with complex taps in everything else: the same methods as Resampler."""
 
+    _query = "sxfir_plan_translation_tx"
+
     def __init__(self, taps, ratio, num, den, nchan=1, fmt="CF32", device=-1, profiling=False):
-        self._lib = load_sxfir(profiling)
-        self.profiling = bool(profiling)
-        self._plan = C.c_void_p()
-        taps = np.ascontiguousarray(taps, dtype=np.complex64)
-        self.mode, self.ratio, self.nchan, self.fmt, self.ntaps = INTERPOLATE, int(ratio), int(nchan), _FMT[fmt], taps.size
-        self._ck(self._lib.sxfir_create_translating_interpolator(C.byref(self._plan), taps.ctypes.data_as(C.c_void_p), taps.size,
-                                                                 int(ratio), int(num), int(den), int(nchan), self.fmt, int(device)))
-
-    def _translation(self):
-        n, d = C.c_int(), C.c_int()
-        self._ck(self._lib.sxfir_plan_translation_tx(self._plan, C.byref(n), C.byref(d)))
-        return n.value, d.value
-
-    @property
-    def num(self):
-        """The band centre's numerator, reduced into [0, den)."""
-        return self._translation()[0]
-
-    @property
-    def den(self):
-        return self._translation()[1]
+        self._create_complex("sxfir_create_translating_interpolator", INTERPOLATE, taps, ratio, (num, den), nchan, fmt, device,
+                             profiling)
 
 
 class RationalResampler(Resampler):

@@ -74,7 +74,7 @@ def tile_walk_model(num, den, ratio, n_groups, n_tiles, consumed=0):
     chunks = (tile_in + 32) // 2
     nload = (chunks + 63) // 64
     t = back_step(num, den, ratio)
-    phase = ((int(consumed) - 32) % den) * t % den               # tx_mixer_of(p, 32): Python's modulo is the mathematical one
+    phase = ((int(consumed) - 32) % den) * t % den               # mixer_of(.., consumed, 32): Python's modulo is the mathematical one
     lane_step = 2 * t % den
     instr_step = 128 * t % den
     tile_step = tile_in * t % den

@@ -71,12 +71,13 @@ def test_shipped_code_object_of_the_complex_interpolators():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import shipped_isa
     rows = shipped_isa.kernels()
-    tiled = {r["name"]: r for r in rows if "interp_cx_pass_kernel" in r["name"]}
-    assert sorted(tiled) == ["interp_cx_pass_kernel<2, 8>", "interp_cx_pass_kernel<4, 4>"], sorted(tiled)
+    # (the kernel's other instances, <.., sxfir::InterpMixTileArgs>, are the translating interpolators': tests/test_mix_tx_host.py)
+    tiled = {r["name"]: r for r in rows if "interp_cx_pass_kernel" in r["name"] and r["name"].endswith(", sxfir::InterpTileArgs>")}
+    assert sorted(tiled) == ["interp_cx_pass_kernel<2, 8, sxfir::InterpTileArgs>", "interp_cx_pass_kernel<4, 4, sxfir::InterpTileArgs>"], sorted(tiled)
     # the real-tap pass instance of the same ratio in the same code object: unkeyed, CF32, <QI, false, false, true, L, L, false>
     real = {r["name"]: r for r in rows if r["name"].startswith("interp8_pass_kernel<")}
     for name, t in tiled.items():
-        qi, ll = [int(v) for v in name.split("<")[1].rstrip(">").split(",")]
+        qi, ll = [int(v) for v in name.split("<")[1].split(",")[:2]]
         base = real["interp8_pass_kernel<%d, false, false, true, %d, %d, false>" % (qi, ll, ll)]
         print(t)
         assert t["scratch_bytes"] == 0 and t["v_mfma"] == 0 and t["s_barrier"] == 0, t

@@ -221,7 +221,8 @@ def test_shipped_code_object_of_the_mix_kernels():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import shipped_isa
     rows = shipped_isa.kernels()
-    tiled = [r for r in rows if "decim4_mix_kernel" in r["name"]]
+    # the mixer instance of the complex-tap decimators' kernel (the launch geometry's decim4_mix_kernel)
+    tiled = [r for r in rows if r["name"] == "decim4_cx_kernel<sxfir::MixTileArgs>"]
     assert len(tiled) == 1, [r["name"] for r in rows]
     t = tiled[0]
     print(t)
@@ -229,9 +230,11 @@ def test_shipped_code_object_of_the_mix_kernels():
     assert t["v_pk_fma_f32"] == 2048, t
     assert t["lds_bytes"] == 18496 and t["vgpr"] <= 256 and t["scratch_bytes"] == 0, t
     assert t["v_mfma"] == 0 and t["s_barrier"] == 0, t
-    generic = sorted(r["name"] for r in rows if r["name"].startswith("decim_mix_generic_kernel<"))
-    assert generic == ["decim_mix_generic_kernel<sxfir::CF16, sxfir::CF16>", "decim_mix_generic_kernel<sxfir::CF32, sxfir::CF32>",
-                       "decim_mix_generic_kernel<sxfir::S32, sxfir::CF32>"], generic
+    # ... and of their generic kernel (the launch geometry's decim_mix_generic_kernel)
+    generic = sorted(r["name"] for r in rows if r["name"].startswith("decim_cx_generic_kernel<") and r["name"].endswith(", sxfir::MixGenericArgs>"))
+    assert generic == ["decim_cx_generic_kernel<sxfir::CF16, sxfir::CF16, sxfir::MixGenericArgs>",
+                       "decim_cx_generic_kernel<sxfir::CF32, sxfir::CF32, sxfir::MixGenericArgs>",
+                       "decim_cx_generic_kernel<sxfir::S32, sxfir::CF32, sxfir::MixGenericArgs>"], generic
     for r in rows:
-        if "decim_mix_generic_kernel" in r["name"]:
+        if r["name"] in generic:
             assert r["scratch_bytes"] == 0 and r["v_mfma"] == 0, r

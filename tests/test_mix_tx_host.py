@@ -169,16 +169,17 @@ def test_shipped_code_object_of_the_translating_interpolators():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import shipped_isa
     rows = shipped_isa.kernels()
-    tiled = {r["name"]: r for r in rows if "interp_mix_pass_kernel" in r["name"]}
-    assert sorted(tiled) == ["interp_mix_pass_kernel<2, 8>", "interp_mix_pass_kernel<4, 4>"], sorted(tiled)
+    # the mixer instances of the complex-tap interpolators' kernel (the launch geometry's interp_mix_pass_kernel)
+    tiled = {r["name"]: r for r in rows if "interp_cx_pass_kernel" in r["name"] and r["name"].endswith(", sxfir::InterpMixTileArgs>")}
+    assert sorted(tiled) == ["interp_cx_pass_kernel<2, 8, sxfir::InterpMixTileArgs>", "interp_cx_pass_kernel<4, 4, sxfir::InterpMixTileArgs>"], sorted(tiled)
     real = {r["name"]: r for r in rows if r["name"].startswith("interp8_pass_kernel<")}
     cx = {r["name"]: r for r in rows if r["name"].startswith("interp_cx_pass_kernel<")}
     for name, t in tiled.items():
-        qi, ll = [int(v) for v in name.split("<")[1].rstrip(">").split(",")]
+        qi, ll = [int(v) for v in name.split("<")[1].split(",")[:2]]
         base = real["interp8_pass_kernel<%d, false, false, true, %d, %d, false>" % (qi, ll, ll)]
         print(t)
         assert t["scratch_bytes"] == 0 and t["v_mfma"] == 0 and t["s_barrier"] == 0 and t["vgpr"] <= 256, t
-        assert t["lds_bytes"] == cx["interp_cx_pass_kernel<%d, %d>" % (qi, ll)]["lds_bytes"], t
+        assert t["lds_bytes"] == cx["interp_cx_pass_kernel<%d, %d, sxfir::InterpTileArgs>" % (qi, ll)]["lds_bytes"], t
         # two chains per window read: twice the real pass instance's packed FMAs, every one with a scalar tap
         assert t["v_pk_fma_f32"] == 2 * base["v_pk_fma_f32"] and t["scalar_tap_fmas"] == t["v_pk_fma_f32"], t
         # the counted wait's premises, read off the disassembly as for interp_cx_pass_kernel: the hand-written wait is the first

@@ -18,13 +18,13 @@ samples, sxfir_time_interpolate; the complex plan (interp_cx_pass_kernel) and th
 TFLOP/s (real: 128 flop per output sample = 32 taps x 2 components x 2 flop; complex: 256), and per round the ratio complex / real
 -- 2.0 is "two real passes", without the combining pass those would still need.  profiles/cx_interp.txt keeps the output.
 
-`mix`: the translating /4 x 128 plan (include/sxfir_translate.h, decim4_mix_kernel) against the route it replaces at that route's
+`mix`: the translating /4 x 128 plan (include/sxfir_translate.h, decim4_cx_kernel<MixTileArgs>: the launch geometry's decim4_mix_kernel) against the route it replaces at that route's
 lower bound -- per round (a) the translating plan, (b) the complex plan of the same taps (decim4_cx_kernel), (c) a device-to-device
 copy of the n / 4 output samples: 8 B read and 8 B written per output, the traffic floor of any separate rotation pass.  The
 condition is (a) < (b) + (c) in every round; (a) / (b) per round and its median say what the fused rotation costs.
 profiles/cx_mix.txt keeps the output.
 
-`mixtx`: the translating interpolators (include/sxfir_translate_tx.h, interp_mix_pass_kernel) the same way -- x4 x 128 and x8 x 256,
+`mixtx`: the translating interpolators (include/sxfir_translate_tx.h, interp_cx_pass_kernel<.., InterpMixTileArgs>: the launch geometry's interp_mix_pass_kernel) the same way -- x4 x 128 and x8 x 256,
 n CF32 OUTPUT samples, sxfir_time_interpolate, per round (a) the translating plan, (b) the ComplexInterpolator plan of the same taps
 (interp_cx_pass_kernel), (c) a device-to-device copy of the call's n / ratio INPUT samples: the traffic floor of the separate
 rotation pass the old route needs in front of (b).  The condition is (a) < (b) + (c) in every round.  profiles/cx_mix_tx.txt keeps

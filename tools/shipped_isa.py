@@ -4,8 +4,9 @@
 
 (`chan4` lists the channelizer kernels of DESIGN.md 5.6, `chan4x2` the oversampled channelizer's of 5.8, `synthesis` the synthesizer's,
 `synthesis4x2` the oversampled synthesizer's of 5.9, `interp_cx` the complex-tap interpolators' of 5.10, `resample` the rational
-resamplers' of 5.11, `decim_mix` / `decim4_mix` the translating decimators' of 5.12, `interp_mix` the translating interpolators' of
-5.13.)
+resamplers' of 5.11, `MixTileArgs` / `MixGenericArgs` the translating decimators' of 5.12 -- the mixer instances of decim4_cx_kernel and
+decim_cx_generic_kernel --, `InterpMixTileArgs` / `interp_mix` the translating interpolators' of 5.13 -- the mixer instances of
+interp_cx_pass_kernel, and interp_mix_generic_kernel.)
 
 Registers / LDS / scratch come from the code object's metadata notes, instruction counts from its disassembly:
 v_pk_fma_f32, ds_read_b128, global_load_lds_dwordx4 (and how many of those carry `nt`), s_barrier, v_mfma, DPP and
@@ -87,9 +88,9 @@ def kernels(lib=None):
                     r["counted_wait"] = cw
             else:
                 r["phase_block_wait"] = phase_block_wait(body)
-        # the pass kernel's frame: the same wait at the loop head (interp_mix_pass_kernel: the compiler's own waits for the table
-        # reads follow it in code order; `n` is the first vmcnt(N > 0) of the kernel, the hand-written one)
-        if "interp_cx_pass_kernel" in r["name"] or "interp_mix_pass_kernel" in r["name"]:
+        # the pass kernel's frame: the same wait at the loop head (the mixer instances, <.., InterpMixTileArgs>: the compiler's own
+        # waits for the table reads follow it in code order; `n` is the first vmcnt(N > 0) of the kernel, the hand-written one)
+        if "interp_cx_pass_kernel" in r["name"]:
             cw = counted_wait(body)
             if cw:
                 r["counted_wait"] = cw
