@@ -12,7 +12,8 @@ import sxxcvr_amd
 from sxxcvr_amd import ComplexInterpolator, Resampler, TranslatingDecimator, TranslatingInterpolator, design_bandpass
 from sxxcvr_amd.resampler import DECIMATE, INTERPOLATE, KERNEL_AUTO, KERNEL_GENERIC, KERNEL_TILED
 from gpu_util import random_taps_cx
-from mix_tx_cases import bound, mix_tx_f64, mix_tx_ref, rotate_in_f32, step
+import rate_cases as rc
+from mix_tx_cases import back_step, bound, mix_tx_f64, mix_tx_ref, rotate_in_f32, step
 from rational_cases import gaussian_stream
 
 pytestmark = pytest.mark.gpu
@@ -245,6 +246,101 @@ def test_more_tiles_than_resident_workgroups(oracle, L, num, den, s4):
     assert g["kernel"] == TILED and g["n_tiles"] == resident + 3 and g["workgroups"] == resident, g
     rig = Rig(oracle, streams(1, n, 19), pad=0)
     same(rig.call(plan, 0, n, TILED), rig.ref(H[L], L, 2, num, den, threads=oracle.max_threads()), "resident + 3 tiles")
+
+
+def _walk_size(n_tiles, L):
+    """Inputs of a call of n_tiles tiles whose last tile is ragged (half a tile and five samples)."""
+    return (n_tiles - 1) * TILE_IN[L] + TILE_IN[L] // 2 + 5
+
+
+@pytest.mark.parametrize("num,den", [(3, 7), (1, 3), (65535, 65536), (65534, 65535)])
+@pytest.mark.parametrize("L", [4, 8])
+def test_a_waves_third_tile(oracle, L, num, den):
+    """2 resident + 3 tiles under a forced TILED: still one generation of waves, so every wave walks to a second tile and three to a
+    THIRD -- `stride_step` applied twice and wrapped twice, a second interior-to-interior hand-over under the counted wait with the
+    table registers in flight, the history carried over by a wave on its third tile.  (3, 7) and (1, 3): more tiles than table
+    entries; (65535, 65536) and (65534, 65535): the smallest steps t above 0 on the largest tables (t = L and t = L)."""
+    plan = plan_of(L, num, den, KERNEL_TILED)
+    resident = plan.geometry(TILE_IN[L])["resident"]
+    n = _walk_size(2 * resident + 3, L)
+    g = plan.geometry(n)
+    print("x%d %d/%d: resident %d, workgroups %d, %d tiles, %d inputs, %d outputs" % (L, num, den, resident, g["workgroups"], g["n_tiles"], n, L * n))
+    assert g["kernel"] == TILED and g["workgroups"] == resident and g["n_tiles"] == 2 * resident + 3, g
+    assert (g["n_tiles"] - 1) % resident == 2                   # (the last tile is the third of the wave that carries the history over)
+    rig = Rig(oracle, streams(1, n + TILE_IN[L] + 8, 19), pad=0)
+    ref = rig.ref(H[L], L, 2, num, den, threads=oracle.max_threads())
+    same(rig.call(plan, 0, n, TILED), ref[:, :2 * L * n], "2 resident + 3 tiles")
+    same(rig.call(plan, n, TILE_IN[L] + 8, TILED), ref[:, 2 * L * n:], "the call after it: the history a third tile's wave left")
+
+
+@pytest.mark.parametrize("L,skew", [(4, 1), (8, 3)])
+def test_more_tiles_than_workgroups_three_channels(oracle, L, skew):
+    """Three channels: the grid per channel is a third of the resident waves -- at x4 no multiple of 8, so the tiles are dealt plainly
+    strided (682 of 2048 on the MI355X; x8: 1024 of 3072, XCD-blocked) -- and a call of that many tiles + 4 per channel has more
+    tiles than waves at a figure the one-channel tests never reach.  The input is a view `skew` samples into rows of an odd, padded stride (the DMA source of every other row is 8-byte
+    aligned only), the output rows lie an even, padded stride apart."""
+    num, den = 123, 1000
+    plan = plan_of(L, num, den, KERNEL_TILED, nchan=3)
+    per = plan.geometry(TILE_IN[L])["resident"] // 3
+    n = _walk_size(per + 4, L)
+    g = plan.geometry(n)
+    G = g["workgroups"] // 3
+    print("x%d, 3 channels: resident %d, %d workgroups per channel, %d tiles per channel, %d inputs per channel" % (L, g["resident"], G, g["n_tiles"], n))
+    assert g["kernel"] == TILED and g["workgroups"] == 3 * G and G == per and g["n_tiles"] == G + 4 and G < g["n_tiles"], g
+    rig = Rig(oracle, streams(3, skew + n, 29), pad=41 - (skew + n) % 2)
+    assert rig.stride % 2 == 1 and rig.stride > skew + n
+    ref = np.stack([rig.words(mix_tx_ref(oracle, H[L], L, rig.x[c, skew:], 2, num, den, threads=oracle.max_threads())) for c in range(3)])
+    same(rig.call(plan, skew, n, TILED), ref, "three channels, groups + 4 tiles each")
+
+
+PLACED = [((1 << 40) + 21, 64, "max", 65535), ((1 << 40) + 21, 64, "one", 7), (5, 40, "one", 65535)]       # (rate_cases.MIXERS' classes)
+
+
+@pytest.mark.parametrize("where,lead,cls,den", PLACED)
+@pytest.mark.parametrize("L", [4, 8])
+def test_more_tiles_than_resident_workgroups_placed(oracle, L, where, lead, cls, den):
+    """resident + 3 tiles from a PLACED, odd position, the samples in front handed to sxfir_set_history raw: the 64-bit reduction of
+    `mix.phase`, the image's halo 32 samples in front of the call and `stride_step` in one call.  From 2^40 + 21 on den 65535 (t = 1,
+    the smallest step) and den 7 (t = 6, more tiles than entries); from position 5 with 40 history samples on den 65535 with s = 1 (the
+    largest t, 65534): the halo's indices -27 .. 4 are reduced from below 0 while the walk wraps at nearly every step."""
+    import torch
+    num = rc.mixer_num(cls, den, None, L)
+    t = back_step(num, den, L)
+    assert t == {"max": 1, "one": den - 1}[cls] and (where - lead) * t % den != 0       # (the far phase is not the near one)
+    plan = plan_of(L, num, den, KERNEL_TILED)
+    resident = plan.geometry(TILE_IN[L])["resident"]
+    n = _walk_size(resident + 3, L)
+    rig = Rig(oracle, streams(1, lead + n, 23), pad=0)
+    plan.set_history_ptr(rig.xg.data_ptr(), lead, rig.stride, torch.cuda.current_stream().cuda_stream)
+    plan.set_position(where)
+    assert plan.position == (where, L * where)
+    g = plan.geometry(n)
+    print("x%d %d/%d from %d: resident %d, workgroups %d, %d tiles, %d inputs" % (L, num, den, where, resident, g["workgroups"], g["n_tiles"], n))
+    assert g["kernel"] == TILED and g["workgroups"] == resident and g["n_tiles"] == resident + 3, g
+    ref = rig.ref(H[L], L, 2, num, den, first=lead, m_first=where, threads=oracle.max_threads())
+    same(rig.call(plan, lead, n, TILED), ref, "resident + 3 tiles from input %d" % where)
+
+
+@pytest.mark.parametrize("ntaps,L,fmt,kernel", [(128, 4, "CF32", KERNEL_GENERIC), (35, 5, "CF32", KERNEL_AUTO), (96, 3, "CF16", KERNEL_AUTO)])
+def test_generic_call_longer_than_the_table(oracle, ntaps, L, fmt, kernel):
+    """ONE generic call of den + 300 inputs on den = 65535 with the largest step the ratio allows (s = gcd(L, den): t = 65534 at x4,
+    65530 at x5, 65532 at x3).  `mix.phase` carries the absolute part of the index, so interp_mix_generic_kernel sees the call-local
+    q alone, and only a call of more than den inputs makes `q % den` wrap; only a large t brings `(q % den) * t` near its stated
+    limit of 65535^2.  Without the reduction q * t passes 2^32 from q = 65539 on, and 2^32 = 1 modulo 65535: every later sample would
+    take the neighbouring table entry.  den = 65536 would prove nothing: 2^32 = 0 modulo a power of two, the wrapped product has the
+    right remainder."""
+    den = 65535
+    num = rc.mixer_num("one", den, None, L)
+    t = back_step(num, den, L)
+    n = den + 300
+    assert t == den - np.gcd(L, den) and (den - 1) * t < 2 ** 32 <= (n - 1) * t and 2 ** 32 % den == 1 and 2 ** 32 % 65536 == 0
+    h = H[4] if (ntaps, L) == (128, 4) else random_taps_cx(ntaps, 9)
+    rig = Rig(oracle, streams(1, n, 31), fmt)
+    plan = TranslatingInterpolator(h, L, num, den, fmt=fmt)
+    plan.set_kernel(kernel)
+    jsplit = plan.contract[0]
+    assert jsplit == (2 if (ntaps // L) % 2 == 0 else 1)
+    same(rig.stream(plan, [n], [GENERIC]), rig.ref(h, L, jsplit, num, den, threads=oracle.max_threads()), "one generic call of den + 300 inputs")
 
 
 # ---- channels and alignment -------------------------------------------------------------------------------------------------------

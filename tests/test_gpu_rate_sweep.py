@@ -1,8 +1,9 @@
-"""Seeded sweep of the frequency-translating decimators and the rational resamplers on the GPU (tests/rate_cases.py), as
-tests/test_gpu_band_sweep.py sweeps the six band kinds: any legal tap count, ratio, mixer, channel count, format, call split, kernel
-request, placement of input and output and START POSITION in the 64-bit stream must give the bits of the float32 reference of the
-whole stream, move the plan's position by the arithmetic, take the kernel the headers say, refuse what they say is refused, and write
-nothing but the call's outputs."""
+"""Seeded sweep of the frequency-translating decimators, the rational resamplers and the frequency-translating interpolators on the
+GPU (tests/rate_cases.py: "translate", "rational", "translate_tx"), as tests/test_gpu_band_sweep.py sweeps the six band kinds: any
+legal tap count, ratio, mixer, channel count, format, call split, kernel request, placement of input and output and START POSITION
+in the 64-bit stream must give the bits of the float32 reference of the whole stream, move the plan's position by the arithmetic,
+take the kernel the headers say, refuse what they say is refused, and write nothing but the call's outputs.  The translating
+interpolators' S32 plans store convert_tx wire words under a keying threshold that leaves both keying states in the reference."""
 import numpy as np
 import pytest
 
@@ -25,11 +26,20 @@ def test_rate_sweep(oracle, kind, case):
     nchan = case.nchan
     h = rc.taps_of(kind, case)
     raw, xs = rc.stream_input(kind, case, oracle)
-    want = [rc.stored_words(oracle, case.fmt, rc.reference(kind, oracle, case, h, xs[c])) for c in range(nchan)]
+    refs = [rc.reference(kind, oracle, case, h, xs[c]) for c in range(nchan)]
     plan = rc.make_plan(kind, case, h)
     assert tuple(plan.contract) == tuple(rc.contract(kind, case)) and plan.contract.rot == 0
-    if kind == "translate":
+    if kind != "rational":
         assert (plan.num, plan.den) == (case.num % case.den, case.den)
+    thr2 = None
+    if case.fmt == "S32" and K.tx:
+        # wire words out: a threshold with outputs on both sides of the keying rule
+        thr2 = rc.keying_threshold(refs[0])
+        plan.set_tx_threshold(float(thr2))
+    want = [rc.stored_words(oracle, case.fmt, r, thr2) for r in refs]
+    if thr2 is not None:
+        keyed = (np.concatenate(want).view(np.int32)[:, 0] & 3) == 3
+        assert 0 < keyed.sum() < keyed.size, (case.ident, int(keyed.sum()), keyed.size)
     wi, wo = raw.shape[-1], want[0].shape[-1]              # 32-bit words per input / output sample
     stream = torch.cuda.current_stream().cuda_stream
     lead = rc.lead_of(case)
@@ -102,9 +112,9 @@ def test_rate_sweep(oracle, kind, case):
         g, w = np.concatenate(got[c]), want[c]
         where = "%s channel %d" % (case.ident, c)
         assert g.shape == w.shape, (where, g.shape, w.shape)
-        if wo == 2:
+        if wo == 2 and thr2 is None:
             assert_bit_exact(g.view(np.complex64).ravel(), w.view(np.complex64).ravel(), where)
-        else:                                               # CF16: the half words
+        else:                                               # CF16: the half words; S32 out: the wire words
             bad = np.nonzero((g != w).any(axis=1))[0]
             assert bad.size == 0, "%s: %d of %d outputs differ, first at %d: got %r want %r" % (where, bad.size, g.shape[0], bad[0], g[bad[0]], w[bad[0]])
     plan.close()

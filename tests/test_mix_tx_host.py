@@ -165,6 +165,39 @@ def test_the_tile_walk_arithmetic_stays_in_32_bits_and_hits_the_table_index():
     assert worst < 2 ** 32 and 65535 * 65535 < 2 ** 32 and 63 * 65535 < 2 ** 32
 
 
+RESIDENT = {4: 2048, 8: 3072}       # workgroups an MI355X holds of interp_mix_pass_kernel's two instances, as tests/test_gpu_mix_tx.py prints them
+# (what, n_groups per channel, n_tiles per channel, (class or num, den), consumed) by the resident figure R: the grids of the
+# tile-walk tests of tests/test_gpu_mix_tx.py -- 2 R + 3 tiles on one channel, groups + 4 tiles on each of three channels (x4: 682
+# groups, no multiple of 8, plainly strided; x8: 1024, XCD-blocked), R + 3 tiles from a placed position
+GPU_GRIDS = [("third tile", lambda R: (R, 2 * R + 3), mixer, 0) for mixer in ((3, 7), (1, 3), (65535, 65536), (65534, 65535))]
+GPU_GRIDS += [("three channels", lambda R: (R // 3, R // 3 + 4), (123, 1000), 0)]
+GPU_GRIDS += [("placed", lambda R: (R, R + 3), ("max", 65535), (1 << 40) + 21), ("placed", lambda R: (R, R + 3), ("one", 7), (1 << 40) + 21),
+              ("placed below 0", lambda R: (R, R + 3), ("one", 65535), 5)]
+
+
+@pytest.mark.parametrize("what,grid,mixer,consumed", GPU_GRIDS, ids=["%s-%s-%s" % (g[0], g[2][0], g[2][1]) for g in GPU_GRIDS])
+@pytest.mark.parametrize("L", [4, 8])
+def test_the_tile_walk_on_the_grids_the_gpu_tests_run(L, what, grid, mixer, consumed):
+    """A second model of what the GPU tests compare with the oracle: tile_walk_model at their own grids, mixers and positions, EVERY
+    index it returns against mix_tx_cases.table_index.  Every wave of the first grid takes a second tile and three a third
+    (stride_step twice); from the placed positions the first tile's phase is (consumed - 32) t reduced in 64 bits, from position 5
+    from below 0."""
+    import rate_cases as rc
+    tile_in = 256 if L == 4 else 128
+    n_groups, n_tiles = grid(RESIDENT[L])
+    num, den = mixer if isinstance(mixer[0], int) else (rc.mixer_num(mixer[0], mixer[1], None, L), mixer[1])
+    assert n_groups < n_tiles and (what != "third tile" or n_tiles > 2 * n_groups)
+    assert what != "three channels" or (n_groups, n_tiles, n_groups % 8) == {4: (682, 686, 2), 8: (1024, 1028, 0)}[L]
+    got, top = tile_walk_model(num, den, L, n_groups, n_tiles, consumed)
+    want = np.stack([table_index(consumed + k * tile_in - 32, tile_in + 32, step(num, den, L), den) for k in range(n_tiles)])
+    assert got.shape == want.shape == (n_tiles, tile_in + 32)
+    bad = np.nonzero(got != want)
+    assert bad[0].size == 0, "x%d %d/%d, %d waves, from %d: tile %d sample %d" % (L, num, den, n_groups, consumed, bad[0][0], bad[1][0] - 32)
+    assert top < 2 ** 32 and 0 <= got.min() and got.max() < den
+    if consumed == 5:
+        assert table_index(5 - 32, 1, step(num, den, L), den)[0] == (-27 * back_step(num, den, L)) % den     # (Python's modulo: the mathematical one)
+
+
 def test_shipped_code_object_of_the_translating_interpolators():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import shipped_isa

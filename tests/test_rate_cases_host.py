@@ -10,8 +10,14 @@ import pytest
 import rate_cases as rc
 from band_cases import AUTO, CX_RATIOS, GENERIC, TILED, Call
 from mix_cases import bound as mix_bound, mix_f64, step
+from mix_tx_cases import back_step, bound as mix_tx_bound, mix_tx_f64
 from rate_cases import KINDS, SWEEP_COUNT, SWEEP_SEED
 from rational_cases import bound as rational_bound, n_out_for, rational_f64
+
+
+# translate_tx: the mixers that must meet the tiled AND the generic kernel -- the smallest step t above 0 on the largest odd and the
+# largest even table, and the largest t of all (s = 1: t = den - 1)
+TX_LIMITS = ("s = den - gcd, den 65535", "s = den - gcd, den 65536", "s = 1, den 65535")
 
 
 def _labels(kind, case):
@@ -33,39 +39,61 @@ def coverage(kind, cases):
         if case.style == "seam":
             c["seam by %s" % case.how] += any(produced[i:i + 3] == ["tiled", "generic", "tiled"] for i in range(len(produced) - 2))
         c["CF16 placed"] += case.fmt == "CF16" and case.place != "start"
+        c["S32 placed"] += case.fmt == "S32" and case.place != "start"
         c["3 ch with a seam"] += case.nchan == 3 and case.style == "seam"
         c["refused in mid-stream on an odd stride"] += any(x == "refused" and form and 0 < i and call.out_stride % 2 == 1 and case.nchan > 1
                                                            for i, (x, call) in enumerate(zip(labels, case.calls)))
         if case.place != "start":
             c["placed"] += 1
             c["place %s" % case.place] += 1
-            if form:
+            if form and KINDS[kind].tx:
+                # no start rule: the tiled kernel takes any position, and must take one of this stream's calls
+                c["placed on a tiled shape, c0 %s" % ("even" if case.c0 % 2 == 0 else "odd")] += 1
+                c["placed on a tiled shape without a tiled call"] += "tiled" not in labels
+            elif form:
                 c["placed, start rule %s" % ("kept" if case.c0 % KINDS[kind].start_multiple == 0 else "broken")] += 1
         for index, log2, i in rc.crossings(case):
             c["%s passes 2^%d" % (index, log2)] += 1
             c["%s passes 2^%d in a %s call" % (index, log2, labels[i])] += 1
-        if kind == "translate":
+        if kind != "rational":
             c["den %d" % case.den] += 1
             for cls in rc.s_classes(case):
                 c[cls] += 1
+                name = cls if cls.startswith("s = den") else "%s, den %d" % (cls, case.den)
+                if KINDS[kind].tx and name in TX_LIMITS:
+                    for label in ("tiled", "generic"):
+                        c["%s, on a %s call" % (name, label)] += label in labels
             c["den below 8 on the tiled kernel"] += case.den < 8 and "tiled" in labels
         else:
             c["pair %d/%d" % (case.up, case.down)] += 1
+        if kind != "translate":
             c["odd taps per phase"] += rc.hist_of(case) % 2 == 1
+        if KINDS[kind].tx and form:
+            c["%dx%d %s" % (case.ntaps, case.up, case.style)] += 1
+            c["%dx%d placed" % (case.ntaps, case.up)] += case.place != "start"
     return c
 
 
 def needed(kind):
     """What must occur in at least one case (for "... calls": in one call)."""
     need = ["tiled calls", "generic calls", "history only calls", "refused calls", "1 ch", "2 ch", "3 ch", "CF16 placed", "3 ch with a seam",
-            "refused in mid-stream on an odd stride", "placed, start rule kept", "placed, start rule broken"]
-    need += sorted(set(KINDS[kind].formats)) + ["seam by %s" % how for how in rc.SEAMS] + ["place %s" % p for p in rc.PLACES[kind]]
+            "refused in mid-stream on an odd stride"]
+    need += sorted(set(KINDS[kind].formats)) + ["seam by %s" % how for how in rc.SEAMS[kind]] + ["place %s" % p for p in rc.PLACES[kind]]
     need += ["%s passes 2^%s" % tuple(p.split()) for p in rc.PLACES[kind] if p != "far"]
-    if kind == "translate":
+    if KINDS[kind].tx:
+        need += ["S32 placed", "placed on a tiled shape, c0 even", "placed on a tiled shape, c0 odd"]
+        need += ["%s passes 2^%s in a tiled call" % tuple(p.split()) for p in rc.PLACES[kind] if p != "far"]
+        need += ["%dx%d %s" % (s[0], s[1], what) for s in KINDS[kind].tiled_shapes for what in ("clean", "seam", "placed")]
+        need += ["%s, on a %s call" % (cls, label) for cls in TX_LIMITS for label in ("tiled", "generic")]
+    else:
+        need += ["placed, start rule kept", "placed, start rule broken"]
+    if kind != "rational":
         need += ["den %d" % d for d in rc.DENS]
         need += ["s = den - gcd, den 65535", "s = den - gcd, den 65536", "s = 1", "s = 0", "negative num", "num above den", "den below 8 on the tiled kernel"]
     else:
-        need += ["pair %d/%d" % p for p in rc.RATIONAL_PAIRS] + ["odd taps per phase"]
+        need += ["pair %d/%d" % p for p in rc.RATIONAL_PAIRS]
+    if kind != "translate":
+        need += ["odd taps per phase"]
     return need
 
 
@@ -81,8 +109,16 @@ def test_the_sweep_covers_what_it_is_for(kind):
     # band_cases' deck
     assert c["CF32"] == 22 and c["placed"] == 12 and sum(rc.has_form(kind, x) for x in cases) == 11, c
     assert sum(x.style == "seam" for x in cases) == 4 and sum(x.style == "clean" for x in cases) == 7, c
-    assert c["placed, start rule kept"] == 2 and c["placed, start rule broken"] == 2, c
-    # at most a quarter of all calls compute nothing
+    if KINDS[kind].tx:
+        assert c["placed on a tiled shape, c0 even"] == 2 and c["placed on a tiled shape, c0 odd"] == 2, c
+        assert c["placed on a tiled shape without a tiled call"] == 0, c
+        # no call with inputs is "history only": every input makes L outputs
+        assert all(call.n == 0 for x in cases for call, label in zip(x.calls, _labels(kind, x)) if label == "history only")
+        for x in cases:
+            assert 0 <= step(x.num, x.den, x.up) < x.den <= 65536 and x.ntaps % x.up == 0 and x.down == 1, x.ident
+    else:
+        assert c["placed, start rule kept"] == 2 and c["placed, start rule broken"] == 2, c
+    # at most a quarter of all calls compute nothing (refused calls and calls that complete no output -- translate_tx: n = 0 -- together)
     assert 4 * (c["refused calls"] + c["history only calls"]) <= c["calls"], c
     if kind == "translate":
         # the mixer at its limits: num 65535 at /4 on den 65536 has s = 65532, as the tiled kernel's comments count on
@@ -96,20 +132,26 @@ def test_the_sweep_covers_what_it_is_for(kind):
 def test_every_draw_is_a_call_the_entry_point_accepts(kind):
     """The argument checks of sxfir_create_translating / sxfir_create_rational and of sxfir_decimate / sxfir_resample (check_buffers),
     restated: legal shapes and formats, a stream of six tiles at the most, strides that hold the block, a position that
-    sxfir_set_position takes and whose product with `up` stays below 2^62, a lead that sxfir_set_history takes."""
+    sxfir_set_position takes and whose product with `up` stays below 2^62, a lead that sxfir_set_history takes.
+    sxfir_create_translating_interpolator: ntaps % ratio == 0, den in 1 .. 65536, and (c0 + 6 tile) L < 2^62 for the output count."""
     K = KINDS[kind]
     for case in rc.cases(kind, SWEEP_SEED, SWEEP_COUNT):
         assert case.fmt in K.formats and case.nchan in (1, 2, 3) and 1 <= len(case.calls) <= 6, case.ident
         if kind == "translate":
             assert case.up == 1 and case.down in CX_RATIOS and 4 <= case.ntaps <= 300 and 1 <= case.den <= 65536, case.ident
             assert -2 ** 31 <= case.num < 2 ** 31, case.ident
+        elif kind == "translate_tx":
+            assert case.down == 1 and case.up in CX_RATIOS and case.ntaps % case.up == 0 and 1 <= case.ntaps // case.up, case.ident
+            assert (case.ntaps <= 300 or (case.ntaps, case.up, case.down) in K.tiled_shapes) and 1 <= case.den <= 65536, case.ident
+            assert -2 ** 31 <= case.num < 2 ** 31, case.ident
+            assert tuple(rc.contract(kind, case)) == ((2, 1) if (case.ntaps // case.up) % 2 == 0 else (1, 1)), case.ident
         else:
             assert case.fmt != "S32" and (case.num, case.den) == (0, 0), case.ident
             assert 2 <= case.up <= 4096 and 2 <= case.down <= 4096 and math.gcd(case.up, case.down) == 1, case.ident
             assert case.ntaps % case.up == 0 and 1 <= case.ntaps // case.up <= 40, case.ident
             assert ((case.up, case.down) in rc.RATIONAL_PAIRS), case.ident
-        assert 0 < sum(call.n for call in case.calls) <= 6 * K.tile, case.ident
-        assert 0 <= case.c0 and (case.c0 + 6 * K.tile) * case.up < 2 ** 62, case.ident
+        assert 0 < sum(call.n for call in case.calls) <= 6 * rc.tile_of(kind, case), case.ident
+        assert 0 <= case.c0 and (case.c0 + 6 * rc.tile_of(kind, case)) * case.up < 2 ** 62, case.ident
         assert (case.c0 == 0) == (case.place == "start"), case.ident
         lead = rc.lead_of(case)
         assert (lead == 0 and case.c0 == 0) or (rc.hist_len(case) <= lead <= case.c0 and (case.c0 - lead) % case.down == 0), case.ident
@@ -126,7 +168,7 @@ def test_the_predictor_on_hand_made_calls():
     """The headers' rules on calls written out by hand: every reason to leave the tiled kernel, both start rules, from the stream's
     start and from a placed position."""
     def case(kind, calls, fmt="CF32", nchan=2, c0=0, shape=None):
-        ntaps, up, down = shape or KINDS[kind].tiled_shape
+        ntaps, up, down = shape or KINDS[kind].tiled_shapes[0]
         return rc.Case("hand", ntaps, up, down, 3, 7, 0, nchan, fmt, 0, "hand", None, "start" if c0 == 0 else "far", c0, tuple(calls))
 
     def call(n, request=AUTO, out_off=0, out_stride=4096):
@@ -145,6 +187,11 @@ def test_the_predictor_on_hand_made_calls():
         assert rc.expected_kernel(kind, case(kind, [call(640)], fmt="CF16"), 0) == "generic"                        # 9
         assert rc.expected_kernel(kind, case(kind, [call(640, TILED)], fmt="CF16"), 0) == "refused"                 # 10
         assert one(0, TILED) == "history only"                                                                      # 11
+        if KINDS[kind].tx:
+            # no position rule: "at any stream position" (sxfir_translate_tx.h), even, odd, beyond 2^32
+            for c0 in (2 ** 40 + 3, 2 ** 40 + 20, 2 ** 31 - 1, 5):
+                assert rc.expected_kernel(kind, case(kind, [call(640, TILED)], c0=c0), 0) == "tiled", (kind, c0)
+            continue
         # a placed stream: the rule is about the ABSOLUTE position
         for c0, want in ((q * (2 ** 40 + 3), "tiled"), (q * 2 ** 40 + 1, "generic"), (2 ** 31, "tiled" if 2 ** 31 % q == 0 else "generic")):
             assert rc.expected_kernel(kind, case(kind, [call(640)], c0=c0), 0) == want, (kind, c0)                   # 12, 13, 14
@@ -161,6 +208,18 @@ def test_the_predictor_on_hand_made_calls():
     assert rc.expected_kernel("translate", case("translate", [call(640, TILED)], shape=(64, 1, 4)), 0) == "refused"
     assert rc.expected_kernel("rational", case("rational", [call(640)], shape=(64, 4, 5)), 0) == "generic"
     assert rc.expected_kernel("rational", case("rational", [call(1)], shape=(24, 3, 8), c0=1), 0) == "history only"
+    # translate_tx: every input makes L outputs, so a call of ANY size above 0 computes, at any position; n = 0 does nothing, whatever
+    # was asked for; the only refusals in mid-stream are the output's alignment and an odd out_stride with nchan > 1; both shapes
+    tx = "translate_tx"
+    c = case(tx, [call(1), call(2, TILED), call(0, TILED, out_off=1), call(31, GENERIC), call(3, TILED, out_off=1), call(3, TILED, out_stride=4097),
+                  call(300, TILED)], c0=2 ** 40 + 21)
+    assert [rc.outputs_for(c, rc.position_before(c, i), x.n) for i, x in enumerate(c.calls)] == [4, 8, 0, 124, 12, 12, 1200]
+    assert [rc.expected_kernel(tx, c, i) for i in range(7)] == ["tiled", "tiled", "history only", "generic", "refused", "refused", "tiled"]
+    assert rc.expected_kernel(tx, c._replace(nchan=1), 5) == "tiled"                        # (one channel: the stride is not used)
+    assert rc.expected_kernel(tx, case(tx, [call(640, TILED)], shape=(256, 8, 1)), 0) == "tiled"
+    assert rc.expected_kernel(tx, case(tx, [call(640, TILED)], shape=(128, 8, 1)), 0) == "refused"
+    assert rc.expected_kernel(tx, case(tx, [call(640)], shape=(35, 5, 1), c0=7), 0) == "generic"
+    assert rc.expected_kernel(tx, case(tx, [call(0, TILED)], shape=(35, 5, 1)), 0) == "refused"      # (sxfir_set_kernel's refusal comes first)
 
 
 def test_crossings_on_hand_made_streams():
@@ -176,6 +235,15 @@ def test_crossings_on_hand_made_streams():
     # 4/5: output m belongs to input floor(5 m / 4); m = ceil(2^31 / 5) = 429496730 is the first with 5 m >= 2^31, its input 536870912
     assert rc.crossings(case(4, 5, 536870911, [2])) == {("raster", 31, 0)}
     assert rc.crossings(case(4, 5, 536870912, [2])) == set()
+    # x4 and x8 (down = 1): a call of inputs [a, b) makes the outputs [L a, L b) -- ma = a up / down holds without a remainder --, so
+    # output 2^32 belongs to input 2^30 at x4 and output 2^31 to input 2^28 at x8; no "raster" of its own
+    assert rc.crossings(case(4, 1, 2 ** 30 - 2, [2, 2])) == set()                          # outputs .. 2^32 - 1, then 2^32 ..: between two calls
+    assert rc.crossings(case(4, 1, 2 ** 30 - 1, [2])) == {("output", 32, 0)}
+    assert rc.crossings(case(4, 1, 2 ** 30, [2])) == set()
+    assert rc.crossings(case(8, 1, 2 ** 28 - 3, [2, 2, 2])) == {("output", 31, 1)}
+    assert rc.crossings(case(8, 1, 2 ** 31 - 10, [5, 10])) == {("input", 31, 1)}
+    assert rc.crossings(case(4, 1, 2 ** 32 - 1, [1, 1])) == set() and rc.crossings(case(4, 1, 2 ** 32 - 1, [2])) == {("input", 32, 0)}
+    assert rc.crossings(case(2, 1, 2 ** 31 - 1, [2])) == {("input", 31, 0), ("output", 32, 0)}     # (x2: both marks in one call)
 
 
 @pytest.mark.parametrize("kind", list(KINDS))
@@ -194,13 +262,26 @@ def test_the_placed_reference_is_the_plain_one_at_the_lead(oracle, kind):
         if kind == "translate" and (case.c0 - lead) // case.down * step(case.num, case.den, case.down) % case.den:
             far = rc.reference(kind, oracle, case, h, xs[0])
             assert far.shape == got.shape and not np.array_equal(far.view(np.uint32), got.view(np.uint32)), "the far phase is not the near one"
+        if kind == "translate_tx" and back_step(case.num, case.den, case.up):
+            far = rc.reference(kind, oracle, case, h, xs[0])
+            assert far.shape == got.shape and np.count_nonzero(far.view(np.uint32) != got.view(np.uint32)) > got.size // 2, "the far phase is not the near one"
+    if kind == "translate_tx":
+        # the generator's promise for EVERY placed case: wherever the kernels step at all (t != 0), the lead's first sample has another
+        # table entry than at c0 = lead, so a plan that lost its 64-bit position cannot pass
+        placed = [c for c in rc.cases(kind, SWEEP_SEED, SWEEP_COUNT) if c.place != "start"]
+        assert len(placed) == 12 and {rc.has_form(kind, c) for c in placed if back_step(c.num, c.den, c.up)} == {True, False}
+        for case in placed:
+            t = back_step(case.num, case.den, case.up)
+            assert rc.lead_of(case) == rc.hist_len(case), case.ident                        # the fewest samples that fill the history
+            assert t == 0 or (case.c0 - rc.lead_of(case)) * t % case.den != 0, case.ident
 
 
 @pytest.mark.parametrize("kind", list(KINDS))
 def test_the_placed_reference_is_the_fp64_definition(oracle, kind):
     """Three placed cases per kind, channel 0: the float32 reference the GPU is compared with bit for bit against the header's formula
-    in fp64 with the TRUE absolute index of the first output -- mix_cases.mix_f64 / rational_cases.rational_f64 over the lead and the
-    stream, the lead's outputs dropped -- within the project's bounds (mix_cases.bound, rational_cases.bound)."""
+    in fp64 with the TRUE absolute index of the first output (translate_tx: of the first input) -- mix_cases.mix_f64 /
+    rational_cases.rational_f64 / mix_tx_cases.mix_tx_f64 over the lead and the stream, the lead's outputs dropped -- within the
+    project's bounds (mix_cases.bound, rational_cases.bound, mix_tx_cases.bound)."""
     placed = [c for c in rc.cases(kind, SWEEP_SEED, SWEEP_COUNT) if c.place != "start"]
     assert len(placed) >= 3
     for case in placed[:3]:
@@ -214,10 +295,36 @@ def test_the_placed_reference_is_the_fp64_definition(oracle, kind):
             m_true = -(-case.c0 // case.down)                                   # ceil(c0 / ratio): sxfir_set_position's `produced`
             want = mix_f64(h, case.down, case.num, case.den, x, m_true - skip)[skip:]
             b = mix_bound(h, x, want)
+        elif kind == "translate_tx":
+            # the first sample of x is input c0 - lead of the stream: the true index, a Python int of 41 bits in the "far" cases
+            want = mix_tx_f64(h, case.up, case.num, case.den, x, case.c0 - lead)[skip:]
+            b = np.full(want.shape, mix_tx_bound(h, x))
         else:
             want = rational_f64(h, case.up, case.down, x)[skip:]
             b = np.full(want.shape, rational_bound(h, x))
         assert got.shape == want.shape and got.size > 0, case.ident
-        err = np.maximum(np.abs(got.real - want.real), np.abs(got.imag - want.imag)) if kind == "translate" else np.abs(got - want)
+        err = np.maximum(np.abs(got.real - want.real), np.abs(got.imag - want.imag)) if kind != "rational" else np.abs(got - want)
         print("%s %s from %d: worst error %.3g, bound there %.3g" % (kind, case.ident, case.c0, err.max(), b[err.argmax()]))
         assert np.all(err <= b), case.ident
+
+
+def test_the_tx_wire_words_stay_in_range_and_hold_both_keying_states(oracle):
+    """translate_tx on S32: CF32 in, convert_tx words out.  The input's scale (rate_cases.tx_scale, an exact power of two) keeps
+    every component of the reference below 1.0, and the threshold -- the median |y|^2 of channel 0's reference -- leaves words of
+    both keying states in EVERY channel's reference: a plan that lost its threshold, or keyed on the raw input, cannot pass."""
+    kind = "translate_tx"
+    s32 = [c for c in rc.cases(kind, SWEEP_SEED, SWEEP_COUNT) if c.fmt == "S32"]
+    assert s32
+    for case in s32:
+        h = rc.taps_of(kind, case)
+        raw, xs = rc.stream_input(kind, case, oracle)
+        scale = rc.tx_scale(h)
+        assert float(np.log2(scale)) == int(np.log2(scale)) and float(np.abs(h.astype(np.complex128)).sum()) * float(np.abs(xs).max()) < 1.0, case.ident
+        refs = [rc.reference(kind, oracle, case, h, xs[c]) for c in range(case.nchan)]
+        thr2 = rc.keying_threshold(refs[0])
+        for ref in refs:
+            assert max(np.abs(ref.real).max(), np.abs(ref.imag).max()) < 1.0, case.ident
+            words = rc.stored_words(oracle, case.fmt, ref, thr2)
+            keyed = (words.view(np.int32)[:, 0] & 3) == 3
+            assert 0 < keyed.sum() < keyed.size, (case.ident, int(keyed.sum()), keyed.size)
+        assert not np.array_equal(rc.stored_words(oracle, case.fmt, refs[0], thr2), rc.stored_words(oracle, case.fmt, refs[0], np.float32(0.0)))
