@@ -160,6 +160,16 @@ def load_sxfir(profiling=False):
         "sxfir_translate_tx_abi_version": (ci, []),
         "sxfir_create_translating_interpolator": (ci, [P(vp), vp, ci, ci, ci, ci, ci, ci, ci]),
         "sxfir_plan_translation_tx": (ci, [vp, P(ci), P(ci)]),
+        # include/sxfir_arbitrary.h: arbitrary-rate resamplers
+        "sxfir_arbitrary_abi_version": (ci, []),
+        "sxfir_create_arbitrary": (ci, [P(vp), vp, ci, ci, u64, ci, ci, ci]),
+        "sxfir_set_rate": (ci, [vp, u64]),
+        "sxfir_set_time": (ci, [vp, i64, i64, C.c_uint32]),
+        "sxfir_plan_arbitrary": (ci, [vp, P(ci), P(u64), P(i64), P(C.c_uint32)]),
+        "sxfir_resample_arbitrary": (ci, [vp, vp, sz, sz, vp, sz, P(sz), vp]),
+        "sxfir_time_resample_arbitrary": (ci, [vp, vp, sz, sz, vp, sz, ci, vp, P(C.c_float)]),
+        "sxfir_arbitrary_outputs": (ci, [i64, C.c_uint32, u64, i64, u64, P(u64), P(i64), P(C.c_uint32)]),
+        "sxfir_arbitrary_locate": (ci, [u64, u64, u64, ci, P(i64), P(ci), P(C.c_float)]),
     }
     if profiling:
         sig["sxfir_debug_clock"] = (ci, [vp, P(dbl)])

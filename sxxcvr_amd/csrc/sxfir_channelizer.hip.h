@@ -28,6 +28,7 @@ int sxfir_channelize(sxfir_plan *p, const void *in_dev, size_t n_in, size_t in_s
     if (!p) return fail(SXFIR_EINVAL, "plan is NULL");
     if (p->kind == KIND_SYNTHESIZER) return fail(SXFIR_EINVAL, "a synthesizer plan takes sxfir_synthesize (include/sxfir_synthesizer.h)");
     if (p->kind == KIND_RATIONAL) return fail(SXFIR_EINVAL, "%s", RATIONAL_TAKES);
+    if (p->kind == KIND_ARBITRARY) return fail(SXFIR_EINVAL, "%s", ARBITRARY_TAKES);
     if (p->kind != KIND_CHANNELIZER) return fail(SXFIR_EINVAL, "not a channelizer plan");
     const long long n_out = outputs_for(p, (long long)n_in);
     if ((n_in && !in_dev) || (n_out > 0 && !out_dev)) return fail(SXFIR_EINVAL, "NULL device buffer");

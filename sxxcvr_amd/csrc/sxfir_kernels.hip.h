@@ -104,6 +104,8 @@ struct GenericArgs {
                             // butterflies' operands), an oversampled synthesizer's per-band input, a rational plan's output
     long long consumed;     // rational plans: absolute index of the call's first input
     int down;               // rational plans: `down` of up / down (up is `ratio`)
+    unsigned long long arb_rel, arb_step;   // arbitrary-rate plans (sxfir_arb.hip.h): the call's first output's time less
+                                            // (consumed - 1) * 2^32, and the step, both Q32.32
 };
 
 // The translating plans' generic kernels (sxfir_mixer.hip.h): GenericArgs keeps its size.  m_first: a translating decimator's

@@ -219,12 +219,39 @@ static LaunchGeom rational_geom(const sxfir_plan *p, long long n_in, long long n
     return g;
 }
 
+// Arbitrary-rate plans: one thread per output of the generic kernel; the form's tiles (256 OUTPUTS, one wave each, four waves per
+// workgroup) for a call that wants it, is aligned and whose step lies in the range the tile's image is sized for.  Any start: the
+// position is computed, not assumed.
+static LaunchGeom arb_geom(const sxfir_plan *p, long long n_out, bool aligned)
+{
+    LaunchGeom g = generic_geom(p, n_out, 1);
+    const PlanForm *f = p->form;
+    const bool in_range = p->arb_step >= sxfir::ArbTile::STEP_MIN && p->arb_step <= sxfir::ArbTile::STEP_MAX;
+    if (!(f && p->kernel != SXFIR_KERNEL_GENERIC && aligned && in_range)) return g;
+    set_tiles(g, p, n_out, p->tile);
+    g.tile_samples = p->tile;                           // (outputs: the input span of a tile depends on the step)
+    // a workgroup's four waves take a tile each and pay for the tap table once: the generations rule counts workgroup-sized units
+    const long long units = (g.n_tiles + sxfir::ArbTile::WAVES - 1) / sxfir::ArbTile::WAVES;
+    g.groups = clamp_groups(g.resident * generations(p, units, g.resident) / p->nchan, units);
+    return g;
+}
+
 // The geometry of a call of n_in samples (per band for a synthesizer), whatever the plan's kind
 static LaunchGeom call_geom(const sxfir_plan *p, long long n_in, bool aligned, bool keyed)
 {
+    if (p->kind == KIND_ARBITRARY) return arb_geom(p, outputs_for(p, n_in), aligned);
     if (p->kind == KIND_RATIONAL) return rational_geom(p, n_in, outputs_for(p, n_in), aligned);
     if (p->mode == SXFIR_DECIMATE) return decim_geom(p, outputs_for(p, n_in), first_offset(p), aligned);
     return interp_geom(p, n_in, aligned, keyed);
+}
+
+// An arbitrary-rate plan's time relative to the call, Q32.32: t - (consumed - 1) * 2^32 >= 0 (the absolute 64.32 time stays on the
+// host).  A call that yields an output has t below (consumed + n_in - 1) * 2^32, so the difference fits 64 bits for every call of
+// fewer than 2^31 inputs -- the bound both entry points set in front of either kernel (check_arbitrary_io); a plan placed further
+// ahead yields no output and launches nothing.
+static unsigned long long arb_rel(const sxfir_plan *p)
+{
+    return ((unsigned long long)(p->arb_t_index - (p->consumed - 1)) << 32) | p->arb_t_frac;
 }
 
 // ---- one builder per argument struct (value-initialised: what a kernel does not read is zero)
@@ -260,6 +287,31 @@ static sxfir::GenericArgs generic_args(const sxfir_plan *p, const CallIO &c, lon
         a.hist_len = p->hist_len / p->bands;        // a band's history; hist_stride stays the channel's
     }
     if (p->kind == KIND_RATIONAL) a.m_first = p->produced;
+    if (p->kind == KIND_ARBITRARY) {
+        a.arb_rel = arb_rel(p);
+        a.arb_step = p->arb_step;
+    }
+    return a;
+}
+
+// arbitrary-rate plans: the tiled kernel's argument struct of sxfir_arb.hip.h
+static sxfir::ArbTileArgs arb_tile_args(const sxfir_plan *p, const CallIO &c, const LaunchGeom &geom)
+{
+    sxfir::ArbTileArgs a{};
+    a.in = c.in;
+    a.hist = p->hist_dev;
+    a.out = c.out;
+    a.table = p->taps_scaled_dev;                   // the extended phase-major table
+    a.n_in = (long long)c.n_in;
+    a.n_out = c.n_out;
+    a.in_stride = (long long)c.in_stride;
+    a.out_stride = (long long)c.out_stride;
+    a.hist_stride = p->hist_len;
+    a.rel = arb_rel(p);
+    a.step = p->arb_step;
+    a.hist_len = p->hist_len;
+    a.n_tiles = (int)geom.n_tiles;
+    a.n_groups = (int)geom.groups;
     return a;
 }
 
@@ -500,6 +552,9 @@ static int launch_interp_tiled(sxfir_plan *p, const CallIO &c, const LaunchGeom 
 static int refuse_tiled(const sxfir_plan *p)
 {
     if (p->kind == KIND_SYNTHESIZER) return fail(SXFIR_EUNSUPPORTED, "tiled synthesizer needs a 16-byte aligned output and an even output stride");
+    if (p->kind == KIND_ARBITRARY)
+        return fail(SXFIR_EUNSUPPORTED, "tiled arbitrary-rate resampler needs a 16-byte aligned output, an even output stride and a step in "
+                                        "[2^31, 2^33] (step %llu)", (unsigned long long)p->arb_step);
     if (p->kind == KIND_RATIONAL)
         return fail(SXFIR_EUNSUPPORTED, "tiled resampler needs a 16-byte aligned output, an even output stride and a call that starts at a "
                                         "stream position that is a multiple of %d", p->form ? p->form->start_multiple : 1);
@@ -556,6 +611,11 @@ static int launch_call(sxfir_plan *p, const CallIO &c, bool *history_done, const
     // last tile's wave carries the history over)
     case GEOM_RAT45: return launch(p->k.rat45, grid, threads, c.st, decim_tile_args(p, c, geom));
     case GEOM_MIX: return launch(p->k.mix, grid, threads, c.st, mix_tile_args(p, c, geom));
+    // resample_arb_kernel leaves the history to the generic path's pass (history_kernel)
+    case GEOM_ARB:
+        *history_done = false;
+        if (int rc = need_tap_table(p, TAPS_ARB, p->form->tiled)) return rc;
+        return launch(p->k.arb, grid, threads, c.st, arb_tile_args(p, c, geom));
     case GEOM_IPASS:
     case GEOM_ITILE:
     case GEOM_ICX:
@@ -584,6 +644,13 @@ static int stream_call(sxfir_plan *p, const CallIO &c, size_t *n_out_p, const Ke
     if (key_pending)
         if (int rc = launch_keyed_count(p, c.in, key, c.st)) return rc;
     std::swap(p->hist_dev, p->hist_alt);
+    if (p->kind == KIND_ARBITRARY) {                // the time after the call's outputs, by the rule that counted them
+        int64_t ti;
+        uint32_t tf;
+        (void)arb_count(p, (long long)c.n_in, &ti, &tf);
+        p->arb_t_index = ti;
+        p->arb_t_frac = tf;
+    }
     p->consumed += (long long)c.n_in;
     p->produced += c.n_out;
     if (n_out_p) *n_out_p = (size_t)c.n_out;
@@ -613,11 +680,13 @@ static int check_buffers(const sxfir_plan *p, const CallIO &c)
 }
 
 static const char *const RATIONAL_TAKES = "a rational plan takes sxfir_resample (include/sxfir_rational.h)";
+static const char *const ARBITRARY_TAKES = "an arbitrary-rate plan takes sxfir_resample_arbitrary (include/sxfir_arbitrary.h)";
 
 // sxfir_decimate, sxfir_interpolate and sxfir_time_*: real and complex taps
 static int check_io(const sxfir_plan *p, int mode, const CallIO &c)
 {
     if (p->kind == KIND_RATIONAL) return fail(SXFIR_EINVAL, "%s", RATIONAL_TAKES);
+    if (p->kind == KIND_ARBITRARY) return fail(SXFIR_EINVAL, "%s", ARBITRARY_TAKES);
     if (p->kind == KIND_SYNTHESIZER) return fail(SXFIR_EINVAL, "a synthesizer plan takes sxfir_synthesize (include/sxfir_synthesizer.h)");
     if (p->mode != mode) return fail(SXFIR_EINVAL, "plan was created for the other direction");
     if (p->kind == KIND_CHANNELIZER) return fail(SXFIR_EINVAL, "a channelizer plan takes sxfir_channelize (include/sxfir_channelizer.h)");
@@ -653,6 +722,7 @@ int sxfir_interpolate_keyed(sxfir_plan *p, const void *in_dev, size_t n_in, size
     if (n_out_p) *n_out_p = 0;
     if (!p) return fail(SXFIR_EINVAL, "plan is NULL");
     if (p->kind == KIND_RATIONAL) return fail(SXFIR_EINVAL, "%s", RATIONAL_TAKES);
+    if (p->kind == KIND_ARBITRARY) return fail(SXFIR_EINVAL, "%s", ARBITRARY_TAKES);
     if (p->kind == KIND_SYNTHESIZER) return fail(SXFIR_EINVAL, "a synthesizer plan takes sxfir_synthesize (include/sxfir_synthesizer.h): no keying count in its version 1");
     if (p->mode != SXFIR_INTERPOLATE) return fail(SXFIR_EINVAL, "not an interpolator plan");
     if (p->fmt == SXFIR_CF16) return fail(SXFIR_EUNSUPPORTED, "the keying count is defined on CF32 input");

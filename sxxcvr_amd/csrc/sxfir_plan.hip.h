@@ -18,7 +18,10 @@
 // their own); the band kinds are a /ratio decimator and a x ratio interpolator in everything about the stream.
 // sxfir_create_rational (sxfir_rational.hip.h): KIND_RATIONAL, a x ratio interpolator (ratio = up) of which every down-th output is
 // computed -- an interpolator's history and contract, positions and output counts of its own (rational_produced).
-enum PlanKind { KIND_REAL = 0, KIND_COMPLEX = 1, KIND_CHANNELIZER = 2, KIND_SYNTHESIZER = 3, KIND_RATIONAL = 4 };
+// sxfir_create_arbitrary (sxfir_arbitrary.hip.h): KIND_ARBITRARY, a x ratio interpolator (ratio = nphases) between whose outputs the
+// plan's own are blended, at a fixed-point time that advances by arb_step per output -- an interpolator's history and contract, a
+// time and output counts of its own (arb_outputs, sxfir_arb_index.h).
+enum PlanKind { KIND_REAL = 0, KIND_COMPLEX = 1, KIND_CHANNELIZER = 2, KIND_SYNTHESIZER = 3, KIND_RATIONAL = 4, KIND_ARBITRARY = 5 };
 
 // The layout of a plan's second tap table (taps_scaled_dev); one function per layout below (second_tap_table).
 // TAPS_SCALED: taps * 2^-31 (exact) in tap order, for the /4 scalar-tap kernels on S32 wire words;
@@ -27,12 +30,13 @@ enum PlanKind { KIND_REAL = 0, KIND_COMPLEX = 1, KIND_CHANNELIZER = 2, KIND_SYNT
 // TAPS_BLOCKS16: the block-major table of decim_blocks_kernel, of the ROTATED taps (times 2^-31 for S32 plans);
 // TAPS_PHASED: the phase-major table of synthesis4_kernel and synthesis4x2_kernel (h[ratio j + r] at (ntaps / ratio) r + j: four
 // phases, or the two output parities of the oversampled plan); TAPS_NONE: the plan's kernels read taps_dev alone;
-// TAPS_PASS8_CX: interp_cx_pass_kernel's, 2 x ntaps floats -- the TAPS_PASS8 table of a, then that of b.
+// TAPS_PASS8_CX: interp_cx_pass_kernel's, 2 x ntaps floats -- the TAPS_PASS8 table of a, then that of b;
+// TAPS_ARB: resample_arb_kernel's, (P + 1) rows of T + 4 floats -- row p holds h[(T - 1 - i) P + p] at i (j descending), row P repeats row 0.
 // Every launch that hands taps_scaled_dev to a kernel checks the plan's layout first (need_tap_table).
-enum TapTable { TAPS_SCALED = 0, TAPS_SUBSET8 = 1, TAPS_PASS8 = 2, TAPS_BLOCKS16 = 3, TAPS_PHASED = 4, TAPS_NONE = 5, TAPS_PASS8_CX = 6 };
+enum TapTable { TAPS_SCALED = 0, TAPS_SUBSET8 = 1, TAPS_PASS8 = 2, TAPS_BLOCKS16 = 3, TAPS_PHASED = 4, TAPS_NONE = 5, TAPS_PASS8_CX = 6, TAPS_ARB = 7 };
 
 // Which kernel family a call launches (LaunchGeom::kind, sxfir_launch.hip.h)
-enum { GEOM_GENERIC = 0, GEOM_MULTI = 1, GEOM_WIDE = 2, GEOM_TILE = 3, GEOM_IPASS = 4, GEOM_ITILE = 5, GEOM_CX = 6, GEOM_CHAN4 = 7, GEOM_SYN4 = 8, GEOM_CHAN4X2 = 9, GEOM_SYN4X2 = 10, GEOM_ICX = 11, GEOM_RAT45 = 12, GEOM_MIX = 13, GEOM_IMIX = 14 };
+enum { GEOM_GENERIC = 0, GEOM_MULTI = 1, GEOM_WIDE = 2, GEOM_TILE = 3, GEOM_IPASS = 4, GEOM_ITILE = 5, GEOM_CX = 6, GEOM_CHAN4 = 7, GEOM_SYN4 = 8, GEOM_CHAN4X2 = 9, GEOM_SYN4X2 = 10, GEOM_ICX = 11, GEOM_RAT45 = 12, GEOM_MIX = 13, GEOM_IMIX = 14, GEOM_ARB = 15 };
 
 // One typed kernel pointer per launch-argument family, and a plan's kernels: resolved once by the plan's creator
 // (resolve_kernels below), read by the occupancy query there and by the launches (sxfir_launch.hip.h).
@@ -47,6 +51,7 @@ typedef void (*SynOsTileFn)(sxfir::SynOsTileArgs);
 typedef void (*MixGenericFn)(sxfir::MixGenericArgs);
 typedef void (*MixTileFn)(sxfir::MixTileArgs);
 typedef void (*InterpMixTileFn)(sxfir::InterpMixTileArgs);
+typedef void (*ArbTileFn)(sxfir::ArbTileArgs);
 struct KernelTable {
     const char *generic_name;    // the plan's generic kernel, as sxfir_launch_geometry reports it, and the instance: every plan of every
     GenericFn generic;           // kind has exactly one (generic_kernel below), the kernel of every call its form does not take
@@ -64,6 +69,7 @@ struct KernelTable {
                                  // decim_cx_generic_kernel<.., MixGenericArgs> or interp_mix_generic_kernel
     MixTileFn mix;               // translating decimators: decim4_cx_kernel<MixTileArgs> (/4 x 128 complex taps, CF32)
     InterpMixTileFn imix;        // translating interpolators: interp_cx_pass_kernel<.., InterpMixTileArgs> (x4 x 128, x8 x 256 complex taps, CF32)
+    ArbTileFn arb;               // arbitrary-rate plans (include/sxfir_arbitrary.h): resample_arb_kernel (128 phases x 32 taps, CF32)
 };
 
 // What the geometry and launch code needs to know of a tiled kernel family (FORM_* below).  A plan has at most one, settled at
@@ -89,6 +95,9 @@ struct sxfir_plan {
     int kind;              // PlanKind
     int mode, ntaps, ratio, nchan, fmt, device;
     int down;              // rational plans: `down` of up / down (up is `ratio`); else 0
+    uint64_t arb_step;     // arbitrary-rate plans (nphases is `ratio`): input samples per output, Q32.32; else 0
+    long long arb_t_index; // ... the time of the next output: whole input samples
+    uint32_t arb_t_frac;   // ... and its fraction, Q0.32
     int bands;             // the band kinds: 4 (= ratio, but for the oversampled plans); else 0.  A synthesizer's hist_dev holds
                            // bands x hist_len / bands samples per channel, band k's at k * hist_len / bands
     int oversample;        // channelizer plans: bands / ratio -- 1 critically sampled (sxfir_create_channelizer), 2 each band at fs/2
@@ -157,6 +166,8 @@ static GenericKernel generic_kernel(int kind, int oversample, int mode, int fmt)
         SXFIR_GENERIC(synthesis_generic_kernel, CF32, S32);
     case KIND_RATIONAL:
         return GenericKernel{"resample_generic_kernel", fmt == SXFIR_CF16 ? (GenericFn)resample_generic_kernel<CF16, CF16> : (GenericFn)resample_generic_kernel<CF32, CF32>};
+    case KIND_ARBITRARY:
+        return GenericKernel{"resample_arb_generic_kernel", fmt == SXFIR_CF16 ? (GenericFn)resample_arb_generic_kernel<CF16> : (GenericFn)resample_arb_generic_kernel<CF32>};
     case KIND_COMPLEX:
         if (rx) SXFIR_GENERIC(decim_cx_generic_kernel, S32, CF32);
         SXFIR_GENERIC(interp_cx_generic_kernel, CF32, S32);
@@ -337,6 +348,12 @@ static const PlanForm FORM_IMIX = {"interp_mix_pass_kernel", GEOM_IMIX, TILE_IPA
 // small call spreads over the chip; generations and occupancy: tools/ratbench.py, profiles/rational.txt
 static const PlanForm FORM_RAT45 = {"resample45_kernel", GEOM_RAT45, sxfir::Resample45::TILE_IN, 64, 5, 2, false, 16, 8, TAPS_NONE};
 
+// resample_arb_kernel: arbitrary-rate plans, 128 phases x 32 taps on CF32, tiles of 256 OUTPUTS, one wave per tile, four waves (one
+// workgroup) around one tap table in LDS; any start.  Which calls it takes: arb_geom (sxfir_launch.hip.h).  Its prologue is heavy (18 KiB
+// of taps into LDS per workgroup), so a small call keeps four workgroup-sized units per workgroup.  Four generations were not swept
+// against other figures; occupancy 4 is what 36 KiB of LDS per workgroup leaves (tools/arbbench.py, profiles/arbitrary.txt)
+static const PlanForm FORM_ARB = {"resample_arb_kernel", GEOM_ARB, sxfir::ArbTile::TILE, 256, 1, 2, true, 4, 4, TAPS_ARB};
+
 // The ratio whose kernel a tile of interp_tile_kernel runs: x48 is three phase blocks of the x16 kernel, x96 three of the x32 kernel
 static int itile_base(int ratio) { return ratio > 32 ? ratio / 3 : ratio; }
 
@@ -408,6 +425,7 @@ static void resolve_kernels(sxfir_plan *p)
     case GEOM_SYN4: k.syn4 = sxfir::synthesis4_kernel; break;
     case GEOM_SYN4X2: k.syn4x2 = sxfir::synthesis4x2_kernel; break;
     case GEOM_RAT45: k.rat45 = sxfir::resample45_kernel; break;
+    case GEOM_ARB: k.arb = sxfir::resample_arb_kernel; break;
     case GEOM_CX: k.cx = sxfir::decim4_cx_kernel<sxfir::DecimTileArgs>; break;
     case GEOM_MIX: k.mix = sxfir::decim4_cx_kernel<sxfir::MixTileArgs>; break;
     case GEOM_ICX: k.interp_cx = interp_cx_kernel<sxfir::InterpTileArgs>(p->ratio); break;
@@ -445,6 +463,7 @@ static const void *occupancy_instance(const sxfir_plan *p)
     case GEOM_SYN4: return (const void *)k.syn4;
     case GEOM_SYN4X2: return (const void *)k.syn4x2;
     case GEOM_RAT45: return (const void *)k.rat45;
+    case GEOM_ARB: return (const void *)k.arb;
     }
     return nullptr;
 }
@@ -559,6 +578,15 @@ static long long rational_produced(const sxfir_plan *p, long long consumed)
     return (consumed * p->ratio + p->down - 1) / p->down;
 }
 
+// An arbitrary-rate plan's outputs for n_in more inputs, and its time after them: the count rule of include/sxfir_arbitrary.h, through
+// the one function that states it
+static long long arb_count(const sxfir_plan *p, long long n_in, int64_t *t_index_after, uint32_t *t_frac_after)
+{
+    uint64_t n_out = 0;
+    sxfir::arb_outputs(p->arb_t_index, p->arb_t_frac, p->arb_step, p->consumed, (uint64_t)n_in, &n_out, t_index_after, t_frac_after);
+    return (long long)n_out;
+}
+
 // The one list of what a plan owns
 static void free_plan(sxfir_plan *p)
 {
@@ -642,6 +670,16 @@ static void taps_pass8_cx(std::vector<float> &t, const float *planar, int ntaps,
     }
 }
 
+// resample_arb_kernel: row p at (T + 4) p, h[(T - 1 - i) P + p] at i (j descending: ascending window samples), the pad zero; row P
+// repeats row 0 (the second chain of the last phase is phase 0, one sample on)
+static void taps_arb(std::vector<float> &t, const float *taps, int ntaps, int P)
+{
+    const int T = ntaps / P, row = T + 4;
+    t.assign((size_t)(P + 1) * row, 0.0f);
+    for (int p = 0; p <= P; ++p)
+        for (int i = 0; i < T; ++i) t[(size_t)p * row + i] = taps[(T - 1 - i) * P + p % P];
+}
+
 // p->ntaps floats in the layout p->tap_table names (TAPS_PASS8_CX: twice as many, from the planar complex taps)
 static std::vector<float> second_tap_table(const sxfir_plan *p, const float *taps)
 {
@@ -653,6 +691,7 @@ static std::vector<float> second_tap_table(const sxfir_plan *p, const float *tap
     case TAPS_BLOCKS16: taps_blocks16(t, taps, p->ratio, p->rot, p->fmt); break;
     case TAPS_PASS8: taps_pass8(t, taps, p->ratio); break;
     case TAPS_PHASED: taps_phased(t, taps, p->ratio); break;
+    case TAPS_ARB: taps_arb(t, taps, p->ntaps, p->ratio); break;
     }
     return t;
 }
@@ -833,6 +872,10 @@ int sxfir_reset(sxfir_plan *p, void *stream)
     // that was misused on two streams, must not make the next stream's tiles join early or never
     if (p->join_arrived) HIPCHECK(hipMemsetAsync(p->join_arrived, 0, sizeof(unsigned) * (size_t)p->join_tiles, S(stream)));
     p->consumed = p->produced = 0;
+    if (p->kind == KIND_ARBITRARY) {    // t = 0
+        p->arb_t_index = 0;
+        p->arb_t_frac = 0;
+    }
     return SXFIR_OK;
 }
 
@@ -855,8 +898,13 @@ int sxfir_set_position(sxfir_plan *p, int64_t consumed)
 {
     if (!p) return fail(SXFIR_EINVAL, "plan is NULL");
     if (consumed < 0) return fail(SXFIR_EINVAL, "negative stream position");
+    if (p->kind == KIND_ARBITRARY && consumed >= (1ll << 62)) return fail(SXFIR_EINVAL, "stream position out of range");
     p->consumed = (long long)consumed;
-    if (p->kind == KIND_RATIONAL) p->produced = rational_produced(p, p->consumed);
+    if (p->kind == KIND_ARBITRARY) {            // t = consumed * 2^32: the next output on the next input; outputs count from here
+        p->arb_t_index = (long long)consumed;
+        p->arb_t_frac = 0;
+        p->produced = 0;                        // (nothing to count: the rule is arb_outputs', and it starts here)
+    } else if (p->kind == KIND_RATIONAL) p->produced = rational_produced(p, p->consumed);
     else p->produced = p->mode == SXFIR_DECIMATE ? ((long long)consumed + p->ratio - 1) / p->ratio
                                                  : (long long)consumed * p->ratio;
     return SXFIR_OK;
@@ -867,7 +915,9 @@ int sxfir_set_kernel(sxfir_plan *p, int kernel)
     if (!p) return fail(SXFIR_EINVAL, "plan is NULL");
     if (kernel < SXFIR_KERNEL_AUTO || kernel > SXFIR_KERNEL_GENERIC) return fail(SXFIR_EINVAL, "bad kernel id");
     if (kernel == SXFIR_KERNEL_TILED && !p->form)
-        return p->kind == KIND_RATIONAL
+        return p->kind == KIND_ARBITRARY
+                   ? fail(SXFIR_EUNSUPPORTED, "no tiled kernel for ntaps=%d nphases=%d fmt=%d (128 phases x 32 taps on CF32 has one)", p->ntaps, p->ratio, p->fmt)
+               : p->kind == KIND_RATIONAL
                    ? fail(SXFIR_EUNSUPPORTED, "no tiled kernel for ntaps=%d up=%d down=%d fmt=%d (4/5 x 128 on CF32 has one)", p->ntaps, p->ratio, p->down, p->fmt)
                    : fail(SXFIR_EUNSUPPORTED, "no tiled kernel for ntaps=%d ratio=%d fmt=%d mode=%d", p->ntaps, p->ratio, p->fmt, p->mode);
     p->kernel = kernel;
@@ -907,6 +957,11 @@ int sxfir_position(const sxfir_plan *p, int64_t *consumed, int64_t *produced)
 static long long outputs_for(const sxfir_plan *p, long long n_in)
 {
     if (p->kind == KIND_RATIONAL) return rational_produced(p, p->consumed + n_in) - rational_produced(p, p->consumed);
+    if (p->kind == KIND_ARBITRARY) {
+        int64_t ti;
+        uint32_t tf;
+        return arb_count(p, n_in, &ti, &tf);
+    }
     if (p->mode == SXFIR_INTERPOLATE) return n_in * p->ratio;
     const long long D = p->ratio;
     const long long before = (p->consumed + D - 1) / D;

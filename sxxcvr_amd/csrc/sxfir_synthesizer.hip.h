@@ -27,6 +27,7 @@ int sxfir_synthesize(sxfir_plan *p, const void *in_dev, size_t n_in, size_t in_s
     if (n_out_p) *n_out_p = 0;
     if (!p) return fail(SXFIR_EINVAL, "plan is NULL");
     if (p->kind == KIND_RATIONAL) return fail(SXFIR_EINVAL, "%s", RATIONAL_TAKES);
+    if (p->kind == KIND_ARBITRARY) return fail(SXFIR_EINVAL, "%s", ARBITRARY_TAKES);
     if (p->kind != KIND_SYNTHESIZER) return fail(SXFIR_EINVAL, "not a synthesizer plan");
     const long long n_out = outputs_for(p, (long long)n_in);
     if ((n_in && !in_dev) || (n_out > 0 && !out_dev)) return fail(SXFIR_EINVAL, "NULL device buffer");

@@ -1,4 +1,4 @@
-"""Python face of the C ABI in include/sxfir.h, include/sxfir_complex.h, include/sxfir_complex_tx.h, include/sxfir_channelizer.h, include/sxfir_synthesizer.h, include/sxfir_rational.h, include/sxfir_translate.h and include/sxfir_translate_tx.h.
+"""Python face of the C ABI in include/sxfir.h, include/sxfir_complex.h, include/sxfir_complex_tx.h, include/sxfir_channelizer.h, include/sxfir_synthesizer.h, include/sxfir_rational.h, include/sxfir_translate.h, include/sxfir_translate_tx.h and include/sxfir_arbitrary.h.
 
 Device memory comes either from torch (complex64 / int32 CUDA tensors, the
 current torch stream is used) or from the library's own sxfir_malloc for
@@ -472,6 +472,88 @@ class RationalResampler(Resampler):
         ms = C.c_float()
         self._ck(self._lib.sxfir_time_resample(self._plan, C.c_void_p(in_ptr), n_in, in_stride, C.c_void_p(out_ptr), out_stride, iters,
                                                C.c_void_p(stream), C.byref(ms)))
+        return ms.value
+
+    time_passes_ptr = time_resample_ptr
+
+
+def design_arbitrary(nphases, taps_per_phase=32, rate=1.0, beta=8.0):
+    """Unit-gain taps of ArbitraryResampler(taps, nphases, rate=rate): the low-pass of the narrower side at the x nphases raster,
+    design_lowpass(nphases * taps_per_phase, ceil(nphases * max(1, 1 / rate)), beta, nphases).  `rate` is out / in."""
+    import math
+    P = int(nphases)
+    return design_lowpass(P * int(taps_per_phase), int(math.ceil(P * max(1.0, 1.0 / float(rate)))), beta, float(P))
+
+
+class ArbitraryResampler(Resampler):
+    """An arbitrary-rate resampler (include/sxfir_arbitrary.h): a polyphase bank of `nphases` phases with linear interpolation between
+    adjacent phases, at a 64.32 fixed-point time that advances by `step` input samples (unsigned Q32.32, 2^28 .. 2^36) per output.
+    Give `rate` (out / in: step = round(2^32 / rate)) or `step`.  `taps`: real, ntaps a multiple of nphases
+    (design_arbitrary(nphases, rate=rate)); CF32 or CF16.  set_rate() changes the step in mid-stream, the time of the next output stays.
+    The plan is an interpolator plan of ratio `nphases` in its history and contract; outputs_for, position, contract, geometry,
+    set_kernel, set_history_ptr, set_position, reset and close are Resampler's."""
+
+    def __init__(self, taps, nphases, rate=None, step=None, nchan=1, fmt="CF32", device=0, profiling=False):
+        if (rate is None) == (step is None):
+            raise ValueError("give rate (out / in) or step (input samples per output, Q32.32), not both")
+        self._lib = load_sxfir(profiling)
+        self.profiling = bool(profiling)
+        self._plan = C.c_void_p()
+        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        self.mode, self.ratio, self.nchan, self.fmt, self.ntaps = INTERPOLATE, int(nphases), int(nchan), _FMT[fmt], taps.size
+        self._ck(self._lib.sxfir_create_arbitrary(C.byref(self._plan), taps.ctypes.data_as(C.c_void_p), taps.size, int(nphases),
+                                                  self._step_of(rate, step), int(nchan), self.fmt, int(device)))
+
+    @staticmethod
+    def _step_of(rate, step):
+        from fractions import Fraction
+        if step is not None:
+            return int(step)
+        if not rate > 0:
+            raise ValueError("rate must be positive")
+        return int(round(Fraction(1 << 32) / Fraction(rate)))
+
+    def _state(self):
+        n, s, ti, tf = C.c_int(), C.c_uint64(), C.c_int64(), C.c_uint32()
+        self._ck(self._lib.sxfir_plan_arbitrary(self._plan, C.byref(n), C.byref(s), C.byref(ti), C.byref(tf)))
+        return n.value, s.value, ti.value, tf.value
+
+    @property
+    def nphases(self):
+        return self._state()[0]
+
+    @property
+    def step(self):
+        """Input samples per output sample, unsigned Q32.32."""
+        return self._state()[1]
+
+    @property
+    def time(self):
+        """(t_index, t_frac): the time of the next output, whole input samples and the fraction in units of 2^-32."""
+        return self._state()[2:]
+
+    def set_rate(self, rate=None, step=None):
+        """The rate (out / in) or step of the outputs from now on (sxfir_set_rate); the time of the next output stays."""
+        if (rate is None) == (step is None):
+            raise ValueError("give rate or step, not both")
+        self._ck(self._lib.sxfir_set_rate(self._plan, self._step_of(rate, step)))
+
+    def set_time(self, consumed, t_index, t_frac=0):
+        """Place the stream exactly (sxfir_set_time): `consumed` inputs taken, the next output at t_index + t_frac * 2^-32."""
+        self._ck(self._lib.sxfir_set_time(self._plan, int(consumed), int(t_index), int(t_frac)))
+
+    def process_ptr(self, in_ptr, n_in, in_stride, out_ptr, out_stride, stream=0):
+        n_out = C.c_size_t()
+        self._ck(self._lib.sxfir_resample_arbitrary(self._plan, C.c_void_p(in_ptr), n_in, in_stride, C.c_void_p(out_ptr), out_stride,
+                                                    C.byref(n_out), C.c_void_p(stream)))
+        return n_out.value
+
+    def time_resample_ptr(self, in_ptr, n_in, in_stride, out_ptr, out_stride, iters, stream=0):
+        """Mean milliseconds of `iters` back-to-back launches of the resampling kernel (sxfir_time_resample_arbitrary); position,
+        time and history are left alone."""
+        ms = C.c_float()
+        self._ck(self._lib.sxfir_time_resample_arbitrary(self._plan, C.c_void_p(in_ptr), n_in, in_stride, C.c_void_p(out_ptr),
+                                                         out_stride, iters, C.c_void_p(stream), C.byref(ms)))
         return ms.value
 
     time_passes_ptr = time_resample_ptr

@@ -8,6 +8,8 @@ pad slot after every PADROWS rows; chunk D/2 - 2 - 2c + h of a row holds half h 
     python tools/lds_bank_model.py            # the shipped lane maps (/32, /16, /8): extra LDS cycles per tile (expect 0)
     python tools/lds_bank_model.py search     # every assignment of (c.., p, g..) to the lane bits, per ratio and pad period
     python tools/lds_bank_model.py interp     # interp_tile_kernel<L>: window reads, transposition writes, read-back
+    python tools/lds_bank_model.py rational   # resample45_kernel: window reads, output transposition
+    python tools/lds_bank_model.py arbitrary  # resample_arb_kernel: tap and window reads per step, row pad and lane map
 """
 import itertools
 import sys
@@ -126,8 +128,40 @@ def rational_model():
     print("4/5 output transposition, per half of 512 outputs: writes %d, read-back %d extra LDS cycles" % (wr, rb))
 
 
+def arbitrary_model():
+    """sxfir_arb.hip.h, resample_arb_kernel: lane l owns outputs 4l .. 4l + 3 of a tile of 256; output m has its own phase p and
+    window start n (big integers here, as tests/arb_cases.py).  Tap reads: ds_read_b128 of 16-byte slot (ROW / 4) p + k (and of row
+    p + 1), k = 0..7, four groups of 16 lanes.  Window reads: ds_read_b64 at dword 2 (n - n0 + i), i = 0..32, two groups of 32 lanes
+    on 64 banks.  Per step and row stride: extra LDS cycles of the first tile from t = 0, over the cycles without conflicts."""
+    halves = [list(range(32)), list(range(32, 64))]
+    steps = ((5 << 30, "5/4"), (3 << 30, "3/4"), (0x16A09E667, "sqrt 2"), ((1 << 32) + 4295, "1 + 1e-6"), (1 << 31, "1/2"), (1 << 33, "2"))
+    # (shipped: four consecutive outputs per lane, rows of 36 floats; the alternatives: unpadded rows, and outputs l, l + 64, .. per lane)
+    for step, what in steps:
+        for row, strided in ((32, False), (36, False), (36, True)):
+            taps = win = 0
+            for o in range(4):
+                pos = [((l + 64 * o) if strided else (4 * l + o)) * step for l in range(64)]
+                n = [q >> 32 for q in pos]
+                p = [((q & 0xffffffff) * 128) >> 32 for q in pos]
+                for k in range(8):
+                    for r in (0, 1):
+                        taps += group_conflicts(GROUPS, lambda l: (row // 4) * (p[l] + r) + k, 16)
+                for i in range(33):
+                    for grp in halves:
+                        banks = {}
+                        for lane in grp:
+                            a = 2 * (n[lane] + i)
+                            for d in (a, a + 1):
+                                banks.setdefault(d % 64, set()).add(d)
+                        win += max(len(x) for x in banks.values()) - 1
+            print("arbitrary, step %-8s rows of %d floats, %s: tap reads %4d extra cycles over %d, window reads %4d over %d" % (
+                what, row, "outputs l + 64 k per lane" if strided else "outputs 4 l + k per lane ", taps, 4 * 16 * 4, win, 4 * 33 * 2))
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "rational":
+    if len(sys.argv) > 1 and sys.argv[1] == "arbitrary":
+        arbitrary_model()
+    elif len(sys.argv) > 1 and sys.argv[1] == "rational":
         rational_model()
     elif len(sys.argv) > 1 and sys.argv[1] == "interp":
         interp_model()
