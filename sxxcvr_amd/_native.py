@@ -160,6 +160,13 @@ def load_sxfir(profiling=False):
         "sxfir_translate_tx_abi_version": (ci, []),
         "sxfir_create_translating_interpolator": (ci, [P(vp), vp, ci, ci, ci, ci, ci, ci, ci]),
         "sxfir_plan_translation_tx": (ci, [vp, P(ci), P(ci)]),
+        # include/sxfir_bank.h: the tuner bank, K translating decimators in one pass
+        "sxfir_bank_abi_version": (ci, []),
+        "sxfir_create_bank": (ci, [P(vp), vp, ci, ci, ci, vp, vp, ci, ci, ci]),
+        "sxfir_decimate_bank": (ci, [vp, vp, sz, sz, vp, sz, sz, P(sz), vp]),
+        "sxfir_time_decimate_bank": (ci, [vp, vp, sz, sz, vp, sz, sz, ci, vp, P(C.c_float)]),
+        "sxfir_plan_bank": (ci, [vp, P(ci)]),
+        "sxfir_plan_bank_band": (ci, [vp, ci, P(ci), P(ci)]),
         # include/sxfir_arbitrary.h: arbitrary-rate resamplers
         "sxfir_arbitrary_abi_version": (ci, []),
         "sxfir_create_arbitrary": (ci, [P(vp), vp, ci, ci, u64, ci, ci, ci]),

@@ -24,19 +24,19 @@ struct CallIO {
     size_t out_stride;
     long long n_out;
     hipStream_t st;
-    size_t band_stride;       // channelizer plans (sxfir_channelize): outputs between the bands of a channel; synthesizer plans
+    size_t band_stride;       // channelizer and bank plans (sxfir_channelize, sxfir_decimate_bank): outputs between the bands of a channel; synthesizer plans
                               // (sxfir_synthesize): inputs between them; else 0
 };
 
 // What the tiled kernels' 16-byte stores need: an aligned output and, between channels, an even stride -- on CF16 storage the
 // form's own quantum (whole 16-byte units of halves, a stride of 4, for the dense and block kernels); a channelizer's bands are
-// stored like channels: an even band stride too (critically sampled or oversampled).  (LDS-DMA sources need no 16-byte alignment
+// stored like channels: an even band stride too (critically sampled or oversampled), and so are a bank's.  (LDS-DMA sources need no 16-byte alignment
 // -- verified on MI355X, tools/probe_unaligned.hip -- and the edge loads go sample by sample: the input's alignment and strides are
 // the entry point's business alone.)
 static bool stores_aligned(const sxfir_plan *p, const CallIO &c)
 {
     const size_t q = p->form && p->fmt == SXFIR_CF16 ? p->form->cf16_stride : 2;
-    return (uintptr_t)c.out % 16 == 0 && (p->nchan == 1 || c.out_stride % q == 0) && (p->kind != KIND_CHANNELIZER || c.band_stride % 2 == 0);
+    return (uintptr_t)c.out % 16 == 0 && (p->nchan == 1 || c.out_stride % q == 0) && ((p->kind != KIND_CHANNELIZER && p->kind != KIND_BANK) || c.band_stride % 2 == 0);
 }
 
 // Generic path: the next call's history goes to the plan's other buffer (stream_call swaps the two); a synthesizer's, band by band
@@ -431,15 +431,18 @@ static sxfir::InterpTileArgs interp_tile_args(const sxfir_plan *p, const CallIO 
 // interpolator's input -- is turned by table entry (m step) mod den, `step` entries per item: a decimator's mix_s, an interpolator's
 // (den - mix_s) mod den.  The call's first item has the absolute index `first` (64 bits); `halo` items in front of it (the tiled
 // interpolator's image) reach below 0 at the stream's start: the mathematical modulo.
-static sxfir::Mixer mixer_of(const sxfir_plan *p, long long step, long long first, long long halo)
+static sxfir::Mixer mixer_of(const float *w, long long den, long long step, long long first, long long halo)
 {
     sxfir::Mixer m{};
-    const long long den = p->mix_den;
-    m.w = p->mix_dev;
+    m.w = w;
     m.den = (unsigned)den;
     m.step = (unsigned)step;
     m.phase = (unsigned)((((first - halo) % den + den) % den) * step % den);
     return m;
+}
+static sxfir::Mixer mixer_of(const sxfir_plan *p, long long step, long long first, long long halo)
+{
+    return mixer_of(p->mix_dev, p->mix_den, step, first, halo);
 }
 
 // the translating plans' generic kernels: a decimator's outputs count from `produced`, an interpolator's inputs from `consumed`
@@ -464,6 +467,42 @@ static sxfir::MixTileArgs mix_tile_args(const sxfir_plan *p, const CallIO &c, co
     a.lane_step = (unsigned)(8 * s % den);
     a.tile_step = (unsigned)(p->tile * s % den);
     a.stride_step = (unsigned)((long long)a.n_waves % den * a.tile_step % den);
+    return a;
+}
+
+// bank plans (include/sxfir_bank.h): every band's mixer by mixer_of's rule at the call's first output (`produced`), and for the tiled
+// kernel mix_tile_args' three steps per band (n_waves 0: the generic kernel, which reads the mixer alone)
+static void bank_bands(const sxfir_plan *p, sxfir::BankBand (&band)[sxfir::BANK_MAX], long long n_waves)
+{
+    for (int k = 0; k < p->bank_n; ++k) {
+        const long long den = p->bank_den[k], s = p->bank_s[k];
+        const sxfir::Mixer m = mixer_of(p->bank_w[k], den, s, p->produced, 0);
+        sxfir::BankBand &b = band[k];
+        b.w = m.w;
+        b.den = m.den;
+        b.step = m.step;
+        b.phase = m.phase;
+        b.lane_step = (unsigned)(8 * s % den);
+        b.tile_step = (unsigned)(p->tile * s % den);
+        b.stride_step = (unsigned)(n_waves % den * b.tile_step % den);
+        b.rden = 1.0f / (float)den;
+    }
+}
+
+static sxfir::BankGenericArgs bank_generic_args(const sxfir_plan *p, const CallIO &c, long long first)
+{
+    sxfir::BankGenericArgs a{generic_args(p, c, first)};            // (the plain struct is its base)
+    a.m_first = p->produced;
+    bank_bands(p, a.band, 0);
+    return a;
+}
+
+static sxfir::BankTileArgs bank_tile_args(const sxfir_plan *p, const CallIO &c, const LaunchGeom &geom)
+{
+    sxfir::BankTileArgs a{decim_tile_args(p, c, geom)};
+    a.band_stride = (long long)c.band_stride;
+    a.nbands = p->bank_n;
+    bank_bands(p, a.band, a.n_waves);
     return a;
 }
 
@@ -552,6 +591,9 @@ static int launch_interp_tiled(sxfir_plan *p, const CallIO &c, const LaunchGeom 
 static int refuse_tiled(const sxfir_plan *p)
 {
     if (p->kind == KIND_SYNTHESIZER) return fail(SXFIR_EUNSUPPORTED, "tiled synthesizer needs a 16-byte aligned output and an even output stride");
+    if (p->kind == KIND_BANK)
+        return fail(SXFIR_EUNSUPPORTED, "tiled bank needs a 16-byte aligned output, an even output stride, an even band stride and a call that "
+                                        "starts on an output boundary (a stream position that is a multiple of 4)");
     if (p->kind == KIND_ARBITRARY)
         return fail(SXFIR_EUNSUPPORTED, "tiled arbitrary-rate resampler needs a 16-byte aligned output, an even output stride and a step in "
                                         "[2^31, 2^33] (step %llu)", (unsigned long long)p->arb_step);
@@ -591,6 +633,8 @@ static int launch_call(sxfir_plan *p, const CallIO &c, bool *history_done, const
     if (geom.kind == GEOM_GENERIC) {
         if (p->kernel == SXFIR_KERNEL_TILED) return refuse_tiled(p);
         const long long first = p->mode == SXFIR_DECIMATE ? first_offset(p) : 0;        // (a rational plan is an interpolator)
+        if (p->kind == KIND_BANK)       // a band per grid plane
+            return launch(p->k.bank_generic, dim3(grid.x, grid.y, (unsigned)p->bank_n), 256, c.st, bank_generic_args(p, c, first));
         if (int rc = !p->mix_den ? launch(p->k.generic, grid, 256, c.st, generic_args(p, c, first))
                                  : launch(p->k.mix_generic, grid, 256, c.st, mix_generic_args(p, c, first))) return rc;
         if (key && key->hi > key->lo && key_pending) *key_pending = true;    // counted by the caller once the call is certain to commit
@@ -611,6 +655,7 @@ static int launch_call(sxfir_plan *p, const CallIO &c, bool *history_done, const
     // last tile's wave carries the history over)
     case GEOM_RAT45: return launch(p->k.rat45, grid, threads, c.st, decim_tile_args(p, c, geom));
     case GEOM_MIX: return launch(p->k.mix, grid, threads, c.st, mix_tile_args(p, c, geom));
+    case GEOM_BANK: return launch(p->k.bank, grid, threads, c.st, bank_tile_args(p, c, geom));
     // resample_arb_kernel leaves the history to the generic path's pass (history_kernel)
     case GEOM_ARB:
         *history_done = false;
@@ -688,6 +733,7 @@ static int check_io(const sxfir_plan *p, int mode, const CallIO &c)
     if (p->kind == KIND_RATIONAL) return fail(SXFIR_EINVAL, "%s", RATIONAL_TAKES);
     if (p->kind == KIND_ARBITRARY) return fail(SXFIR_EINVAL, "%s", ARBITRARY_TAKES);
     if (p->kind == KIND_SYNTHESIZER) return fail(SXFIR_EINVAL, "a synthesizer plan takes sxfir_synthesize (include/sxfir_synthesizer.h)");
+    if (p->kind == KIND_BANK) return fail(SXFIR_EINVAL, "a bank plan takes sxfir_decimate_bank (include/sxfir_bank.h)");
     if (p->mode != mode) return fail(SXFIR_EINVAL, "plan was created for the other direction");
     if (p->kind == KIND_CHANNELIZER) return fail(SXFIR_EINVAL, "a channelizer plan takes sxfir_channelize (include/sxfir_channelizer.h)");
     return check_buffers(p, c);
@@ -742,7 +788,7 @@ int sxfir_launch_geometry(const sxfir_plan *p, size_t n_in, sxfir_geometry *out)
     out->split = g.split;
     out->tile_samples = g.tile_samples;
     out->n_tiles = g.n_tiles;
-    out->workgroups = g.groups * p->nchan;
+    out->workgroups = g.groups * p->nchan * (p->kind == KIND_BANK && g.kind == GEOM_GENERIC ? p->bank_n : 1);   // (the bank's generic kernel: a grid plane per band)
     out->resident = g.resident;
     return SXFIR_OK;
 }

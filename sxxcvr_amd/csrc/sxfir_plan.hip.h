@@ -21,7 +21,9 @@
 // sxfir_create_arbitrary (sxfir_arbitrary.hip.h): KIND_ARBITRARY, a x ratio interpolator (ratio = nphases) between whose outputs the
 // plan's own are blended, at a fixed-point time that advances by arb_step per output -- an interpolator's history and contract, a
 // time and output counts of its own (arb_outputs, sxfir_arb_index.h).
-enum PlanKind { KIND_REAL = 0, KIND_COMPLEX = 1, KIND_CHANNELIZER = 2, KIND_SYNTHESIZER = 3, KIND_RATIONAL = 4, KIND_ARBITRARY = 5 };
+// sxfir_create_bank (sxfir_bank.hip.h): KIND_BANK, a /ratio decimator with bank_n sets of complex taps (taps_dev: band k's planar a | b at
+// 2 ntaps k) and a mixer per band (bank_num, bank_den, bank_s, bank_w) -- one history, one position, K output rows.
+enum PlanKind { KIND_REAL = 0, KIND_COMPLEX = 1, KIND_CHANNELIZER = 2, KIND_SYNTHESIZER = 3, KIND_RATIONAL = 4, KIND_ARBITRARY = 5, KIND_BANK = 6 };
 
 // The layout of a plan's second tap table (taps_scaled_dev); one function per layout below (second_tap_table).
 // TAPS_SCALED: taps * 2^-31 (exact) in tap order, for the /4 scalar-tap kernels on S32 wire words;
@@ -36,7 +38,7 @@ enum PlanKind { KIND_REAL = 0, KIND_COMPLEX = 1, KIND_CHANNELIZER = 2, KIND_SYNT
 enum TapTable { TAPS_SCALED = 0, TAPS_SUBSET8 = 1, TAPS_PASS8 = 2, TAPS_BLOCKS16 = 3, TAPS_PHASED = 4, TAPS_NONE = 5, TAPS_PASS8_CX = 6, TAPS_ARB = 7 };
 
 // Which kernel family a call launches (LaunchGeom::kind, sxfir_launch.hip.h)
-enum { GEOM_GENERIC = 0, GEOM_MULTI = 1, GEOM_WIDE = 2, GEOM_TILE = 3, GEOM_IPASS = 4, GEOM_ITILE = 5, GEOM_CX = 6, GEOM_CHAN4 = 7, GEOM_SYN4 = 8, GEOM_CHAN4X2 = 9, GEOM_SYN4X2 = 10, GEOM_ICX = 11, GEOM_RAT45 = 12, GEOM_MIX = 13, GEOM_IMIX = 14, GEOM_ARB = 15 };
+enum { GEOM_GENERIC = 0, GEOM_MULTI = 1, GEOM_WIDE = 2, GEOM_TILE = 3, GEOM_IPASS = 4, GEOM_ITILE = 5, GEOM_CX = 6, GEOM_CHAN4 = 7, GEOM_SYN4 = 8, GEOM_CHAN4X2 = 9, GEOM_SYN4X2 = 10, GEOM_ICX = 11, GEOM_RAT45 = 12, GEOM_MIX = 13, GEOM_IMIX = 14, GEOM_ARB = 15, GEOM_BANK = 16 };
 
 // One typed kernel pointer per launch-argument family, and a plan's kernels: resolved once by the plan's creator
 // (resolve_kernels below), read by the occupancy query there and by the launches (sxfir_launch.hip.h).
@@ -52,6 +54,8 @@ typedef void (*MixGenericFn)(sxfir::MixGenericArgs);
 typedef void (*MixTileFn)(sxfir::MixTileArgs);
 typedef void (*InterpMixTileFn)(sxfir::InterpMixTileArgs);
 typedef void (*ArbTileFn)(sxfir::ArbTileArgs);
+typedef void (*BankGenericFn)(sxfir::BankGenericArgs);
+typedef void (*BankTileFn)(sxfir::BankTileArgs);
 struct KernelTable {
     const char *generic_name;    // the plan's generic kernel, as sxfir_launch_geometry reports it, and the instance: every plan of every
     GenericFn generic;           // kind has exactly one (generic_kernel below), the kernel of every call its form does not take
@@ -70,6 +74,8 @@ struct KernelTable {
     MixTileFn mix;               // translating decimators: decim4_cx_kernel<MixTileArgs> (/4 x 128 complex taps, CF32)
     InterpMixTileFn imix;        // translating interpolators: interp_cx_pass_kernel<.., InterpMixTileArgs> (x4 x 128, x8 x 256 complex taps, CF32)
     ArbTileFn arb;               // arbitrary-rate plans (include/sxfir_arbitrary.h): resample_arb_kernel (128 phases x 32 taps, CF32)
+    BankGenericFn bank_generic;  // bank plans (include/sxfir_bank.h), in the place of `generic`: decim_bank_generic_kernel
+    BankTileFn bank;             // ... and decim4_bank_kernel (/4 x 128 complex taps per band, CF32)
 };
 
 // What the geometry and launch code needs to know of a tiled kernel family (FORM_* below).  A plan has at most one, settled at
@@ -98,7 +104,7 @@ struct sxfir_plan {
     uint64_t arb_step;     // arbitrary-rate plans (nphases is `ratio`): input samples per output, Q32.32; else 0
     long long arb_t_index; // ... the time of the next output: whole input samples
     uint32_t arb_t_frac;   // ... and its fraction, Q0.32
-    int bands;             // the band kinds: 4 (= ratio, but for the oversampled plans); else 0.  A synthesizer's hist_dev holds
+    int bands;             // the band kinds: 4 (= ratio, but for the oversampled plans); bank plans: bank_n; else 0.  A synthesizer's hist_dev holds
                            // bands x hist_len / bands samples per channel, band k's at k * hist_len / bands
     int oversample;        // channelizer plans: bands / ratio -- 1 critically sampled (sxfir_create_channelizer), 2 each band at fs/2
                            // (sxfir_create_channelizer_os: ratio 2, bands 4); synthesizer plans likewise: 1 each band at fs/4
@@ -131,6 +137,9 @@ struct sxfir_plan {
     int mix_den, mix_num;  // ... its length (0: the plan has no mixer) and num mod den of the band centre num / den
     int mix_s;             // ... (num * ratio) mod den: table entries per output.  A translating INTERPOLATOR (include/sxfir_translate_tx.h:
                            // mode SXFIR_INTERPOLATE tells the two apart) carries the same three: its inputs are turned, by den - mix_s entries each
+    int bank_n;            // bank plans (include/sxfir_bank.h): the band count (0: not a bank); per band num mod den, den,
+    int bank_num[sxfir::BANK_MAX], bank_den[sxfir::BANK_MAX], bank_s[sxfir::BANK_MAX];   // ... (num * ratio) mod den,
+    float *bank_w[sxfir::BANK_MAX];   // ... and the rotation table: bands of one den share one (free_plan frees each once)
     KernelTable k;         // the instances this plan launches (null: none in this build for that family)
     ProfKnobs prof;        // written and read by the profiling build's hooks alone
     long long consumed, produced;
@@ -168,6 +177,8 @@ static GenericKernel generic_kernel(int kind, int oversample, int mode, int fmt)
         return GenericKernel{"resample_generic_kernel", fmt == SXFIR_CF16 ? (GenericFn)resample_generic_kernel<CF16, CF16> : (GenericFn)resample_generic_kernel<CF32, CF32>};
     case KIND_ARBITRARY:
         return GenericKernel{"resample_arb_generic_kernel", fmt == SXFIR_CF16 ? (GenericFn)resample_arb_generic_kernel<CF16> : (GenericFn)resample_arb_generic_kernel<CF32>};
+    case KIND_BANK:             // on an argument struct of its own (GenericArgs plus the bands): the instance is bank_generic_kernel's
+        return GenericKernel{"decim_bank_generic_kernel", nullptr};
     case KIND_COMPLEX:
         if (rx) SXFIR_GENERIC(decim_cx_generic_kernel, S32, CF32);
         SXFIR_GENERIC(interp_cx_generic_kernel, CF32, S32);
@@ -188,6 +199,13 @@ static MixGenericFn mix_generic_kernel(int mode, int fmt)
                : fmt == SXFIR_CF16 ? decim_cx_generic_kernel<CF16, CF16, MixGenericArgs>
                                    : decim_cx_generic_kernel<S32, CF32, MixGenericArgs>;
     return fmt == SXFIR_CF32 ? interp_mix_generic_kernel<CF32> : fmt == SXFIR_CF16 ? interp_mix_generic_kernel<CF16> : interp_mix_generic_kernel<CF32, S32>;
+}
+
+// Bank plans (include/sxfir_bank.h), on BankGenericArgs: the three instances of an RX kind
+static BankGenericFn bank_generic_kernel(int fmt)
+{
+    using namespace sxfir;
+    return fmt == SXFIR_CF32 ? decim_bank_generic_kernel<CF32, CF32> : fmt == SXFIR_CF16 ? decim_bank_generic_kernel<CF16, CF16> : decim_bank_generic_kernel<S32, CF32>;
 }
 
 // /8, /16, /32 with 32 taps per phase: decim_dense_kernel, non-temporal staging loads for the image rows no other tile reads
@@ -336,6 +354,9 @@ static const PlanForm FORM_CX = {"decim4_cx_kernel", GEOM_CX, 512, 64, 1, 2, tru
 // decim4_cx_kernel<MixTileArgs>: translating plans, /4 x 128 complex taps on CF32: the complex-tap instance's tile, threads, start rule (an output
 // boundary, which at /4 is a stream position that is a multiple of 4: decim_geom), store rule and generations
 static const PlanForm FORM_MIX = {"decim4_mix_kernel", GEOM_MIX, 512, 64, 1, 2, true, 16, 8, TAPS_NONE};
+// decim4_bank_kernel: bank plans, /4 x 128 complex taps per band on CF32: the translating instance's tile, threads, start rule, store rule
+// (a band's row is stored like a channel's: stores_aligned) and generations; 19 584 B of LDS per wave leave its 8 waves per CU
+static const PlanForm FORM_BANK = {"decim4_bank_kernel", GEOM_BANK, 512, 64, 1, 2, true, 16, 8, TAPS_NONE};
 // interp_cx_pass_kernel: complex taps, x4 x 128 and x8 x 256 on CF32, on the pass kernel's frame and with its tiles and generations;
 // a small call keeps four tiles per workgroup as the other complex-tap and band kernels' do (a tile is twice the pass kernel's work)
 static const PlanForm FORM_ICX = {"interp_cx_pass_kernel", GEOM_ICX, TILE_IPASS, 64, 1, 2, true, 8, 8, TAPS_PASS8_CX};
@@ -413,6 +434,7 @@ static void resolve_kernels(sxfir_plan *p)
     const GenericKernel g = generic_kernel(p->kind, p->oversample, p->mode, p->fmt);
     k.generic_name = g.name;
     k.generic = g.fn;
+    if (p->kind == KIND_BANK) k.bank_generic = bank_generic_kernel(p->fmt);
     if (p->mix_den) {           // a translating plan's generic kernel has an argument struct of its own
         // (RX: the label of decim_cx_generic_kernel's mixer instances)
         k.generic_name = p->mode == SXFIR_DECIMATE ? "decim_mix_generic_kernel" : "interp_mix_generic_kernel";
@@ -428,6 +450,7 @@ static void resolve_kernels(sxfir_plan *p)
     case GEOM_ARB: k.arb = sxfir::resample_arb_kernel; break;
     case GEOM_CX: k.cx = sxfir::decim4_cx_kernel<sxfir::DecimTileArgs>; break;
     case GEOM_MIX: k.mix = sxfir::decim4_cx_kernel<sxfir::MixTileArgs>; break;
+    case GEOM_BANK: k.bank = sxfir::decim4_bank_kernel; break;
     case GEOM_ICX: k.interp_cx = interp_cx_kernel<sxfir::InterpTileArgs>(p->ratio); break;
     case GEOM_IMIX: k.imix = interp_cx_kernel<sxfir::InterpMixTileArgs>(p->ratio); break;
     case GEOM_MULTI:
@@ -456,6 +479,7 @@ static const void *occupancy_instance(const sxfir_plan *p)
     case GEOM_IPASS: return (const void *)interp_kernel(p->ratio < 16 ? p->ratio : 16, SXFIR_CF32, false, false);
     case GEOM_CX: return (const void *)k.cx;
     case GEOM_MIX: return (const void *)k.mix;
+    case GEOM_BANK: return (const void *)k.bank;
     case GEOM_ICX: return (const void *)k.interp_cx;
     case GEOM_IMIX: return (const void *)k.imix;
     case GEOM_CHAN4: return (const void *)k.chan4;
@@ -595,6 +619,8 @@ static void free_plan(sxfir_plan *p)
     (void)hipFree(p->hist_dev);
     (void)hipFree(p->hist_alt);
     (void)hipFree(p->mix_dev);
+    for (int k = 0; k < p->bank_n; ++k)                 // (a table shared by several bands: once, at its first band)
+        if (std::find(p->bank_w, p->bank_w + k, p->bank_w[k]) == p->bank_w + k) (void)hipFree(p->bank_w[k]);
     (void)hipFree(p->join_partials);
     (void)hipFree(p->join_arrived);
     prof_free(p);
@@ -718,6 +744,16 @@ static int plan_to_device(sxfir_plan **out, sxfir_plan *p, const float *taps, si
         std::vector<float> w(2 * (size_t)p->mix_den);
         (void)sxfir_design_rotator(p->mix_den, w.data());
         e = upload(&p->mix_dev, w.data(), w.size());
+    }
+    for (int k = 0; e == hipSuccess && k < p->bank_n; ++k) {      // a bank plan's rotation tables, one per distinct den
+        const int *same = std::find(p->bank_den, p->bank_den + k, p->bank_den[k]);
+        if (same != p->bank_den + k) {
+            p->bank_w[k] = p->bank_w[same - p->bank_den];
+            continue;
+        }
+        std::vector<float> w(2 * (size_t)p->bank_den[k]);
+        (void)sxfir_design_rotator(p->bank_den[k], w.data());
+        e = upload(&p->bank_w[k], w.data(), w.size());
     }
     if (e == hipSuccess && p->blocks) {
         if (!p->join_tiles) p->join_tiles = 8LL * p->compute_units * p->occ;

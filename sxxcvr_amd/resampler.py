@@ -651,6 +651,97 @@ class Channelizer(_BandPlan):
         return res[0] if squeeze else res
 
 
+class TranslatingBank(_Plan):
+    """A bank of frequency-translating decimators (include/sxfir_bank.h): K bands at any centres out of one wideband stream in one
+    pass.  `taps`: complex [K, ntaps], band k's own (design_bandpass(ntaps, ratio, num_k, den_k), or anything else); `centres`: K
+    (num, den) pairs.  Band k has the bits of TranslatingDecimator(taps[k], ratio, num_k, den_k) over the same stream.  One history
+    and one position whatever K is: stream state, contract, geometry and kernel choice are a /ratio decimator's, the same methods
+    as Resampler."""
+
+    def __init__(self, taps, ratio, centres, nchan=1, fmt="CF32", device=-1):
+        self._lib = load_sxfir()
+        self._plan = C.c_void_p()
+        taps = np.ascontiguousarray(taps, dtype=np.complex64)
+        centres = [(int(n), int(d)) for n, d in centres]
+        if taps.ndim != 2 or taps.shape[0] != len(centres):
+            raise ValueError("taps must be [K, ntaps] complex, one row per centre (%d centres)" % len(centres))
+        self.mode, self.ratio, self.nchan, self.fmt, self.ntaps = DECIMATE, int(ratio), int(nchan), _FMT[fmt], taps.shape[1]
+        num = (C.c_int * max(len(centres), 1))(*[n for n, _ in centres])
+        den = (C.c_int * max(len(centres), 1))(*[d for _, d in centres])
+        self._ck(self._lib.sxfir_create_bank(C.byref(self._plan), taps.ctypes.data_as(C.c_void_p), taps.shape[1], int(ratio),
+                                             len(centres), num, den, int(nchan), self.fmt, int(device)))
+
+    @property
+    def nbands(self):
+        """The band count K (sxfir_plan_bank)."""
+        n = C.c_int()
+        self._ck(self._lib.sxfir_plan_bank(self._plan, C.byref(n)))
+        return n.value
+
+    @property
+    def centres(self):
+        """The K (num mod den, den) pairs (sxfir_plan_bank_band)."""
+        out = []
+        for k in range(self.nbands):
+            n, d = C.c_int(), C.c_int()
+            self._ck(self._lib.sxfir_plan_bank_band(self._plan, k, C.byref(n), C.byref(d)))
+            out.append((n.value, d.value))
+        return out
+
+    @property
+    def complex_taps(self):
+        f = C.c_int()
+        self._ck(self._lib.sxfir_taps_are_complex(self._plan, C.byref(f)))
+        return bool(f.value)
+
+    def process_ptr(self, in_ptr, n_in, in_stride, out_ptr, out_stride, band_stride, stream=0):
+        """sxfir_decimate_bank: band k of channel c starts at out_ptr + c * out_stride + k * band_stride (samples of the output
+        format); returns the outputs PER BAND."""
+        n_out = C.c_size_t()
+        self._ck(self._lib.sxfir_decimate_bank(self._plan, C.c_void_p(in_ptr), n_in, in_stride, C.c_void_p(out_ptr), out_stride,
+                                               band_stride, C.byref(n_out), C.c_void_p(stream)))
+        return n_out.value
+
+    def time_ptr(self, in_ptr, n_in, in_stride, out_ptr, out_stride, band_stride, iters, stream=0):
+        """Mean milliseconds of `iters` back-to-back launches of the call's kernel (sxfir_time_decimate_bank); the state is left alone."""
+        ms = C.c_float()
+        self._ck(self._lib.sxfir_time_decimate_bank(self._plan, C.c_void_p(in_ptr), n_in, in_stride, C.c_void_p(out_ptr), out_stride,
+                                                    band_stride, iters, C.c_void_p(stream), C.byref(ms)))
+        return ms.value
+
+    def process(self, x, out=None):
+        """x: CUDA tensor [nchan, n] or [n]; complex64 (CF32), int32 words (CF16: half pairs) or int32 wire words [.., n, 2]
+        (S32, complex64 out).  Returns [K, n_out], or [nchan, K, n_out] for a 2-D x.  A caller-given `out` of that shape (or
+        longer rows) supplies its own channel and band strides."""
+        import torch
+        if self.fmt == S32:
+            x = torch.view_as_complex(x.view(torch.float32))               # same 8 bytes per sample
+        out_dtype = torch.complex64 if self.fmt == S32 else x.dtype
+        squeeze = x.dim() == 1
+        x2 = x.unsqueeze(0) if squeeze else x
+        if x2.dim() != 2 or x2.shape[0] != self.nchan or (x2.shape[1] > 1 and x2.stride(1) != 1):
+            raise ValueError("expected a [nchan=%d, n] tensor with unit sample stride" % self.nchan)
+        K = self.nbands
+        n_in = x2.shape[1]
+        n_out = self.outputs_for(n_in)
+        if out is None:
+            # rows of whole 16-byte units: an odd band stride would break the tiled kernel's store alignment
+            q = 4 if self.fmt == CF16 else 2
+            out = torch.empty((self.nchan, K, -(-n_out // q) * q), dtype=out_dtype, device=x2.device)
+        o3 = out.unsqueeze(0) if out.dim() == 2 else out
+        # the kernel writes through a raw pointer: a caller-supplied `out` must really hold the result
+        if (o3.dim() != 3 or o3.shape[0] != self.nchan or o3.shape[1] != K or o3.shape[2] < n_out
+                or (o3.shape[2] > 1 and o3.stride(2) != 1) or o3.dtype != out_dtype or o3.device != x2.device):
+            raise ValueError("out must be a [nchan=%d, K=%d, >=%d] %s tensor with unit sample stride on %s" % (
+                self.nchan, K, n_out, out_dtype, x2.device))
+        got = self.process_ptr(x2.data_ptr(), n_in, x2.stride(0) if self.nchan > 1 else n_in, o3.data_ptr(),
+                               o3.stride(0) if self.nchan > 1 else 0, max(o3.stride(1), n_out),
+                               torch.cuda.current_stream(x2.device).cuda_stream)
+        assert got == n_out
+        res = o3[:, :, :n_out]
+        return res[0] if squeeze else res
+
+
 class Synthesizer(_BandPlan):
     """The 4-band synthesizer (include/sxfir_synthesizer.h): `nbands` sub-bands of the x nbands raster into one wideband stream in one
     pass -- what Channelizer takes apart, put together.  `taps`: the REAL prototype low-pass of a x nbands interpolator
