@@ -109,24 +109,25 @@ def _stride(rng, need, mode):
     return s + 1 if (s % 2 == 1) != (mode == "odd") else s
 
 
-def _layout(rng, nchan, n, banded, chan_mode, band_mode, nesting):
-    """(channel stride, band stride) of one side of a call with n samples per row."""
+def _layout(rng, nchan, n, banded, chan_mode, band_mode, nesting, bands=BANDS):
+    """(channel stride, band stride) of one side of a call with n samples per row and `bands` bands."""
     if not banded:
         return _stride(rng, n, chan_mode), 0
     if nchan == 1 or nesting == "bands inside channels":
         band = _stride(rng, n, band_mode)
-        return _stride(rng, (BANDS - 1) * band + n, chan_mode), band
+        return _stride(rng, (bands - 1) * band + n, chan_mode), band
     chan = _stride(rng, n, chan_mode)
     return chan, _stride(rng, (nchan - 1) * chan + n, band_mode)
 
 
-def _make_call(rng, kind, ratio, nchan, consumed, n, request, perturb, nesting, n_out=None):
+def _make_call(rng, kind, ratio, nchan, consumed, n, request, perturb, nesting, n_out=None, bands=BANDS):
     """One call of n inputs.  perturb: None (an aligned output, even strides on the output side), "offset" (the output starts one
     sample in), "out_stride" / "band_stride" (that stride odd) or "any" (every placement drawn).  The input side is always drawn: a
     view `skew` samples into its buffer, strides padded by nothing, to an even or to an odd figure -- no header asks more of the
     input than one sample's alignment (sxfir_channelizer.hip.h / sxfir_synthesizer.hip.h: "buffers must be aligned to one complex
     sample"; sxfir_synthesizer.h: "an odd in_stride or band_stride stays with the tiled kernel").  n_out: the call's outputs where
-    the kind is not one of KINDS (tests/rate_cases.py: `kind` is then a Kind of its own, without bands on either side)."""
+    the kind is not one of KINDS (tests/rate_cases.py: `kind` is then a Kind of its own; its "bank" has `bands` bands on the output
+    side, tests/arb_sweep_cases.py's kind none)."""
     K = KINDS[kind] if n_out is None else kind
     n_out = outputs_for(kind, ratio, consumed, n) if n_out is None else n_out
     modes = ("tight", "even", "odd")
@@ -141,9 +142,9 @@ def _make_call(rng, kind, ratio, nchan, consumed, n, request, perturb, nesting, 
     elif perturb == "any":
         out_off = int(rng.choice([0, 0, 1]))
         chan_mode, band_mode = str(rng.choice(modes)), str(rng.choice(modes))
-    out_stride, out_band = _layout(rng, nchan, n_out, K.banded_out, chan_mode, band_mode, nesting)
+    out_stride, out_band = _layout(rng, nchan, n_out, K.banded_out, chan_mode, band_mode, nesting, bands)
     skew = int(rng.choice([0, 0, 1, 3, 6]))
-    in_stride, in_band = _layout(rng, nchan, n, K.banded_in, str(rng.choice(modes)), str(rng.choice(modes)), nesting)
+    in_stride, in_band = _layout(rng, nchan, n, K.banded_in, str(rng.choice(modes)), str(rng.choice(modes)), nesting, bands)
     return Call(n, request, out_off, out_stride, skew, in_stride, out_band if K.banded_out else in_band, nesting)
 
 

@@ -1,13 +1,14 @@
-"""The three plan kinds that change the rate by more than a band plan does, or turn the stream while they do -- frequency-translating
-decimators (include/sxfir_translate.h, "translate"), rational resamplers (include/sxfir_rational.h, "rational") and
-frequency-translating interpolators (include/sxfir_translate_tx.h, "translate_tx") -- as tests/band_cases.py has the six band kinds: a
+"""The four plan kinds that change the rate by more than a band plan does, or turn the stream while they do -- frequency-translating
+decimators (include/sxfir_translate.h, "translate"), rational resamplers (include/sxfir_rational.h, "rational"),
+frequency-translating interpolators (include/sxfir_translate_tx.h, "translate_tx") and tuner banks (include/sxfir_bank.h, "bank": K
+translating decimators over one stream) -- as tests/band_cases.py has the six band kinds: a
 seeded generator of streams, a predictor of the kernel each call takes, and the float32 reference of a whole stream, from zero
 history or PLACED (sxfir_set_history + sxfir_set_position) anywhere in a 64-bit stream.  CPU only: torch is never imported.
-tests/test_rate_cases_host.py checks the generator's coverage and the references; tests/test_gpu_rate_sweep.py runs the cases.  The
-calls (Call, their strides and placements) and the sizes' menu are band_cases' own.
+tests/test_rate_cases_host.py checks the generator's coverage and the references; tests/test_gpu_rate_sweep.py runs the cases
+(tests/test_gpu_bank_sweep.py the bank's).  The calls (Call, their strides and placements) and the sizes' menu are band_cases' own.
 
-One description serves the three kinds: `up` outputs for every `down` inputs (translate: up = 1, down = the ratio; translate_tx:
-up = the ratio L, down = 1), so after c inputs ceil(c up / down) outputs exist (rational_cases.n_out_for)."""
+One description serves the four kinds: `up` outputs for every `down` inputs (translate and bank: up = 1, down = the ratio;
+translate_tx: up = the ratio L, down = 1), so after c inputs ceil(c up / down) outputs exist (rational_cases.n_out_for)."""
 import collections
 import math
 
@@ -16,6 +17,7 @@ import numpy as np
 from band_cases import AUTO, CX_RATIOS, GENERIC, GUARD, TILED, Call, Contract, _layout, _make_call, _sizes, _stride     # noqa: F401
 from band_cases import contract as band_contract
 from band_cases import keying_threshold                    # noqa: F401  (the TX kind's S32 cases: the median |y|^2 of a reference)
+from bank_cases import bank_ref
 from gpu_util import random_taps_cx
 from mix_cases import mix_ref, step
 from mix_tx_cases import back_step, mix_tx_ref
@@ -28,13 +30,15 @@ Kind = collections.namedtuple("Kind", "name tiled_shapes tile start_multiple til
 # first figure serves a shape without one (tile_of).  start_multiple: the tiled kernel takes a call whose stream position is a
 # multiple of it (translate_tx: anywhere).  formats: CF32, CF16 and the kind's third -- S32 wire words in (CF32 out) for translate;
 # rational refuses S32, CF16 again; translate_tx, a TX kind: CF32 in, convert_tx wire words out under the plan's keying threshold,
-# as in band_cases.  banded_*: what band_cases._make_call asks of a kind (no bands on either side).  tx: an interpolator of the
-# translating kind -- the mixer turns the INPUT, by its absolute index.
+# as in band_cases; bank: translate's.  banded_*: what band_cases._make_call asks of a kind (bands on the bank's output side alone: K
+# rows per channel, the channelizer's layout).  tx: an interpolator of the translating kind -- the mixer turns the INPUT, by its
+# absolute index.
 KINDS = collections.OrderedDict((k.name, k) for k in (
     Kind("translate", ((128, 1, 4),), {(1, 4): 2048}, 4, "decim4_mix_kernel", "decim_mix_generic_kernel", ("CF32", "CF16", "S32"), False, False, False),
     Kind("rational", ((128, 4, 5),), {(4, 5): 1280}, 5, "resample45_kernel", "resample_generic_kernel", ("CF32", "CF16", "CF16"), False, False, False),
     Kind("translate_tx", ((128, 4, 1), (256, 8, 1)), {(4, 1): 256, (8, 1): 128}, 1, "interp_mix_pass_kernel", "interp_mix_generic_kernel",
          ("CF32", "CF16", "S32"), False, False, True),
+    Kind("bank", ((128, 1, 4),), {(1, 4): 2048}, 4, "decim4_bank_kernel", "decim_bank_generic_kernel", ("CF32", "CF16", "S32"), False, True, False),
 ))
 # rational, generic: the coprime pairs, dealt in turn; taps per phase drawn from 1..40 -- four for the two pairs with a side above 64
 RATIONAL_PAIRS = ((2, 3), (3, 2), (3, 4), (5, 4), (7, 5), (3, 8), (8, 3), (4, 5), (125, 128), (128, 125))
@@ -53,14 +57,32 @@ DENS = (1, 2, 3, 5, 7, 8, 1000, 4096, 65535, 65536)
 PLACES = {"translate": ("far", "input 31", "output 31", "input 32", "output 32"),
           "rational": ("far", "input 31", "output 31", "raster 31", "input 32", "output 32", "raster 32"),
           "translate_tx": ("far", "input 31", "input 32", "output 31", "output 32")}
+PLACES["bank"] = PLACES["translate"]
 # how the four "seam" cases leave the tiled kernel in mid-stream.  translate_tx has no position rule; its fourth seam is "short": a
 # GENERIC call of 1 .. 31 inputs, fewer than the 32-sample history, so that the next history is part old history, part new input
 SEAMS = {"translate": ("offset", "out_stride", "generic", "position"), "rational": ("offset", "out_stride", "generic", "position"),
          "translate_tx": ("offset", "out_stride", "generic", "short")}
+# the bank's are translate's.  Its "out_stride" seam has a second odd stride to show, the band's: of the seam's two perturbed calls
+# (the one that leaves the tiled kernel under AUTO, the one that is refused under a forced TILED) one has an odd out_stride and the
+# other an odd band_stride, in turn over the seeds
+SEAMS["bank"] = SEAMS["translate"]
+# bank: the band count, dealt in turn to the cases of each of the deck's three parts (the tiled shape on CF32, a generic shape on
+# CF32, CF16 / S32): every part has eight slots or more, so every count meets the tiled kernel, the generic one and the 16-bit and
+# wire formats.  The centres are MIXERS, dealt per band, continuing from case to case: one turn for the cases whose calls the tiled
+# kernel takes (the tiled shape on CF32 under the start rule) and one for all others, so that both kernels see every class.  The
+# first case of each turn with three bands or more has its last band a TWIN of band 0, taps and centre.
+BANK_KS = (1, 2, 3, 4, 5, 8, 15, 16)
 
 Case = collections.namedtuple("Case", "ident ntaps up down num den tap_seed nchan fmt data_seed style how place c0 calls")
 # ntaps: all taps (rational, translate_tx: up times the taps per phase).  num, den: the mixer (rational: 0, 0).  how: a seam case's
 # perturbation.  place: "start" (c0 = 0) or one of PLACES; c0: the stream position of the first call.
+BankCase = collections.namedtuple("BankCase", Case._fields + ("centres", "twin"))
+# a bank's case: num = den = 0; centres: K (num, den) pairs; twin: None, or (j, k) -- band k has band j's taps and centre.
+
+
+def nbands_of(case):
+    """The bands on the output side: K of a bank's case, none of any other."""
+    return len(case.centres) if isinstance(case, BankCase) else 0
 
 
 def ratio_of(case):
@@ -102,13 +124,19 @@ def contract(kind, case):
     """The numeric contract the plan must report.  translate: the complex-tap decimator's of the shape (sxfir_translate.h: "z[m] has
     the bits of the sxfir_create_complex plan of the same shape").  rational and translate_tx: the x up interpolator's -- a phase's
     taps in two halves when their count is even, else one chain (sxfir_rational.h, sxfir_complex_tx.h)."""
-    if kind == "translate":
+    if kind in ("translate", "bank"):
         return band_contract("decimate_cx", case.ntaps, case.down)
     return Contract((2 if hist_of(case) % 2 == 0 else 1, 1))
 
 
 def taps_of(kind, case):
-    """Random taps without symmetry: complex for the translating kinds, real for rational."""
+    """Random taps without symmetry: complex for the translating kinds, real for rational.  bank: [K, ntaps], band k's from the
+    seed tap_seed + k -- a twin's from its sibling's."""
+    if kind == "bank":
+        seeds = [case.tap_seed + k for k in range(nbands_of(case))]
+        if case.twin:
+            seeds[case.twin[1]] = seeds[case.twin[0]]
+        return np.stack([random_taps_cx(case.ntaps, s) for s in seeds])
     if kind != "rational":
         return random_taps_cx(case.ntaps, case.tap_seed)
     return rational_taps(case.up, case.ntaps // case.up, case.tap_seed)
@@ -118,6 +146,8 @@ def make_plan(kind, case, h):
     import sxxcvr_amd
     if kind == "translate":
         return sxxcvr_amd.TranslatingDecimator(h, case.down, case.num, case.den, nchan=case.nchan, fmt=case.fmt)
+    if kind == "bank":
+        return sxxcvr_amd.TranslatingBank(h, case.down, case.centres, nchan=case.nchan, fmt=case.fmt)
     if kind == "translate_tx":
         return sxxcvr_amd.TranslatingInterpolator(h, case.up, case.num, case.den, nchan=case.nchan, fmt=case.fmt)
     return sxxcvr_amd.RationalResampler(h, case.up, case.down, nchan=case.nchan, fmt=case.fmt)
@@ -147,17 +177,22 @@ def mixer_num(cls, den, num, ratio):
 
 def s_classes(case):
     """The classes of MIXERS a translating case's (num, den) falls into, from the numbers themselves."""
-    s, g = step(case.num, case.den, ratio_of(case)), math.gcd(ratio_of(case), case.den)
+    return centre_classes(case.num, case.den, ratio_of(case))
+
+
+def centre_classes(num, den, ratio):
+    """s_classes of one (num, den) at a ratio: a bank has one per band."""
+    s, g = step(num, den, ratio), math.gcd(ratio, den)
     out = set()
-    if case.den >= 65535 and s == case.den - g:
-        out.add("s = den - gcd, den %d" % case.den)
+    if den >= 65535 and s == den - g:
+        out.add("s = den - gcd, den %d" % den)
     if s == 1:
         out.add("s = 1")
     if s == 0:
         out.add("s = 0")
-    if case.num < 0:
+    if num < 0:
         out.add("negative num")
-    if case.num > case.den:
+    if num > den:
         out.add("num above den")
     return out
 
@@ -185,18 +220,26 @@ def _first_position(rng, K, up, down, calls, r, place, period=None, among=None):
     return mid - (mid - r) % period
 
 
-def _one_case(rng, kind, index, slot, pair, mixer, place):
+def _one_case(rng, kind, index, slot, pair, mixer, place, bank=None):
     """`pair`: what is dealt in turn to a case that draws its shape -- a rational pair; translate_tx: the parity of the taps per
-    phase, so that the contracts (2, 1) and (1, 1) both occur."""
+    phase, so that the contracts (2, 1) and (1, 1) both occur.  `bank`: (the bank's mixers, one per band; whether the last band is
+    band 0's twin; whether the "out_stride" seam's refused call, not its AUTO call, has the odd out_stride)."""
     K = KINDS[kind]
     shape_tiled, fmt, style, how, keep_rule, which = slot
     num = den = 0
-    if kind == "translate":
+    nbands, centres = 0, ()
+    if kind in ("translate", "bank"):
         ntaps, up, down = K.tiled_shapes[which]
         while not shape_tiled and (ntaps, up, down) in K.tiled_shapes:
             ntaps, down = int(rng.integers(4, 301)), int(rng.choice(CX_RATIOS))         # any count
-        cls, den, num = mixer
-        num = mixer_num(cls, den, num, down)
+        if kind == "translate":
+            cls, den, num = mixer
+            num = mixer_num(cls, den, num, down)
+        else:
+            mixers, twin, swap = bank
+            centres = tuple((mixer_num(cls, d, n, down), d) for cls, d, n in mixers)
+            centres += (centres[0],) if twin else ()
+            nbands = len(centres)
     elif shape_tiled:
         ntaps, up, down = K.tiled_shapes[which]
     elif K.tx:
@@ -241,7 +284,11 @@ def _one_case(rng, kind, index, slot, pair, mixer, place):
 
     def add(n, request, perturb):
         nonlocal consumed, budget
-        calls.append(_make_call(rng, K, None, nchan, None, n, request, perturb, "bands inside channels", n_out=n_out_for(n, up, down, r + consumed)))
+        nesting = "bands inside channels"
+        if nbands:                                          # (a draw of the bank's alone: the other kinds' streams stay as they were)
+            nesting = str(rng.choice(["bands inside channels", "channels inside bands"]))
+        calls.append(_make_call(rng, K, None, nchan, None, n, request, perturb, nesting, n_out=n_out_for(n, up, down, r + consumed),
+                                bands=max(nbands, 1)))
         consumed += n
         budget -= n
 
@@ -263,11 +310,13 @@ def _one_case(rng, kind, index, slot, pair, mixer, place):
             a, b = a + off, b + q - off
         if how == "short":
             b = int(rng.integers(1, hist))                  # fewer inputs than the history holds: the next one is part old, part new
+        # (bank, "out_stride": the odd stride of the call that leaves the tiled kernel and of the refused one -- SEAMS)
+        hows = (how, how) if not (nbands and how == "out_stride") else ("band_stride", how) if swap else (how, "band_stride")
         add(a, int(rng.choice([AUTO, TILED])), None)
-        add(b, GENERIC if how in ("generic", "short") else AUTO, how if how in ("offset", "out_stride") else None)
+        add(b, GENERIC if how in ("generic", "short") else AUTO, hows[0] if how in ("offset", "out_stride") else None)
         add(int(rng.choice([T, T + q, 2 * T])), int(rng.choice([AUTO, TILED])), None)
         if how in ("offset", "out_stride"):
-            add(q * int(rng.integers(1, 60)), TILED, how)   # the same placement under a forced TILED: refused in mid-stream
+            add(q * int(rng.integers(1, 60)), TILED, hows[1])              # the same placement under a forced TILED: refused in mid-stream
         menu = _sizes(rng, T, hist)
         for _ in range(int(rng.integers(0, 3))):
             n = menu[int(rng.integers(len(menu)))]
@@ -302,7 +351,10 @@ def _one_case(rng, kind, index, slot, pair, mixer, place):
         assert t == 0 or (c0 - lead) * t % den != 0, (num, den, up, c0)
     shape = "%dx%d" % (ntaps, up * down) if kind != "rational" else "%dx%d:%d" % (ntaps, up, down)
     ident = "%02d-%s-%s-%dch-%s" % (index, shape, fmt, nchan, style) + ("" if place == "start" else "-" + place.replace(" ", ""))
-    return Case(ident, ntaps, up, down, num, den, 100 + index, nchan, fmt, 7000 + index, style, how, place, c0, tuple(calls))
+    case = Case(ident, ntaps, up, down, num, den, 100 + index, nchan, fmt, 7000 + index, style, how, place, c0, tuple(calls))
+    if kind != "bank":
+        return case
+    return BankCase(*case._replace(ident=ident.replace("-%s-" % fmt, "-%s-K%d-" % (fmt, nbands), 1)), centres, (0, nbands - 1) if twin else None)
 
 
 def cases(kind, seed, n):
@@ -317,7 +369,9 @@ def cases(kind, seed, n):
     own, because only 11 of the 36 cases can reach the tiled kernel: the mixers are dealt to those 11 and to the other 25 apart --
     the first 11 of MIXERS hold both "max" rows and "one" on den 65535 and four dens below 8, the 25 see all of MIXERS --,
     and the four placed cases among the 11 take the four crossings of PLACES, one each (the other eight every place in turn).  Of
-    those four two start at an even c0 and two at an odd one."""
+    those four two start at an even c0 and two at an odd one.
+
+    bank is translate's deck with K and K centres on top (BANK_KS), and the output's nesting drawn per call."""
     K = KINDS[kind]
     rng = np.random.default_rng([seed, 100 + list(KINDS).index(kind)])
     deck = []
@@ -344,6 +398,17 @@ def cases(kind, seed, n):
             out.append(_one_case(rng, kind, i, slot, n_generic % 2, MIXERS[turn[form] % len(MIXERS)], place))
             turn[form] += 1
             turn["placed " + form] += placed
+        elif kind == "bank":
+            part = "form" if slot[0] and slot[1] == "CF32" else "generic" if slot[1] == "CF32" else "other"
+            side = "tiled" if part == "form" and (not placed or slot[4]) else "not tiled"        # (the mixers' turn: BANK_KS)
+            nb = BANK_KS[turn[part] % len(BANK_KS)]
+            twin = nb >= 3 and not turn["twin " + side]
+            mixers = tuple(MIXERS[(turn[side] + k) % len(MIXERS)] for k in range(nb - twin))
+            place = PLACES[kind][n_placed % len(PLACES[kind])] if placed else "start"
+            out.append(_one_case(rng, kind, i, slot, None, None, place, (mixers, twin, (seed + i // 36) % 2 == 1)))
+            turn[part] += 1
+            turn[side] += nb - twin
+            turn["twin " + side] += twin
         else:
             place = PLACES[kind][n_placed % len(PLACES[kind])] if placed else "start"
             out.append(_one_case(rng, kind, i, slot, RATIONAL_PAIRS[n_generic % len(RATIONAL_PAIRS)], MIXERS[i % len(MIXERS)], place))
@@ -358,7 +423,7 @@ def expected_kernel(kind, case, call_index, request=None, assume_aligned=False):
     """"tiled" | "generic" | "history only" | "refused" for call `call_index` of the stream, every call before it having been made
     (a refused one again under AUTO).  The headers' rules: the tiled kernel runs when the shape and format have one and the request is
     not GENERIC, the output is 16-byte aligned, out_stride is even with nchan > 1 and the stream position is a multiple of 4
-    (translate) or 5 (rational) -- translate_tx: any position, so its refused rule is the output's alignment and the even out_stride
+    (translate; bank, which asks for an even band_stride as well) or 5 (rational) -- translate_tx: any position, so its refused rule is the output's alignment and the even out_stride
     alone; under a forced TILED "refused" replaces "generic" -- sxfir_set_kernel's own refusal where the plan
     has no tiled kernel at all.  A call that completes no output only carries its samples into the history, whatever was asked for
     (translate_tx: every input makes L outputs, so this is the call with n = 0 alone, which does nothing).
@@ -372,7 +437,8 @@ def expected_kernel(kind, case, call_index, request=None, assume_aligned=False):
     consumed = position_before(case, call_index)
     if outputs_for(case, consumed, call.n) == 0:
         return "history only"
-    aligned = assume_aligned or (call.out_off % 2 == 0 and (case.nchan == 1 or call.out_stride % 2 == 0))
+    aligned = assume_aligned or (call.out_off % 2 == 0 and (case.nchan == 1 or call.out_stride % 2 == 0)
+                                 and (not KINDS[kind].banded_out or call.band_stride % 2 == 0))
     if form and request != GENERIC and aligned and consumed % KINDS[kind].start_multiple == 0:
         return "tiled"
     return "refused" if request == TILED else "generic"
@@ -436,6 +502,8 @@ def plain_reference(kind, oracle, case, h, x, m_first=0):
     translate_tx: the absolute index of the first INPUT, the mixer's phase again; nothing else of any kind sees it)."""
     if kind == "translate":
         return mix_ref(oracle, h, case.down, x, contract(kind, case), case.num, case.den, m_first)
+    if kind == "bank":                                      # [K, n_out]: band k is the translating decimator of its taps and centre
+        return bank_ref(oracle, h, case.down, x, contract(kind, case), case.centres, m_first)
     if kind == "translate_tx":
         return mix_tx_ref(oracle, h, case.up, x, contract(kind, case)[0], case.num, case.den, m_first)
     return rational_ref(oracle, h, case.up, case.down, x, contract(kind, case)[0])
@@ -449,7 +517,7 @@ def reference(kind, oracle, case, h, x):
     no output of the stream sees what lay in front of the lead; the filter part sees the position only modulo its period -- `down`
     input samples, which are `up` outputs --, and lead = c0 modulo down keeps it; the translating plan's rotation alone sees the
     absolute output index m, and mix_ref takes that as a Python int: the first output of x has m = (c0 - lead) / down, so that the
-    stream's first has the true ceil(c0 / down).
+    stream's first has the true ceil(c0 / down).  A bank is that per band ([K, n_out]: bank_cases.bank_ref).
 
     translate_tx (mix_tx_cases.mix_tx_ref over the lead and the stream with m_first = c0 - lead, the lead's L lead outputs dropped):
     the same holds with less to say.  The filter -- the complex-tap interpolator over the rotated input -- sees the position not at
@@ -460,7 +528,7 @@ def reference(kind, oracle, case, h, x):
     lead = lead_of(case)
     assert (case.c0 - lead) % case.down == 0 and (lead == 0 or lead >= hist_len(case))
     y = plain_reference(kind, oracle, case, h, x, (case.c0 - lead) // case.down)
-    return y[n_out_for(lead, case.up, case.down):]
+    return y[..., n_out_for(lead, case.up, case.down):]
 
 
 def stored_words(oracle, fmt, ref, thr2=None):

@@ -488,6 +488,59 @@ def test_process_takes_tensors(oracle, P, T, fmt, nchan, name):
     same(got, want, "process() over two calls")
 
 
+@pytest.mark.parametrize("P,T,kernel,name", [(128, 32, KERNEL_AUTO, TILED), (7, 8, KERNEL_AUTO, GENERIC)])
+def test_timed_pass_in_mid_stream(oracle, P, T, kernel, name):
+    """sxfir_time_resample_arbitrary in the middle of a stream: two back-to-back passes write the words of the call that the
+    stream makes next, between guards that stay; position, time and step are as they were; and the real call after it gives the
+    reference's bits -- the history was left alone."""
+    import torch
+    h = arb_taps(P, T)
+    n, a, b = 2300, 700, 900
+    rig = Rig(oracle, streams(2, n, 27))
+    plan = ArbitraryResampler(h, P, step=SQRT2, nchan=2)
+    plan.set_kernel(kernel)
+    ref = rig.ref(h, P, SQRT2, plan.contract[0])
+    model = Stream(SQRT2)
+    first = rig.call(plan, model, 0, a, name)
+    k0 = first.shape[1]
+    n_out = count(model.t, model.step, model.consumed, b)[0]
+    assert plan.outputs_for(b) == n_out > 0 and plan.geometry(b)["kernel"] == name
+    row = 2 * GUARD + n_out + n_out % 2
+    buf = torch.full((2, row * rig.wps), _i32(FILL), dtype=torch.int32, device="cuda")
+    ms = plan.time_resample_ptr(rig.xg.data_ptr() + rig.sb * a, b, rig.stride, buf.data_ptr() + rig.sb * GUARD, row, 2,
+                                torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert ms > 0.0
+    rig.check_state(plan, model)
+    got = buf.cpu().numpy().view(np.uint32).reshape(2, row, rig.wps)
+    assert np.all(got[:, :GUARD] == FILL) and np.all(got[:, GUARD + n_out:] == FILL), "the guard around the timed passes' outputs was written"
+    want = ref[:, k0:k0 + n_out * rig.wps]
+    same(np.ascontiguousarray(got[:, GUARD:GUARD + n_out]).reshape(2, -1), want, "what the timed passes wrote")
+    second = rig.call(plan, model, a, b, name)
+    same(second, want, "the call after the timed passes")
+    same(np.concatenate([first, second, rig.call(plan, model, a + b, n - a - b, name)], axis=1), ref, "the whole stream")
+
+
+@pytest.mark.parametrize("P,T", [(2, 1), (2, 2), (4096, 1), (4096, 2)])
+def test_create_at_the_ends_of_the_range(oracle, P, T):
+    """The fewest and the most phases the header allows with one and two taps per phase: a history of 2 samples, the contracts
+    (1, 1) and (2, 1), z = frac * P at its 44 bits.  One short stream at sqrt(2), placed on the last 2^-14 of a sample so that its
+    first output is of the last phase at either P (asserted from the model), in two calls, against the reference."""
+    h = arb_taps(P, T)
+    n, t0 = 600, 0xFFFC0000
+    rig = Rig(oracle, streams(2, n, 28))
+    plan = ArbitraryResampler(h, P, step=SQRT2, nchan=2)
+    assert plan.nphases == P and tuple(plan.contract) == ((2, 1) if T == 2 else (1, 1)) and plan.contract.rot == 0
+    with pytest.raises(sxxcvr_amd.NativeError) as ei:
+        plan.set_kernel(KERNEL_TILED)
+    assert ei.value.code == EUNSUPPORTED
+    plan.set_time(0, 0, t0)
+    times = times_of(SQRT2, n, 0, t0)
+    assert position(times[0], P)[1] == P - 1 and wraps(times, P) >= 1 and len(times) > 400
+    want = rig.ref(h, P, SQRT2, plan.contract[0], 0, t0)
+    same(rig.stream(plan, Stream(SQRT2, 0, t0), [n // 3, n - n // 3], [GENERIC] * 2), want, "%d phases x %d taps" % (P, T))
+
+
 # ---- 5. against code that already ships ----------------------------------------------------------------------------------------
 def test_against_the_rational_plan(oracle):
     """4 phases at step 5/4 from t = 0: alpha = 0 throughout, so the outputs are those of sxfir_create_rational(4, 5) over the same

@@ -2,7 +2,8 @@
 reference (mix_cases.mix_ref), and on the GPU the TranslatingDecimator of the same band under the same kernel request.
 
 Every call goes through `Rig.call`: each band's row lands between two guards of fill words that must come back untouched, and the
-plan's position, outputs_for and geometry(...)["kernel"] are checked around it."""
+plan's position, outputs_for and geometry(...)["kernel"] are checked around it.  The two layout tests (`_laid_out`) name both
+strides themselves: bands and channels that overlap, and channels inside bands.  The seeded sweep is tests/test_gpu_bank_sweep.py."""
 import ctypes as C
 
 import numpy as np
@@ -146,6 +147,89 @@ def test_strides(oracle):
     one = Rig(oracle, streams(1, n, 16))
     same(one.call(bank4(hs, centres), 0, n, odd_band=True), ref[:1], "one channel, odd band stride under AUTO")
     one.call(bank4(hs, centres, KERNEL_TILED), 0, n, TILED, expect=EUNSUPPORTED, odd_band=True)
+
+
+def _laid_out(rig, plan, n, out_stride, band_stride, expect=None, timed=False):
+    """sxfir_decimate_bank (timed: sxfir_time_decimate_bank, one pass) over inputs [0, n) with the two strides as given, the first
+    output GUARD samples into a buffer of fill that holds either nesting.  Returns [nchan, K, words], everything else still fill; with
+    `expect` the call must fail with that code and leave the plan and the whole buffer alone."""
+    import torch
+    K, nchan = plan.nbands, rig.nchan
+    n_out = plan.outputs_for(n)
+    pos = plan.position
+    at = [[GUARD + c * out_stride + k * band_stride for k in range(K)] for c in range(nchan)]
+    total = max(max(r) for r in at) + n_out + GUARD
+    buf = torch.full((total, rig.wps), _i32(FILL), dtype=torch.int32, device="cuda")
+    args = (rig.xg.data_ptr(), n, rig.stride, buf.data_ptr() + rig.sb * GUARD, out_stride, band_stride)
+    stream = torch.cuda.current_stream().cuda_stream
+    if expect is not None:
+        with pytest.raises(sxxcvr_amd.NativeError) as ei:
+            plan.time_ptr(*args, 1, stream) if timed else plan.process_ptr(*args, stream)
+        torch.cuda.synchronize()
+        assert ei.value.code == expect and plan.position == pos
+        assert np.all(buf.cpu().numpy().view(np.uint32) == FILL), "a refused call wrote to the output"
+        return None
+    if timed:
+        assert plan.time_ptr(*args, 1, stream) > 0.0 and plan.position == pos
+    else:
+        assert plan.process_ptr(*args, stream) == n_out and plan.position == (pos[0] + n, pos[1] + n_out)
+    torch.cuda.synchronize()
+    got = buf.cpu().numpy().view(np.uint32)
+    rows = np.zeros(total, dtype=bool)
+    for r in at:
+        for a in r:
+            assert not rows[a:a + n_out].any(), "two rows overlap"
+            rows[a:a + n_out] = True
+    assert np.all(got[~rows] == FILL), "something outside the %d x %d rows was written" % (K, nchan)
+    return np.stack([np.stack([got[a:a + n_out].reshape(-1) for a in r]) for r in at])
+
+
+def test_overlapping_bands_and_channels(oracle):
+    """Three channels, three bands, strides under which neither nesting holds: out_stride one short of a channel's three rows, and
+    band_stride far below three channels' rows.  SXFIR_EINVAL whatever the kernel request (check_band_layout comes in front of the
+    kernel choice), plan and output untouched, through sxfir_decimate_bank and sxfir_time_decimate_bank; the next call gives the
+    reference's bits."""
+    hs, centres, K = HS[:3], [(3, 7), (123, 1000), (12345, 65536)], 3
+    n = TILE + 144
+    rig = Rig(oracle, streams(3, n, 18))
+    ref = rig.ref(hs, 4, bank4(hs, centres).contract, centres)
+    n_out = n // 4
+    band = n_out + 12                                           # an even band stride, and an even out_stride once it holds the rows
+    short = (K - 1) * band + n_out - 1
+    assert band % 2 == 0 and (short + 1) % 2 == 0 and n_out <= band < 2 * short + n_out and short >= n_out
+    for request, name in ((KERNEL_AUTO, TILED), (KERNEL_TILED, TILED), (KERNEL_GENERIC, GENERIC)):
+        plan = bank4(hs, centres, request, nchan=3)
+        assert plan.geometry(n)["kernel"] == name
+        _laid_out(rig, plan, n, short, band, expect=EINVAL)
+        assert b"overlap" in plan._lib.sxfir_last_error()
+        _laid_out(rig, plan, n, short, band, expect=EINVAL, timed=True)
+        assert b"overlap" in plan._lib.sxfir_last_error()
+        same(_laid_out(rig, plan, n, short + 1, band), ref, "one sample more: bands inside channels, request %d" % request)
+        plan.reset()
+        same(rig.call(plan, 0, n, name), ref, "the call after the refused ones, request %d" % request)
+
+
+def test_channels_inside_bands(oracle):
+    """The output's other nesting: a band's three channels in a row, band after band (band_stride >= (nchan - 1) * out_stride +
+    n_out).  One tiled call of a tile and 140 samples, the same call on the generic kernel, and a timed pass of each: the
+    reference's bits in every row, nothing written between them."""
+    hs, centres = HS[:3], [(123, 1000), (65535, 65536), (1, 3)]
+    n = TILE + 140
+    rig = Rig(oracle, streams(3, n, 19))
+    ref = rig.ref(hs, 4, bank4(hs, centres).contract, centres)
+    n_out = n // 4
+    chan = n_out + 7                                            # even, larger than the block
+    band = 2 * chan + n_out + 9                                 # even, larger than three channels' rows
+    assert chan % 2 == 0 and band % 2 == 0 and chan < 2 * band + n_out
+    for request, name in ((KERNEL_TILED, TILED), (KERNEL_AUTO, TILED), (KERNEL_GENERIC, GENERIC)):
+        plan = bank4(hs, centres, request, nchan=3)
+        g = plan.geometry(n)
+        assert g["kernel"] == name and g["tiled"] == (name == TILED), g
+        same(_laid_out(rig, plan, n, chan, band, timed=True), ref, "%s, a timed pass" % name)
+        same(_laid_out(rig, plan, n, chan, band), ref, name)
+    # an odd stride between the channels of a band: the generic kernel under AUTO, refused under a forced TILED
+    same(_laid_out(rig, bank4(hs, centres, nchan=3), n, chan + 1, band + 2), ref, "odd out_stride under AUTO")
+    _laid_out(rig, bank4(hs, centres, KERNEL_TILED, nchan=3), n, chan + 1, band + 2, expect=EUNSUPPORTED)
 
 
 # ---- more tiles than waves: the tile loop's second iteration ----------------------------------------------------------------------

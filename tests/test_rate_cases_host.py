@@ -9,6 +9,7 @@ import pytest
 
 import rate_cases as rc
 from band_cases import AUTO, CX_RATIOS, GENERIC, TILED, Call
+from bank_cases import bank_f64
 from mix_cases import bound as mix_bound, mix_f64, step
 from mix_tx_cases import back_step, bound as mix_tx_bound, mix_tx_f64
 from rate_cases import KINDS, SWEEP_COUNT, SWEEP_SEED
@@ -41,7 +42,8 @@ def coverage(kind, cases):
         c["CF16 placed"] += case.fmt == "CF16" and case.place != "start"
         c["S32 placed"] += case.fmt == "S32" and case.place != "start"
         c["3 ch with a seam"] += case.nchan == 3 and case.style == "seam"
-        c["refused in mid-stream on an odd stride"] += any(x == "refused" and form and 0 < i and call.out_stride % 2 == 1 and case.nchan > 1
+        c["refused in mid-stream on an odd stride"] += any(x == "refused" and form and 0 < i
+                                                           and ((call.out_stride % 2 == 1 and case.nchan > 1) or call.band_stride % 2 == 1)
                                                            for i, (x, call) in enumerate(zip(labels, case.calls)))
         if case.place != "start":
             c["placed"] += 1
@@ -55,7 +57,9 @@ def coverage(kind, cases):
         for index, log2, i in rc.crossings(case):
             c["%s passes 2^%d" % (index, log2)] += 1
             c["%s passes 2^%d in a %s call" % (index, log2, labels[i])] += 1
-        if kind != "rational":
+        if kind == "bank":
+            bank_coverage(c, case, labels)
+        elif kind != "rational":
             c["den %d" % case.den] += 1
             for cls in rc.s_classes(case):
                 c[cls] += 1
@@ -66,12 +70,50 @@ def coverage(kind, cases):
             c["den below 8 on the tiled kernel"] += case.den < 8 and "tiled" in labels
         else:
             c["pair %d/%d" % (case.up, case.down)] += 1
-        if kind != "translate":
+        if kind not in ("translate", "bank"):
             c["odd taps per phase"] += rc.hist_of(case) % 2 == 1
         if KINDS[kind].tx and form:
             c["%dx%d %s" % (case.ntaps, case.up, case.style)] += 1
             c["%dx%d placed" % (case.ntaps, case.up)] += case.place != "start"
     return c
+
+
+BANK_CLASSES = ("s = den - gcd, den 65535", "s = den - gcd, den 65536", "s = 1", "s = 0", "negative num", "num above den")
+
+
+def bank_coverage(c, case, labels):
+    """The bank's own counts: per band what a translating case counts once, and what only a plan with bands can show."""
+    nb, form = rc.nbands_of(case), rc.has_form("bank", case)
+    assert nb == len(case.centres) >= 1
+    c["K %d" % nb] += 1
+    c["K %d on %s" % (nb, "the tiled shape" if form else "a generic shape")] += 1
+    c["K %d on %s" % (nb, case.fmt)] += 1
+    seen = set()
+    for num, den in case.centres:
+        seen |= rc.centre_classes(num, den, case.down)
+        c["den %d" % den] += 1
+        c["den below 8 on the tiled kernel"] += den < 8 and "tiled" in labels
+    for cls in seen:
+        c[cls] += 1
+        c["%s, at another ratio than 4" % cls] += case.down != 4
+        for label in ("tiled", "generic"):
+            c["%s, on a %s call" % (cls, label)] += label in labels
+    c["two bands share a den and differ in num"] += any(a[1] == b[1] and a[0] % a[1] != b[0] % b[1]
+                                                        for i, a in enumerate(case.centres) for b in case.centres[i + 1:])
+    if case.twin:
+        j, k = case.twin
+        assert j != k and case.centres[j] == case.centres[k] and np.array_equal(rc.taps_of("bank", case)[j], rc.taps_of("bank", case)[k])
+        c["twin bands"] += 1
+        c["twin bands on a %s call" % ("tiled" if "tiled" in labels else "generic")] += 1
+    for i, (label, call) in enumerate(zip(labels, case.calls)):
+        inside = call.nesting if case.nchan > 1 else "bands inside channels"         # (one channel: the strides name one nesting alone)
+        c["%s on a %s call" % (inside, label)] += 1
+        c["a skewed input on a %s call" % label] += call.skew > 0
+        c["input off the 16-byte raster on a %s call" % label] += (call.skew * (4 if case.fmt == "CF16" else 8)) % 16 != 0
+        c["an odd band stride leaves the tiled kernel in mid-stream"] += i > 0 and form and call.band_stride % 2 == 1 and label in ("generic", "refused") \
+            and "tiled" in labels[:i]
+        c["more than two bands and more than two channels on a %s call" % label] += nb > 2 and case.nchan > 2
+        c["sixteen bands on a %s call" % label] += nb == 16
 
 
 def needed(kind):
@@ -92,8 +134,17 @@ def needed(kind):
         need += ["s = den - gcd, den 65535", "s = den - gcd, den 65536", "s = 1", "s = 0", "negative num", "num above den", "den below 8 on the tiled kernel"]
     else:
         need += ["pair %d/%d" % p for p in rc.RATIONAL_PAIRS]
-    if kind != "translate":
+    if kind not in ("translate", "bank"):
         need += ["odd taps per phase"]
+    if kind == "bank":
+        need += ["K %d" % k for k in rc.BANK_KS] + ["K 16 on the tiled shape", "K 16 on a generic shape"]
+        need += ["%s, on a %s call" % (cls, label) for cls in BANK_CLASSES for label in ("tiled", "generic")]
+        need += ["%s, at another ratio than 4" % cls for cls in BANK_CLASSES]
+        need += ["%s on a %s call" % (nesting, label) for nesting in ("bands inside channels", "channels inside bands") for label in ("tiled", "generic")]
+        need += ["a skewed input on a tiled call", "input off the 16-byte raster on a tiled call", "two bands share a den and differ in num",
+                 "twin bands on a tiled call", "twin bands on a generic call", "an odd band stride leaves the tiled kernel in mid-stream",
+                 "more than two bands and more than two channels on a tiled call", "more than two bands and more than two channels on a generic call",
+                 "sixteen bands on a tiled call", "sixteen bands on a generic call"]
     return need
 
 
@@ -120,6 +171,10 @@ def test_the_sweep_covers_what_it_is_for(kind):
         assert c["placed, start rule kept"] == 2 and c["placed, start rule broken"] == 2, c
     # at most a quarter of all calls compute nothing (refused calls and calls that complete no output -- translate_tx: n = 0 -- together)
     assert 4 * (c["refused calls"] + c["history only calls"]) <= c["calls"], c
+    if kind == "bank":
+        assert c["K 16 on CF16"] + c["K 16 on S32"] >= 1, c
+        for x in cases:
+            assert all(0 <= step(num, den, x.down) < den <= 65536 for num, den in x.centres), x.ident
     if kind == "translate":
         # the mixer at its limits: num 65535 at /4 on den 65536 has s = 65532, as the tiled kernel's comments count on
         assert rc.mixer_num("max", 65536, None, 4) == 65535 and step(65535, 65536, 4) == 65532
@@ -140,6 +195,12 @@ def test_every_draw_is_a_call_the_entry_point_accepts(kind):
         if kind == "translate":
             assert case.up == 1 and case.down in CX_RATIOS and 4 <= case.ntaps <= 300 and 1 <= case.den <= 65536, case.ident
             assert -2 ** 31 <= case.num < 2 ** 31, case.ident
+        elif kind == "bank":
+            # sxfir_create_bank: nbands in 1 .. 16, every den in 1 .. 65536, num any int
+            assert case.up == 1 and case.down in CX_RATIOS and 4 <= case.ntaps <= 300 and (case.num, case.den) == (0, 0), case.ident
+            assert 1 <= rc.nbands_of(case) <= 16 and rc.nbands_of(case) in rc.BANK_KS, case.ident
+            assert all(1 <= den <= 65536 and -2 ** 31 <= num < 2 ** 31 for num, den in case.centres), case.ident
+            assert rc.taps_of(kind, case).shape == (rc.nbands_of(case), case.ntaps), case.ident
         elif kind == "translate_tx":
             assert case.down == 1 and case.up in CX_RATIOS and case.ntaps % case.up == 0 and 1 <= case.ntaps // case.up, case.ident
             assert (case.ntaps <= 300 or (case.ntaps, case.up, case.down) in K.tiled_shapes) and 1 <= case.den <= 65536, case.ident
@@ -160,8 +221,21 @@ def test_every_draw_is_a_call_the_entry_point_accepts(kind):
         for call in case.calls:
             n_out = n_out_for(call.n, case.up, case.down, pos)
             pos += call.n
-            assert call.request in (AUTO, TILED, GENERIC) and call.out_off in (0, 1) and call.skew >= 0 and call.band_stride == 0, case.ident
+            assert call.request in (AUTO, TILED, GENERIC) and call.out_off in (0, 1) and call.skew >= 0, case.ident
             assert call.in_stride >= call.n and call.out_stride >= n_out, (case.ident, call)
+            if kind != "bank":
+                assert call.band_stride == 0, case.ident
+                continue
+            # check_bank_io and check_band_layout (sxfir_bank.hip.h, sxfir_launch.hip.h), restated: a band stride that holds the
+            # block, and one of the two nestings
+            nb, nc = rc.nbands_of(case), case.nchan
+            assert call.band_stride >= n_out, (case.ident, call)
+            bands_inside = call.out_stride >= (nb - 1) * call.band_stride + n_out
+            channels_inside = call.out_stride >= n_out and call.band_stride >= (nc - 1) * call.out_stride + n_out
+            assert nc == 1 or bands_inside or channels_inside, (case.ident, call)
+            if nc > 1:                                      # (the nesting the call was drawn with is the one its strides state)
+                assert channels_inside if call.nesting == "channels inside bands" else bands_inside, (case.ident, call)
+                assert n_out == 0 or nb == 1 or bands_inside != channels_inside, (case.ident, call)
 
 
 def test_the_predictor_on_hand_made_calls():
@@ -257,11 +331,17 @@ def test_the_placed_reference_is_the_plain_one_at_the_lead(oracle, kind):
         raw, xs = rc.stream_input(kind, case, oracle)
         whole = rc.plain_reference(kind, oracle, case, h, xs[0])
         got = rc.reference(kind, oracle, near, h, xs[0])
-        assert got.size == n_out_for(xs.shape[1] - lead, case.up, case.down, lead) and got.size == whole.size - n_out_for(lead, case.up, case.down)
-        assert np.array_equal(got.view(np.uint32), whole[whole.size - got.size:].view(np.uint32)), case.ident
+        assert got.shape[-1] == n_out_for(xs.shape[1] - lead, case.up, case.down, lead) and got.shape[-1] == whole.shape[-1] - n_out_for(lead, case.up, case.down)
+        assert np.array_equal(got.view(np.uint32), whole[..., whole.shape[-1] - got.shape[-1]:].view(np.uint32)), case.ident
         if kind == "translate" and (case.c0 - lead) // case.down * step(case.num, case.den, case.down) % case.den:
             far = rc.reference(kind, oracle, case, h, xs[0])
             assert far.shape == got.shape and not np.array_equal(far.view(np.uint32), got.view(np.uint32)), "the far phase is not the near one"
+        if kind == "bank":
+            far = rc.reference(kind, oracle, case, h, xs[0])
+            assert far.shape == got.shape == (rc.nbands_of(case), got.shape[-1])
+            for k, (num, den) in enumerate(case.centres):
+                if (case.c0 - lead) // case.down * step(num, den, case.down) % den:
+                    assert not np.array_equal(far[k].view(np.uint32), got[k].view(np.uint32)), "band %d: the far phase is not the near one" % k
         if kind == "translate_tx" and back_step(case.num, case.den, case.up):
             far = rc.reference(kind, oracle, case, h, xs[0])
             assert far.shape == got.shape and np.count_nonzero(far.view(np.uint32) != got.view(np.uint32)) > got.size // 2, "the far phase is not the near one"
@@ -295,6 +375,10 @@ def test_the_placed_reference_is_the_fp64_definition(oracle, kind):
             m_true = -(-case.c0 // case.down)                                   # ceil(c0 / ratio): sxfir_set_position's `produced`
             want = mix_f64(h, case.down, case.num, case.den, x, m_true - skip)[skip:]
             b = mix_bound(h, x, want)
+        elif kind == "bank":                                                    # the translating decimator's definition and bound, band by band
+            m_true = -(-case.c0 // case.down)
+            want = bank_f64(h, case.down, x, case.centres, m_true - skip)[:, skip:]
+            b = np.stack([mix_bound(h[k], x, want[k]) for k in range(rc.nbands_of(case))])
         elif kind == "translate_tx":
             # the first sample of x is input c0 - lead of the stream: the true index, a Python int of 41 bits in the "far" cases
             want = mix_tx_f64(h, case.up, case.num, case.den, x, case.c0 - lead)[skip:]
@@ -304,7 +388,7 @@ def test_the_placed_reference_is_the_fp64_definition(oracle, kind):
             b = np.full(want.shape, rational_bound(h, x))
         assert got.shape == want.shape and got.size > 0, case.ident
         err = np.maximum(np.abs(got.real - want.real), np.abs(got.imag - want.imag)) if kind != "rational" else np.abs(got - want)
-        print("%s %s from %d: worst error %.3g, bound there %.3g" % (kind, case.ident, case.c0, err.max(), b[err.argmax()]))
+        print("%s %s from %d: worst error %.3g, bound there %.3g" % (kind, case.ident, case.c0, err.max(), b.ravel()[err.argmax()]))
         assert np.all(err <= b), case.ident
 
 
