@@ -10,6 +10,6 @@ libraries and mirrors the reference's Python-facing call pattern; there is no
 CPU implementation and nothing here imports the oracle.
 """
 from ._native import NativeError, load_sxfir  # noqa: F401
-from .resampler import ArbitraryResampler, Channelizer, ComplexInterpolator, PipelinedResampler, RationalResampler, Resampler, Synthesizer, TranslatingBank, TranslatingDecimator, TranslatingInterpolator, design_arbitrary, design_bandpass, design_lowpass, design_rational, design_rotator, pin_array, synth_fill, unpin_array  # noqa: F401
+from .resampler import ArbitraryResampler, Channelizer, ComplexInterpolator, PipelinedResampler, RationalResampler, Resampler, Synthesizer, TranslatingBank, TranslatingCombiner, TranslatingDecimator, TranslatingInterpolator, design_arbitrary, design_bandpass, design_lowpass, design_rational, design_rotator, pin_array, synth_fill, unpin_array  # noqa: F401
 
-__all__ = ["NativeError", "load_sxfir", "Resampler", "ComplexInterpolator", "RationalResampler", "ArbitraryResampler", "TranslatingDecimator", "TranslatingInterpolator", "TranslatingBank", "Channelizer", "Synthesizer", "PipelinedResampler", "design_lowpass", "design_bandpass", "design_rational", "design_arbitrary", "design_rotator", "synth_fill", "pin_array", "unpin_array"]
+__all__ = ["NativeError", "load_sxfir", "Resampler", "ComplexInterpolator", "RationalResampler", "ArbitraryResampler", "TranslatingDecimator", "TranslatingInterpolator", "TranslatingBank", "TranslatingCombiner", "Channelizer", "Synthesizer", "PipelinedResampler", "design_lowpass", "design_bandpass", "design_rational", "design_arbitrary", "design_rotator", "synth_fill", "pin_array", "unpin_array"]

@@ -167,6 +167,13 @@ def load_sxfir(profiling=False):
         "sxfir_time_decimate_bank": (ci, [vp, vp, sz, sz, vp, sz, sz, ci, vp, P(C.c_float)]),
         "sxfir_plan_bank": (ci, [vp, P(ci)]),
         "sxfir_plan_bank_band": (ci, [vp, ci, P(ci), P(ci)]),
+        # include/sxfir_bank_tx.h: the combiner bank, K translating interpolators summed in one pass
+        "sxfir_bank_tx_abi_version": (ci, []),
+        "sxfir_create_bank_interpolator": (ci, [P(vp), vp, ci, ci, ci, vp, vp, ci, ci, ci]),
+        "sxfir_interpolate_bank": (ci, [vp, vp, sz, sz, sz, vp, sz, P(sz), vp]),
+        "sxfir_time_interpolate_bank": (ci, [vp, vp, sz, sz, sz, vp, sz, ci, vp, P(C.c_float)]),
+        "sxfir_plan_bank_tx": (ci, [vp, P(ci)]),
+        "sxfir_plan_bank_tx_band": (ci, [vp, ci, P(ci), P(ci)]),
         # include/sxfir_arbitrary.h: arbitrary-rate resamplers
         "sxfir_arbitrary_abi_version": (ci, []),
         "sxfir_create_arbitrary": (ci, [P(vp), vp, ci, ci, u64, ci, ci, ci]),

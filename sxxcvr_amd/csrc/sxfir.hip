@@ -12,6 +12,7 @@
 #include "../../include/sxfir_translate_tx.h"
 #include "../../include/sxfir_arbitrary.h"
 #include "../../include/sxfir_bank.h"
+#include "../../include/sxfir_bank_tx.h"
 
 #include <hip/hip_runtime.h>
 
@@ -90,6 +91,7 @@
 #include "sxfir_resample.hip.h"                 // rational up / down: the generic kernel and 4/5 x 128 (include/sxfir_rational.h)
 #include "sxfir_arb.hip.h"                      // arbitrary rates: the generic kernel and 128 x 32 (include/sxfir_arbitrary.h)
 #include "sxfir_decim_bank.hip.h"               // the tuner bank: the generic kernel and /4 x 128 per band (include/sxfir_bank.h)
+#include "sxfir_interp_bank.hip.h"              // the combiner bank: the generic kernel and x4 x 128 per band, summed (include/sxfir_bank_tx.h)
 
 namespace {
 
@@ -132,3 +134,4 @@ inline size_t sample_bytes(int fmt) { return fmt == SXFIR_CF16 ? 4 : 8; }   // C
 #include "sxfir_translate.hip.h"   // sxfir_design_rotator, sxfir_create_translating, sxfir_create_translating_interpolator, sxfir_plan_translation, sxfir_plan_translation_tx (include/sxfir_translate.h, include/sxfir_translate_tx.h)
 #include "sxfir_arbitrary.hip.h"   // sxfir_create_arbitrary, sxfir_set_rate, sxfir_set_time, sxfir_plan_arbitrary, sxfir_resample_arbitrary, sxfir_time_resample_arbitrary, sxfir_arbitrary_outputs, sxfir_arbitrary_locate (include/sxfir_arbitrary.h)
 #include "sxfir_bank.hip.h"   // sxfir_create_bank, sxfir_decimate_bank, sxfir_time_decimate_bank, sxfir_plan_bank, sxfir_plan_bank_band (include/sxfir_bank.h)
+#include "sxfir_bank_tx.hip.h"   // sxfir_create_bank_interpolator, sxfir_interpolate_bank, sxfir_time_interpolate_bank, sxfir_plan_bank_tx, sxfir_plan_bank_tx_band (include/sxfir_bank_tx.h)

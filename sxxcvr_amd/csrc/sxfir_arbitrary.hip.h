@@ -106,7 +106,7 @@ static int check_arbitrary_io(const sxfir_plan *p, const CallIO &c)
 {
     if (p->kind != KIND_ARBITRARY)
         return fail(SXFIR_EINVAL, "sxfir_resample_arbitrary takes an arbitrary-rate plan (sxfir_create_arbitrary); this plan takes %s",
-                    p->kind == KIND_CHANNELIZER ? "sxfir_channelize" : p->kind == KIND_SYNTHESIZER ? "sxfir_synthesize" : p->kind == KIND_BANK ? "sxfir_decimate_bank"
+                    p->kind == KIND_CHANNELIZER ? "sxfir_channelize" : p->kind == KIND_SYNTHESIZER ? "sxfir_synthesize" : p->kind == KIND_BANK ? "sxfir_decimate_bank" : p->kind == KIND_BANK_TX ? "sxfir_interpolate_bank"
                     : p->kind == KIND_RATIONAL ? "sxfir_resample" : p->mode == SXFIR_DECIMATE ? "sxfir_decimate" : "sxfir_interpolate");
     // both kernels take the call's first output's time relative to the call in 64 bits, Q32.32 (arb_rel): a call that yields an
     // output has that time below n_in * 2^32

@@ -82,14 +82,15 @@ int sxfir_time_decimate_bank(sxfir_plan *p, const void *in_dev, size_t n_in, siz
 int sxfir_plan_bank(const sxfir_plan *p, int *nbands)
 {
     if (!p || !nbands) return fail(SXFIR_EINVAL, "NULL argument");
-    *nbands = p->bank_n;
+    *nbands = p->kind == KIND_BANK ? p->bank_n : 0;
     return SXFIR_OK;
 }
 
 int sxfir_plan_bank_band(const sxfir_plan *p, int band, int *num, int *den)
 {
     if (!p || !num || !den) return fail(SXFIR_EINVAL, "NULL argument");
-    if (band < 0 || band >= p->bank_n) return fail(SXFIR_EINVAL, "band %d of %d", band, p->bank_n);
+    const int n = p->kind == KIND_BANK ? p->bank_n : 0;             // (a combiner plan carries the same fields: sxfir_plan_bank_tx_band answers for it)
+    if (band < 0 || band >= n) return fail(SXFIR_EINVAL, "band %d of %d", band, n);
     *num = p->bank_num[band];
     *den = p->bank_den[band];
     return SXFIR_OK;

@@ -62,7 +62,7 @@ int sxfir_create_complex_interpolator(sxfir_plan **out, const float *taps_iq, in
 int sxfir_taps_are_complex(const sxfir_plan *p, int *is_complex)
 {
     if (!p || !is_complex) return fail(SXFIR_EINVAL, "NULL argument");
-    *is_complex = p->kind == KIND_COMPLEX || p->kind == KIND_BANK;
+    *is_complex = p->kind == KIND_COMPLEX || p->kind == KIND_BANK || p->kind == KIND_BANK_TX;
     return SXFIR_OK;
 }
 

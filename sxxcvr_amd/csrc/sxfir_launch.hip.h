@@ -24,8 +24,8 @@ struct CallIO {
     size_t out_stride;
     long long n_out;
     hipStream_t st;
-    size_t band_stride;       // channelizer and bank plans (sxfir_channelize, sxfir_decimate_bank): outputs between the bands of a channel; synthesizer plans
-                              // (sxfir_synthesize): inputs between them; else 0
+    size_t band_stride;       // channelizer and bank plans (sxfir_channelize, sxfir_decimate_bank): outputs between the bands of a channel; synthesizer and
+                              // combiner plans (sxfir_synthesize, sxfir_interpolate_bank): inputs between them; else 0
 };
 
 // What the tiled kernels' 16-byte stores need: an aligned output and, between channels, an even stride -- on CF16 storage the
@@ -39,7 +39,7 @@ static bool stores_aligned(const sxfir_plan *p, const CallIO &c)
     return (uintptr_t)c.out % 16 == 0 && (p->nchan == 1 || c.out_stride % q == 0) && ((p->kind != KIND_CHANNELIZER && p->kind != KIND_BANK) || c.band_stride % 2 == 0);
 }
 
-// Generic path: the next call's history goes to the plan's other buffer (stream_call swaps the two); a synthesizer's, band by band
+// Generic path: the next call's history goes to the plan's other buffer (stream_call swaps the two); a synthesizer's and a combiner's, band by band
 template <typename T>
 static void launch_history_of(sxfir_plan *p, const CallIO &c)
 {
@@ -48,6 +48,10 @@ static void launch_history_of(sxfir_plan *p, const CallIO &c)
     if (p->kind == KIND_SYNTHESIZER) {
         const int hb = p->hist_len / p->bands;
         hipLaunchKernelGGL(sxfir::synthesis_history_kernel<T>, dim3((unsigned)((hb + 255) / 256), (unsigned)p->nchan, (unsigned)p->bands), dim3(256), 0, c.st,
+                           next, hist, in, (long long)c.n_in, (long long)c.in_stride, (long long)c.band_stride, hb);
+    } else if (p->kind == KIND_BANK_TX) {
+        const int hb = p->hist_len / p->bank_n;
+        hipLaunchKernelGGL(sxfir::bank_tx_history_kernel<T>, dim3((unsigned)((hb + 255) / 256), (unsigned)p->nchan, (unsigned)p->bank_n), dim3(256), 0, c.st,
                            next, hist, in, (long long)c.n_in, (long long)c.in_stride, (long long)c.band_stride, hb);
     } else {
         hipLaunchKernelGGL(sxfir::history_kernel<T>, dim3((unsigned)((p->hist_len + 255) / 256), (unsigned)p->nchan), dim3(256), 0, c.st,
@@ -506,6 +510,46 @@ static sxfir::BankTileArgs bank_tile_args(const sxfir_plan *p, const CallIO &c, 
     return a;
 }
 
+// combiner plans (include/sxfir_bank_tx.h): every band's mixer by mixer_of's rule for the translating interpolator at the call's first
+// input (`consumed`), `halo` samples in front of it, and for the tiled kernel imix_tile_args' four steps per band (n_groups 0: the
+// generic kernel, which reads the mixer alone).  64-bit arithmetic here; every value handed over is below den.
+static void bank_tx_bands(const sxfir_plan *p, sxfir::BankTxBand (&band)[sxfir::BANK_MAX], long long halo, long long n_groups)
+{
+    for (int k = 0; k < p->bank_n; ++k) {
+        const long long den = p->bank_den[k], t = (den - p->bank_s[k]) % den;
+        const sxfir::Mixer m = mixer_of(p->bank_w[k], den, t, p->consumed, halo);
+        sxfir::BankTxBand &b = band[k];
+        b.w = m.w;
+        b.den = m.den;
+        b.step = m.step;
+        b.phase = m.phase;
+        b.lane_step = (unsigned)(2 * t % den);
+        b.instr_step = (unsigned)(128 * t % den);
+        b.tile_step = (unsigned)(256 * t % den);
+        b.stride_step = (unsigned)(n_groups % den * b.tile_step % den);
+    }
+}
+
+static sxfir::BankTxGenericArgs bank_tx_generic_args(const sxfir_plan *p, const CallIO &c)
+{
+    sxfir::BankTxGenericArgs a{generic_args(p, c, 0)};              // (the plain struct is its base)
+    a.hist_len = p->hist_len / p->bank_n;                           // a band's history; hist_stride stays the channel's
+    a.nbands = p->bank_n;
+    bank_tx_bands(p, a.band, 0, 0);
+    return a;
+}
+
+static sxfir::BankTxTileArgs bank_tx_tile_args(const sxfir_plan *p, const CallIO &c, const LaunchGeom &geom)
+{
+    sxfir::BankTxTileArgs a{interp_tile_args(p, c, geom, nullptr)};
+    a.taps = p->taps_scaled_dev;                                    // every band's pass-major tables
+    a.band_stride = (long long)c.band_stride;
+    a.nbands = p->bank_n;
+    // (the image of tile 0 starts InterpPass8::HIST samples in front of the call)
+    bank_tx_bands(p, a.band, 32, a.n_groups);
+    return a;
+}
+
 // the tiled translating interpolators: the steps between the chunks of two lanes, a lane's chunks, tiles and a wave's tiles
 static sxfir::InterpMixTileArgs imix_tile_args(const sxfir_plan *p, const CallIO &c, const LaunchGeom &geom)
 {
@@ -594,6 +638,7 @@ static int refuse_tiled(const sxfir_plan *p)
     if (p->kind == KIND_BANK)
         return fail(SXFIR_EUNSUPPORTED, "tiled bank needs a 16-byte aligned output, an even output stride, an even band stride and a call that "
                                         "starts on an output boundary (a stream position that is a multiple of 4)");
+    if (p->kind == KIND_BANK_TX) return fail(SXFIR_EUNSUPPORTED, "tiled combiner needs a 16-byte aligned output and an even output stride");
     if (p->kind == KIND_ARBITRARY)
         return fail(SXFIR_EUNSUPPORTED, "tiled arbitrary-rate resampler needs a 16-byte aligned output, an even output stride and a step in "
                                         "[2^31, 2^33] (step %llu)", (unsigned long long)p->arb_step);
@@ -635,6 +680,8 @@ static int launch_call(sxfir_plan *p, const CallIO &c, bool *history_done, const
         const long long first = p->mode == SXFIR_DECIMATE ? first_offset(p) : 0;        // (a rational plan is an interpolator)
         if (p->kind == KIND_BANK)       // a band per grid plane
             return launch(p->k.bank_generic, dim3(grid.x, grid.y, (unsigned)p->bank_n), 256, c.st, bank_generic_args(p, c, first));
+        if (p->kind == KIND_BANK_TX)    // the bands inside the thread: they meet in one output word
+            return launch(p->k.bank_tx_generic, grid, 256, c.st, bank_tx_generic_args(p, c));
         if (int rc = !p->mix_den ? launch(p->k.generic, grid, 256, c.st, generic_args(p, c, first))
                                  : launch(p->k.mix_generic, grid, 256, c.st, mix_generic_args(p, c, first))) return rc;
         if (key && key->hi > key->lo && key_pending) *key_pending = true;    // counted by the caller once the call is certain to commit
@@ -656,6 +703,9 @@ static int launch_call(sxfir_plan *p, const CallIO &c, bool *history_done, const
     case GEOM_RAT45: return launch(p->k.rat45, grid, threads, c.st, decim_tile_args(p, c, geom));
     case GEOM_MIX: return launch(p->k.mix, grid, threads, c.st, mix_tile_args(p, c, geom));
     case GEOM_BANK: return launch(p->k.bank, grid, threads, c.st, bank_tile_args(p, c, geom));
+    case GEOM_BANK_TX:
+        if (int rc = need_tap_table(p, TAPS_PASS8_CX, p->form->tiled)) return rc;
+        return launch(p->k.bank_tx, grid, threads, c.st, bank_tx_tile_args(p, c, geom));
     // resample_arb_kernel leaves the history to the generic path's pass (history_kernel)
     case GEOM_ARB:
         *history_done = false;
@@ -725,6 +775,7 @@ static int check_buffers(const sxfir_plan *p, const CallIO &c)
 }
 
 static const char *const RATIONAL_TAKES = "a rational plan takes sxfir_resample (include/sxfir_rational.h)";
+static const char *const BANK_TX_TAKES = "a combiner plan takes sxfir_interpolate_bank (include/sxfir_bank_tx.h)";
 static const char *const ARBITRARY_TAKES = "an arbitrary-rate plan takes sxfir_resample_arbitrary (include/sxfir_arbitrary.h)";
 
 // sxfir_decimate, sxfir_interpolate and sxfir_time_*: real and complex taps
@@ -734,6 +785,7 @@ static int check_io(const sxfir_plan *p, int mode, const CallIO &c)
     if (p->kind == KIND_ARBITRARY) return fail(SXFIR_EINVAL, "%s", ARBITRARY_TAKES);
     if (p->kind == KIND_SYNTHESIZER) return fail(SXFIR_EINVAL, "a synthesizer plan takes sxfir_synthesize (include/sxfir_synthesizer.h)");
     if (p->kind == KIND_BANK) return fail(SXFIR_EINVAL, "a bank plan takes sxfir_decimate_bank (include/sxfir_bank.h)");
+    if (p->kind == KIND_BANK_TX) return fail(SXFIR_EINVAL, "%s", BANK_TX_TAKES);
     if (p->mode != mode) return fail(SXFIR_EINVAL, "plan was created for the other direction");
     if (p->kind == KIND_CHANNELIZER) return fail(SXFIR_EINVAL, "a channelizer plan takes sxfir_channelize (include/sxfir_channelizer.h)");
     return check_buffers(p, c);
@@ -770,6 +822,7 @@ int sxfir_interpolate_keyed(sxfir_plan *p, const void *in_dev, size_t n_in, size
     if (p->kind == KIND_RATIONAL) return fail(SXFIR_EINVAL, "%s", RATIONAL_TAKES);
     if (p->kind == KIND_ARBITRARY) return fail(SXFIR_EINVAL, "%s", ARBITRARY_TAKES);
     if (p->kind == KIND_SYNTHESIZER) return fail(SXFIR_EINVAL, "a synthesizer plan takes sxfir_synthesize (include/sxfir_synthesizer.h): no keying count in its version 1");
+    if (p->kind == KIND_BANK_TX) return fail(SXFIR_EINVAL, "%s: no keying count in its version 1", BANK_TX_TAKES);
     if (p->mode != SXFIR_INTERPOLATE) return fail(SXFIR_EINVAL, "not an interpolator plan");
     if (p->fmt == SXFIR_CF16) return fail(SXFIR_EUNSUPPORTED, "the keying count is defined on CF32 input");
     if (!counter || ((uintptr_t)counter & 7)) return fail(SXFIR_EINVAL, "counter must be an 8-byte aligned device word");

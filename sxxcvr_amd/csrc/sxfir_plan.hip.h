@@ -23,7 +23,9 @@
 // time and output counts of its own (arb_outputs, sxfir_arb_index.h).
 // sxfir_create_bank (sxfir_bank.hip.h): KIND_BANK, a /ratio decimator with bank_n sets of complex taps (taps_dev: band k's planar a | b at
 // 2 ntaps k) and a mixer per band (bank_num, bank_den, bank_s, bank_w) -- one history, one position, K output rows.
-enum PlanKind { KIND_REAL = 0, KIND_COMPLEX = 1, KIND_CHANNELIZER = 2, KIND_SYNTHESIZER = 3, KIND_RATIONAL = 4, KIND_ARBITRARY = 5, KIND_BANK = 6 };
+// sxfir_create_bank_interpolator (sxfir_bank_tx.hip.h): KIND_BANK_TX, a x ratio interpolator with the bank's fields (bank_n tap sets, a mixer per
+// band) whose K results are summed -- one position, a history per band (hist_dev: bank_n x hist_len / bank_n samples per channel), one output row.
+enum PlanKind { KIND_REAL = 0, KIND_COMPLEX = 1, KIND_CHANNELIZER = 2, KIND_SYNTHESIZER = 3, KIND_RATIONAL = 4, KIND_ARBITRARY = 5, KIND_BANK = 6, KIND_BANK_TX = 7 };
 
 // The layout of a plan's second tap table (taps_scaled_dev); one function per layout below (second_tap_table).
 // TAPS_SCALED: taps * 2^-31 (exact) in tap order, for the /4 scalar-tap kernels on S32 wire words;
@@ -38,7 +40,7 @@ enum PlanKind { KIND_REAL = 0, KIND_COMPLEX = 1, KIND_CHANNELIZER = 2, KIND_SYNT
 enum TapTable { TAPS_SCALED = 0, TAPS_SUBSET8 = 1, TAPS_PASS8 = 2, TAPS_BLOCKS16 = 3, TAPS_PHASED = 4, TAPS_NONE = 5, TAPS_PASS8_CX = 6, TAPS_ARB = 7 };
 
 // Which kernel family a call launches (LaunchGeom::kind, sxfir_launch.hip.h)
-enum { GEOM_GENERIC = 0, GEOM_MULTI = 1, GEOM_WIDE = 2, GEOM_TILE = 3, GEOM_IPASS = 4, GEOM_ITILE = 5, GEOM_CX = 6, GEOM_CHAN4 = 7, GEOM_SYN4 = 8, GEOM_CHAN4X2 = 9, GEOM_SYN4X2 = 10, GEOM_ICX = 11, GEOM_RAT45 = 12, GEOM_MIX = 13, GEOM_IMIX = 14, GEOM_ARB = 15, GEOM_BANK = 16 };
+enum { GEOM_GENERIC = 0, GEOM_MULTI = 1, GEOM_WIDE = 2, GEOM_TILE = 3, GEOM_IPASS = 4, GEOM_ITILE = 5, GEOM_CX = 6, GEOM_CHAN4 = 7, GEOM_SYN4 = 8, GEOM_CHAN4X2 = 9, GEOM_SYN4X2 = 10, GEOM_ICX = 11, GEOM_RAT45 = 12, GEOM_MIX = 13, GEOM_IMIX = 14, GEOM_ARB = 15, GEOM_BANK = 16, GEOM_BANK_TX = 17 };
 
 // One typed kernel pointer per launch-argument family, and a plan's kernels: resolved once by the plan's creator
 // (resolve_kernels below), read by the occupancy query there and by the launches (sxfir_launch.hip.h).
@@ -56,6 +58,8 @@ typedef void (*InterpMixTileFn)(sxfir::InterpMixTileArgs);
 typedef void (*ArbTileFn)(sxfir::ArbTileArgs);
 typedef void (*BankGenericFn)(sxfir::BankGenericArgs);
 typedef void (*BankTileFn)(sxfir::BankTileArgs);
+typedef void (*BankTxGenericFn)(sxfir::BankTxGenericArgs);
+typedef void (*BankTxTileFn)(sxfir::BankTxTileArgs);
 struct KernelTable {
     const char *generic_name;    // the plan's generic kernel, as sxfir_launch_geometry reports it, and the instance: every plan of every
     GenericFn generic;           // kind has exactly one (generic_kernel below), the kernel of every call its form does not take
@@ -76,6 +80,8 @@ struct KernelTable {
     ArbTileFn arb;               // arbitrary-rate plans (include/sxfir_arbitrary.h): resample_arb_kernel (128 phases x 32 taps, CF32)
     BankGenericFn bank_generic;  // bank plans (include/sxfir_bank.h), in the place of `generic`: decim_bank_generic_kernel
     BankTileFn bank;             // ... and decim4_bank_kernel (/4 x 128 complex taps per band, CF32)
+    BankTxGenericFn bank_tx_generic;   // combiner plans (include/sxfir_bank_tx.h), in the place of `generic`: interp_bank_generic_kernel
+    BankTxTileFn bank_tx;        // ... and interp4_bank_kernel (x4 x 128 complex taps per band, CF32)
 };
 
 // What the geometry and launch code needs to know of a tiled kernel family (FORM_* below).  A plan has at most one, settled at
@@ -104,7 +110,7 @@ struct sxfir_plan {
     uint64_t arb_step;     // arbitrary-rate plans (nphases is `ratio`): input samples per output, Q32.32; else 0
     long long arb_t_index; // ... the time of the next output: whole input samples
     uint32_t arb_t_frac;   // ... and its fraction, Q0.32
-    int bands;             // the band kinds: 4 (= ratio, but for the oversampled plans); bank plans: bank_n; else 0.  A synthesizer's hist_dev holds
+    int bands;             // the band kinds: 4 (= ratio, but for the oversampled plans); bank and combiner plans: bank_n; else 0.  A synthesizer's hist_dev holds
                            // bands x hist_len / bands samples per channel, band k's at k * hist_len / bands
     int oversample;        // channelizer plans: bands / ratio -- 1 critically sampled (sxfir_create_channelizer), 2 each band at fs/2
                            // (sxfir_create_channelizer_os: ratio 2, bands 4); synthesizer plans likewise: 1 each band at fs/4
@@ -137,7 +143,7 @@ struct sxfir_plan {
     int mix_den, mix_num;  // ... its length (0: the plan has no mixer) and num mod den of the band centre num / den
     int mix_s;             // ... (num * ratio) mod den: table entries per output.  A translating INTERPOLATOR (include/sxfir_translate_tx.h:
                            // mode SXFIR_INTERPOLATE tells the two apart) carries the same three: its inputs are turned, by den - mix_s entries each
-    int bank_n;            // bank plans (include/sxfir_bank.h): the band count (0: not a bank); per band num mod den, den,
+    int bank_n;            // bank and combiner plans (include/sxfir_bank.h, include/sxfir_bank_tx.h): the band count (0: neither); per band num mod den, den,
     int bank_num[sxfir::BANK_MAX], bank_den[sxfir::BANK_MAX], bank_s[sxfir::BANK_MAX];   // ... (num * ratio) mod den,
     float *bank_w[sxfir::BANK_MAX];   // ... and the rotation table: bands of one den share one (free_plan frees each once)
     KernelTable k;         // the instances this plan launches (null: none in this build for that family)
@@ -179,6 +185,8 @@ static GenericKernel generic_kernel(int kind, int oversample, int mode, int fmt)
         return GenericKernel{"resample_arb_generic_kernel", fmt == SXFIR_CF16 ? (GenericFn)resample_arb_generic_kernel<CF16> : (GenericFn)resample_arb_generic_kernel<CF32>};
     case KIND_BANK:             // on an argument struct of its own (GenericArgs plus the bands): the instance is bank_generic_kernel's
         return GenericKernel{"decim_bank_generic_kernel", nullptr};
+    case KIND_BANK_TX:          // likewise (GenericArgs plus the bands): bank_tx_generic_kernel's
+        return GenericKernel{"interp_bank_generic_kernel", nullptr};
     case KIND_COMPLEX:
         if (rx) SXFIR_GENERIC(decim_cx_generic_kernel, S32, CF32);
         SXFIR_GENERIC(interp_cx_generic_kernel, CF32, S32);
@@ -206,6 +214,13 @@ static BankGenericFn bank_generic_kernel(int fmt)
 {
     using namespace sxfir;
     return fmt == SXFIR_CF32 ? decim_bank_generic_kernel<CF32, CF32> : fmt == SXFIR_CF16 ? decim_bank_generic_kernel<CF16, CF16> : decim_bank_generic_kernel<S32, CF32>;
+}
+
+// Combiner plans (include/sxfir_bank_tx.h), on BankTxGenericArgs: the three instances of a TX kind
+static BankTxGenericFn bank_tx_generic_kernel(int fmt)
+{
+    using namespace sxfir;
+    return fmt == SXFIR_CF32 ? interp_bank_generic_kernel<CF32> : fmt == SXFIR_CF16 ? interp_bank_generic_kernel<CF16> : interp_bank_generic_kernel<CF32, S32>;
 }
 
 // /8, /16, /32 with 32 taps per phase: decim_dense_kernel, non-temporal staging loads for the image rows no other tile reads
@@ -363,6 +378,9 @@ static const PlanForm FORM_ICX = {"interp_cx_pass_kernel", GEOM_ICX, TILE_IPASS,
 // interp_cx_pass_kernel<.., InterpMixTileArgs>: translating interpolators, x4 x 128 and x8 x 256 complex taps on CF32: the complex-tap instances' tile, threads,
 // start rule (any start), store rule, generations and tap tables
 static const PlanForm FORM_IMIX = {"interp_mix_pass_kernel", GEOM_IMIX, TILE_IPASS, 64, 1, 2, true, 8, 8, TAPS_PASS8_CX};
+// interp4_bank_kernel: combiner plans, x4 x 128 complex taps per band on CF32: the translating instance's tile, threads, start rule (any start),
+// store rule and generations; every band's two pass-major tables, band after band
+static const PlanForm FORM_BANK_TX = {"interp4_bank_kernel", GEOM_BANK_TX, TILE_IPASS, 64, 1, 2, true, 8, 8, TAPS_PASS8_CX};
 
 // resample45_kernel: rational 4/5 x 128 on CF32, tiles of Resample45::TILE_IN = 1280 inputs (256 periods of five), one wave per tile; a
 // call starts on a period (a stream position that is a multiple of 5).  Its prologue is light (the taps are re-loaded per tile), so a
@@ -435,6 +453,7 @@ static void resolve_kernels(sxfir_plan *p)
     k.generic_name = g.name;
     k.generic = g.fn;
     if (p->kind == KIND_BANK) k.bank_generic = bank_generic_kernel(p->fmt);
+    if (p->kind == KIND_BANK_TX) k.bank_tx_generic = bank_tx_generic_kernel(p->fmt);
     if (p->mix_den) {           // a translating plan's generic kernel has an argument struct of its own
         // (RX: the label of decim_cx_generic_kernel's mixer instances)
         k.generic_name = p->mode == SXFIR_DECIMATE ? "decim_mix_generic_kernel" : "interp_mix_generic_kernel";
@@ -451,6 +470,7 @@ static void resolve_kernels(sxfir_plan *p)
     case GEOM_CX: k.cx = sxfir::decim4_cx_kernel<sxfir::DecimTileArgs>; break;
     case GEOM_MIX: k.mix = sxfir::decim4_cx_kernel<sxfir::MixTileArgs>; break;
     case GEOM_BANK: k.bank = sxfir::decim4_bank_kernel; break;
+    case GEOM_BANK_TX: k.bank_tx = sxfir::interp4_bank_kernel; break;
     case GEOM_ICX: k.interp_cx = interp_cx_kernel<sxfir::InterpTileArgs>(p->ratio); break;
     case GEOM_IMIX: k.imix = interp_cx_kernel<sxfir::InterpMixTileArgs>(p->ratio); break;
     case GEOM_MULTI:
@@ -480,6 +500,7 @@ static const void *occupancy_instance(const sxfir_plan *p)
     case GEOM_CX: return (const void *)k.cx;
     case GEOM_MIX: return (const void *)k.mix;
     case GEOM_BANK: return (const void *)k.bank;
+    case GEOM_BANK_TX: return (const void *)k.bank_tx;
     case GEOM_ICX: return (const void *)k.interp_cx;
     case GEOM_IMIX: return (const void *)k.imix;
     case GEOM_CHAN4: return (const void *)k.chan4;
@@ -706,12 +727,20 @@ static void taps_arb(std::vector<float> &t, const float *taps, int ntaps, int P)
         for (int i = 0; i < T; ++i) t[(size_t)p * row + i] = taps[(T - 1 - i) * P + p % P];
 }
 
-// p->ntaps floats in the layout p->tap_table names (TAPS_PASS8_CX: twice as many, from the planar complex taps)
+// p->ntaps floats in the layout p->tap_table names (TAPS_PASS8_CX: twice as many, from the planar complex taps; a combiner plan:
+// that for every band, band k's two tables at 2 ntaps k)
 static std::vector<float> second_tap_table(const sxfir_plan *p, const float *taps)
 {
-    std::vector<float> t(taps, taps + (p->tap_table == TAPS_PASS8_CX ? 2 : 1) * (size_t)p->ntaps);
+    const size_t sets = p->kind == KIND_BANK_TX ? (size_t)p->bank_n : 1;
+    std::vector<float> t(taps, taps + (p->tap_table == TAPS_PASS8_CX ? 2 * sets : 1) * (size_t)p->ntaps);
     switch (p->tap_table) {
-    case TAPS_PASS8_CX: taps_pass8_cx(t, taps, p->ntaps, p->ratio); break;
+    case TAPS_PASS8_CX:
+        for (size_t k = 0; k < sets; ++k) {
+            std::vector<float> band(2 * (size_t)p->ntaps);
+            taps_pass8_cx(band, taps + 2 * (size_t)p->ntaps * k, p->ntaps, p->ratio);
+            std::copy(band.begin(), band.end(), t.begin() + 2 * (size_t)p->ntaps * k);
+        }
+        break;
     case TAPS_SCALED: taps_scaled(t, taps); break;
     case TAPS_SUBSET8: taps_subset8(t, taps, p->fmt); break;
     case TAPS_BLOCKS16: taps_blocks16(t, taps, p->ratio, p->rot, p->fmt); break;
@@ -918,8 +947,9 @@ int sxfir_reset(sxfir_plan *p, void *stream)
 int sxfir_set_history(sxfir_plan *p, const void *src_dev, size_t n, size_t stride, void *stream)
 {
     if (!p || !src_dev) return fail(SXFIR_EINVAL, "NULL argument");
-    if (p->kind == KIND_SYNTHESIZER)
-        return fail(SXFIR_EUNSUPPORTED, "sxfir_set_history has one stride: it cannot name the bands and the channels of a synthesizer plan's input");
+    if (p->kind == KIND_SYNTHESIZER || p->kind == KIND_BANK_TX)
+        return fail(SXFIR_EUNSUPPORTED, "sxfir_set_history has one stride: it cannot name the bands and the channels of a %s plan's input",
+                    p->kind == KIND_SYNTHESIZER ? "synthesizer" : "combiner");
     if (n < (size_t)p->hist_len) return fail(SXFIR_EINVAL, "history needs %d samples per channel, %zu given", p->hist_len, n);
     if (p->nchan > 1 && stride < n) return fail(SXFIR_EINVAL, "channel stride %zu shorter than the block (%zu)", stride, n);
     const size_t sb = sample_bytes(p->fmt);

@@ -59,7 +59,7 @@ static int check_rational_io(const sxfir_plan *p, const CallIO &c)
 {
     if (p->kind != KIND_RATIONAL)
         return fail(SXFIR_EINVAL, "sxfir_resample takes a rational plan (sxfir_create_rational); this plan takes %s",
-                    p->kind == KIND_CHANNELIZER ? "sxfir_channelize" : p->kind == KIND_SYNTHESIZER ? "sxfir_synthesize" : p->kind == KIND_BANK ? "sxfir_decimate_bank"
+                    p->kind == KIND_CHANNELIZER ? "sxfir_channelize" : p->kind == KIND_SYNTHESIZER ? "sxfir_synthesize" : p->kind == KIND_BANK ? "sxfir_decimate_bank" : p->kind == KIND_BANK_TX ? "sxfir_interpolate_bank"
                     : p->kind == KIND_ARBITRARY ? "sxfir_resample_arbitrary" : p->mode == SXFIR_DECIMATE ? "sxfir_decimate" : "sxfir_interpolate");
     return check_buffers(p, c);
 }

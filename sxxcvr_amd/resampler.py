@@ -742,6 +742,100 @@ class TranslatingBank(_Plan):
         return res[0] if squeeze else res
 
 
+class TranslatingCombiner(_Plan):
+    """A bank of frequency-translating interpolators (include/sxfir_bank_tx.h), TranslatingBank's way back: K base-band streams, each
+    turned to its own centre and interpolated x ratio with its own complex taps, summed into one wideband stream in one pass.
+    `taps`: complex [K, ntaps], band k's own; `centres`: K (num, den) pairs.  The output is the float32 sum, in band order, of
+    TranslatingInterpolator(taps[k], ratio, num_k, den_k) over band k's stream; with K = 1 it has that plan's bits.  One position and
+    a history per band inside the plan: stream state, contract, geometry and kernel choice are a x ratio interpolator's, the same
+    methods as Resampler (set_history_ptr is refused)."""
+
+    def __init__(self, taps, ratio, centres, nchan=1, fmt="CF32", device=0):
+        self._lib = load_sxfir()
+        self._plan = C.c_void_p()
+        taps = np.ascontiguousarray(taps, dtype=np.complex64)
+        centres = [(int(n), int(d)) for n, d in centres]
+        if taps.ndim != 2 or taps.shape[0] != len(centres):
+            raise ValueError("taps must be [K, ntaps] complex, one row per centre (%d centres)" % len(centres))
+        self.mode, self.ratio, self.nchan, self.fmt, self.ntaps = INTERPOLATE, int(ratio), int(nchan), _FMT[fmt], taps.shape[1]
+        num = (C.c_int * max(len(centres), 1))(*[n for n, _ in centres])
+        den = (C.c_int * max(len(centres), 1))(*[d for _, d in centres])
+        self._ck(self._lib.sxfir_create_bank_interpolator(C.byref(self._plan), taps.ctypes.data_as(C.c_void_p), taps.shape[1],
+                                                          int(ratio), len(centres), num, den, int(nchan), self.fmt, int(device)))
+
+    @property
+    def nbands(self):
+        """The band count K (sxfir_plan_bank_tx)."""
+        n = C.c_int()
+        self._ck(self._lib.sxfir_plan_bank_tx(self._plan, C.byref(n)))
+        return n.value
+
+    @property
+    def centres(self):
+        """The K (num mod den, den) pairs (sxfir_plan_bank_tx_band)."""
+        out = []
+        for k in range(self.nbands):
+            n, d = C.c_int(), C.c_int()
+            self._ck(self._lib.sxfir_plan_bank_tx_band(self._plan, k, C.byref(n), C.byref(d)))
+            out.append((n.value, d.value))
+        return out
+
+    @property
+    def complex_taps(self):
+        f = C.c_int()
+        self._ck(self._lib.sxfir_taps_are_complex(self._plan, C.byref(f)))
+        return bool(f.value)
+
+    def set_tx_threshold(self, threshold2):
+        self._ck(self._lib.sxfir_set_tx_threshold(self._plan, float(threshold2)))
+
+    def process_ptr(self, in_ptr, n_in, in_stride, band_stride, out_ptr, out_stride, stream=0):
+        """sxfir_interpolate_bank: band k of channel c is read at in_ptr + c * in_stride + k * band_stride (samples of the input
+        format), n_in inputs PER BAND; returns the wideband outputs per channel (ratio x n_in)."""
+        n_out = C.c_size_t()
+        self._ck(self._lib.sxfir_interpolate_bank(self._plan, C.c_void_p(in_ptr), n_in, in_stride, band_stride, C.c_void_p(out_ptr),
+                                                  out_stride, C.byref(n_out), C.c_void_p(stream)))
+        return n_out.value
+
+    def time_ptr(self, in_ptr, n_in, in_stride, band_stride, out_ptr, out_stride, iters, stream=0):
+        """Mean milliseconds of `iters` back-to-back launches of the call's kernel (sxfir_time_interpolate_bank); the state is left alone."""
+        ms = C.c_float()
+        self._ck(self._lib.sxfir_time_interpolate_bank(self._plan, C.c_void_p(in_ptr), n_in, in_stride, band_stride, C.c_void_p(out_ptr),
+                                                       out_stride, iters, C.c_void_p(stream), C.byref(ms)))
+        return ms.value
+
+    def process(self, x, out=None):
+        """x: CUDA tensor [K, n] or [nchan, K, n], possibly strided between bands and channels; complex64 (CF32 and S32 plans) or
+        int32 words (CF16: half pairs).  Returns [ratio * n], or [nchan, ratio * n] for a 3-D x: complex64, int32 words (CF16) or
+        int32 wire words [.., ratio * n, 2] (S32).  A caller-given `out` of that shape (or longer rows) supplies its own channel
+        stride."""
+        import torch
+        K = self.nbands
+        squeeze = x.dim() == 2
+        x3 = x.unsqueeze(0) if squeeze else x
+        if x3.dim() != 3 or x3.shape[0] != self.nchan or x3.shape[1] != K or (x3.shape[2] > 1 and x3.stride(2) != 1):
+            raise ValueError("expected a [nchan=%d, K=%d, n] tensor with unit sample stride" % (self.nchan, K))
+        n_in = x3.shape[2]
+        n_out = self.outputs_for(n_in)
+        if self.fmt == S32 and out is not None:
+            out = torch.view_as_complex(out.view(torch.float32))          # same 8 bytes per sample
+        if out is None:
+            out = torch.empty((self.nchan, n_out), dtype=x3.dtype, device=x3.device)
+        o2 = out.unsqueeze(0) if out.dim() == 1 else out
+        # the kernel writes through a raw pointer: a caller-supplied `out` must really hold the result
+        if (o2.dim() != 2 or o2.shape[0] != self.nchan or o2.shape[1] < n_out or (o2.shape[1] > 1 and o2.stride(1) != 1)
+                or o2.dtype != x3.dtype or o2.device != x3.device):
+            raise ValueError("out must be a [nchan=%d, >=%d] %s tensor with unit sample stride on %s" % (self.nchan, n_out, x3.dtype, x3.device))
+        got = self.process_ptr(x3.data_ptr(), n_in, x3.stride(0) if self.nchan > 1 else 0, max(x3.stride(1), n_in) if K > 1 else n_in,
+                               o2.data_ptr(), o2.stride(0) if self.nchan > 1 else max(n_out, 1),
+                               torch.cuda.current_stream(x3.device).cuda_stream)
+        assert got == n_out
+        res = o2[:, :n_out]
+        if self.fmt == S32:
+            res = torch.view_as_real(res).view(torch.int32)
+        return res[0] if squeeze else res
+
+
 class Synthesizer(_BandPlan):
     """The 4-band synthesizer (include/sxfir_synthesizer.h): `nbands` sub-bands of the x nbands raster into one wideband stream in one
     pass -- what Channelizer takes apart, put together.  `taps`: the REAL prototype low-pass of a x nbands interpolator
